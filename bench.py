@@ -1,6 +1,6 @@
 """bench.py -- SSD300-VGG16 train step throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = Model.SSD_300 forward + Losses.ssd (match, loss) + backward through every
@@ -13,6 +13,11 @@ Extra objects on that line:
                   events on the stream the kernels run on, against the f32-MFMA peak;
   cpu_baseline -- the oracle's torch-CPU restatement of the same step on this box's host cores
                   (rank 0, N=1 only, bounded sample).
+
+--dump-outputs DIR writes what rank 0's last timed step returned as DIR/<name>.npy (float32 /
+float64, under 64 MB; see dump_train_outputs).  The time-bounded spin-up leaves no SGD update
+behind, so with the same arguments the warm-up and timed steps see the same weights, momentum and
+batch on every run and two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -33,6 +38,8 @@ import torch.distributed as dist
 PER_GPU_BATCH = 32
 TRAIN_GFLOP_PER_IMAGE = 187.930        # BASELINE.md section 3 (fwd + dgrad + wgrad, no dgrad for conv1_1)
 PEAK_F32_MFMA_TFLOPS = 157.3           # MI355X_MICROARCH.md chip-level parameters
+DUMP_MAX_BYTES = 64 << 20              # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 21                  # --dump-outputs: elements of the parameter / gradient samples
 
 
 def synth_batch(bs: int, seed: int, dev):
@@ -591,6 +598,34 @@ def roofline_of(net, step, conv_dtype: str, ms: float, layers: bool = False) -> 
     return roof
 
 
+def dump_train_outputs(out_dir: str, last: dict, l1, l2, n_pos, trainer) -> dict:
+    """--dump-outputs: what the last timed train step handed its caller, one DIR/<name>.npy per array:
+      loss_loc, loss_conf, n_pos     float64 (1,): the un-normalised loss sums and the positive-prior count of the step (norm_mode 1)
+      params_sample, grads_sample    float32: the parameters after the step's SGD update and the gradient that made it, at the same
+                                     DUMP_SAMPLE flat-buffer positions (seeded choice; the full buffers are 105 MB each)
+      loc, conf                      float32 (k, priors, 4 / 21): the step's forward outputs for its first k images, k = the whole
+                                     batch unless that exceeds DUMP_MAX_BYTES (eager step only: the graph replay keeps them internal)
+    Returns the manifest that goes on the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: np.array([float(t.item())], np.float64) for name, t in (("loss_loc", l1), ("loss_conf", l2), ("n_pos", n_pos))}
+    n = trainer.n
+    pick = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(pick).to(trainer.flat_param.device)
+    arrays["params_sample"] = trainer.flat_param[idx].float().cpu().numpy()
+    arrays["grads_sample"] = trainer.flat_grad[:n][idx].float().cpu().numpy()
+    if "loc" in last:
+        room = DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values()) - (1 << 16)      # (1 << 16): the .npy headers
+        per_image = (last["loc"][0].numel() + last["conf"][0].numel()) * 4
+        k = min(last["loc"].shape[0], room // per_image)
+        arrays["loc"] = last["loc"][:k].float().cpu().numpy()
+        arrays["conf"] = last["conf"][:k].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total < DUMP_MAX_BYTES, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "bytes": total, "arrays": {name: list(a.shape) for name, a in arrays.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -649,9 +684,16 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="plumbing check: start the ranks, init the process group, all-reduce one number, print the world size and stop "
                          "before anything touches a GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (losses, forward outputs, samples of the updated parameters "
+                         "and of their gradient) to DIR/<name>.npy; train workload only")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "train":
+        raise SystemExit("--dump-outputs: only the train workload writes its outputs")
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves, one process per GPU, BEFORE
     # anything in this process touches the GPU (a process that has initialised HIP must not be replaced or forked into ranks).
@@ -690,7 +732,7 @@ def main():
         note("live traffic: two rocprofv3 --pmc child runs (FETCH_SIZE, WRITE_SIZE)")
         # the same engine flags as this run (later options win): one step, every kernel on one stream, none of the extra legs
         tail = sys.argv[1:] + ["--steps", "1", "--warmup", "1", "--spinup-seconds", "0", "--no-cpu-baseline", "--no-bf16-leg", "--no-overlap-tail",
-                               "--live-traffic", "off", "--graph-step", "off"]
+                               "--live-traffic", "off", "--graph-step", "off", "--dump-outputs", ""]
         _LIVE_PMC = live_traffic_passes(tail)
         _LIVE_PMC["conv_dtype"] = args.conv_dtype
         note("live traffic: " + (_LIVE_PMC.get("note") or "done"))
@@ -778,9 +820,13 @@ def main():
     if args.variant == 512:
         x = torch.randn(bs, 3, 512, 512, generator=torch.Generator().manual_seed(1234 + rank)).to(dev)
 
+    last = {}                                              # --dump-outputs: the forward outputs of the latest eager step
+
     def eager_step():
         trainer.zero_grad()
         loc, conf = net(x)
+        if args.dump_outputs:
+            last["loc"], last["conf"] = loc.detach(), conf.detach()
         l1, l2, n_pos = Losses.ssd((loc, conf), classes, boxes, norm_mode=1, with_n_pos=True)     # un-normalised sums (ddp.py)
         (l1 + l2).backward()
         trainer.reduce_and_step(n_pos)
@@ -811,6 +857,9 @@ def main():
     spin_steps, spin_t0 = 0, time.perf_counter()
     if args.spinup_seconds > 0:
         note(f"spin-up: untimed steps for {args.spinup_seconds:.1f} s (device clock ramp)")
+        # how many steps fit in the spin-up depends on the device's speed: its SGD updates are undone below, so that the warm-up and
+        # timed steps start from the same weights and momentum on every run
+        state0 = (trainer.flat_param.clone(), trainer.flat_mom.clone(), trainer._has_momentum, trainer.steps)
         while True:
             for _ in range(5):
                 step()
@@ -823,6 +872,13 @@ def main():
                 go = bool(t.item())
             if not go:
                 break
+        with torch.no_grad():
+            trainer.flat_param.copy_(state0[0])
+            trainer.flat_mom.copy_(state0[1])
+        trainer._has_momentum, trainer.steps = state0[2], state0[3]
+        net.invalidate_weight_cache()
+        del state0
+        torch.cuda.synchronize()
     note(f"{args.warmup} warm-up + {args.steps} timed steps")
     for _ in range(args.warmup):
         step()
@@ -843,6 +899,10 @@ def main():
     ms = elapsed / args.steps * 1e3
     ips = bs * world * args.steps / elapsed
     note(f"timed: {ms:.3f} ms/step")
+    dumped = None
+    if args.dump_outputs and rank == 0:                    # before anything below runs another step over the same buffers
+        dumped = dump_train_outputs(args.dump_outputs, last if gstep is None else {}, l1, l2, n_pos_local, trainer)
+        note(f"outputs of the last timed step: {dumped['bytes'] / 2**20:.1f} MB in {args.dump_outputs}")
     # host-side enqueue time of ONE step into an empty queue (diagnostic: the step is GPU-bound while this stays below
     # ms_per_step; several steps back to back would measure the queue's back-pressure instead)
     host_ms = host_eager_ms = 0.0
@@ -921,6 +981,8 @@ def main():
                                       if gstep is not None else {"form": "eager: every kernel launched from Python"}),
                       "shader_clock_mhz_during_timed_steps": round(mhz, 0),
                       "f32_mfma_peak_at_that_clock_tflops": round(PEAK_F32_MFMA_TFLOPS * mhz / 2400.0, 1)}}
+    if dumped is not None:
+        out["dump_outputs"] = dumped
 
     # ---- roofline of the dominant kernel: per-launch HIP events on the launch stream -----------------
     if not args.no_roofline and rank != 0:

@@ -307,6 +307,46 @@ def test_bench_gpus_n_starts_n_ranks_itself():
     assert bad.returncode != 0 and "WORLD_SIZE=4" in (bad.stderr + bad.stdout) and '"metric"' not in bad.stdout
 
 
+def test_bench_refuses_arguments_it_cannot_honour():
+    """No timed step to report (--steps 0), and --dump-outputs on a workload that does not write its outputs, stop before any GPU
+    is touched instead of printing a line that says something else was measured."""
+    import subprocess
+    import sys
+    for argv, msg in ((["--steps", "0"], "--steps must be >= 1"), (["--warmup", "-1"], "--steps must be >= 1"),
+                      (["--workload", "decode", "--dump-outputs", "d"], "only the train workload")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and msg in (r.stderr + r.stdout), (argv, r.stderr[-2000:])
+        assert '"metric"' not in r.stdout
+
+
+@pytest.mark.parametrize("bs", [2, 32, 96])
+def test_bench_dump_outputs_files(tmp_path, bs):
+    """bench.py --dump-outputs: float32 / float64 .npy files under 64 MB in all; the parameter and gradient samples sit at the same
+    seeded positions of the flat buffers on every call; the forward outputs keep whole leading images when the batch is too big."""
+    import types
+    import bench
+    n = 16_000_000                                                # (< 2^24: every position is exact in float32)
+    g = torch.Generator().manual_seed(0)
+    tr = types.SimpleNamespace(n=n, flat_param=torch.arange(n, dtype=torch.float32), flat_grad=torch.randn(n + 64, generator=g))
+    last = {"loc": torch.randn(bs, 8732, 4, generator=g), "conf": torch.randn(bs, 8732, 21, generator=g)}
+    l1, l2, npos = torch.tensor(1.5), torch.tensor(2.25), torch.tensor(7.0)
+    man = bench.dump_train_outputs(str(tmp_path / "a"), last, l1, l2, npos, tr)
+    files = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(files) == {"loss_loc", "loss_conf", "n_pos", "params_sample", "grads_sample", "loc", "conf"} == set(man["arrays"])
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 64 << 20
+    assert files["loss_loc"].tolist() == [1.5] and files["loss_conf"].tolist() == [2.25] and files["n_pos"].tolist() == [7.0]
+    pos = files["params_sample"].astype(np.int64)                 # flat_param[i] == i: the sample's own positions
+    assert len(pos) == bench.DUMP_SAMPLE and np.all(np.diff(pos) > 0) and pos[-1] < n
+    assert np.array_equal(files["grads_sample"], tr.flat_grad[torch.from_numpy(pos)].numpy())
+    k = files["loc"].shape[0]
+    assert (k == bs if bs <= 32 else 32 <= k < bs) and files["conf"].shape == (k, 8732, 21)
+    assert np.array_equal(files["loc"], last["loc"][:k].numpy()) and np.array_equal(files["conf"], last["conf"][:k].numpy())
+    bench.dump_train_outputs(str(tmp_path / "b"), {}, l1, l2, npos, tr)                 # graph step: no forward outputs
+    assert sorted(os.listdir(tmp_path / "b")) == sorted(f"{k}.npy" for k in ("loss_loc", "loss_conf", "n_pos", "params_sample", "grads_sample"))
+    assert np.array_equal(np.load(tmp_path / "b" / "params_sample.npy"), files["params_sample"])
+
+
 def test_photometric_draws_equal_reference(gold_dir):
     """`Dataset.plan_photometric` == the order and factors Util.photometric_distort (Util.py:752-780) applies on the same
     seeded `random` stream (recorded from the reference's own function), and it leaves the stream at the same position."""
