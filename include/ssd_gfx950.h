@@ -508,6 +508,43 @@ int ssd_graph_node_counts(void* graph, int* kernel_nodes, int* total_nodes);
 int ssd_sgd_momentum(float* param, const float* grad, float* momentum_buf, size_t n, float lr, float momentum,
                      float weight_decay, const float* grad_scale_dev, int first_step, void* stream);
 
+/* ---- BatchNorm2d in training mode, Dropout / Dropout2d (SSD_resnet34 train mode: Model.py:24,56-70,72-126 and
+ * torchvision's BasicBlock).  Tensors are [M][ld] f32 rows whose first C columns are the channels (M = N*H*W), C % 4 == 0,
+ * ld % 4 == 0, rows 16-byte aligned.  Reductions use fixed-order slab partials (no atomics): results are bitwise reproducible.
+ *
+ * Dropout generator: Philox4x32-10 with key = {lo32(seed), hi32(seed)}; element idx of site `site` reads word (idx & 3) of
+ * philox({lo32(idx >> 2), hi32(idx >> 2), site, 0}) and is kept iff (word >> 8) * 2^-24 < 1 - p (float); kept values are scaled by
+ * 1/(1-p).  drop_mode 0: none; 1: elementwise nn.Dropout, idx = row*C + c; 2: nn.Dropout2d per (sample, channel),
+ * idx = n*C + c with n = row / HW. */
+
+/* workspace bytes of ssd_bn_train_stats / ssd_bn_train_bwd for M rows of C channels */
+size_t ssd_bn_workspace(size_t M, int C);
+
+/* batch mean and biased variance over the M rows (Welford per thread, Chan merges in a fixed order); writes mean, invstd =
+ * 1/sqrt(var+eps), scale = gamma*invstd, shift = beta - mean*scale (C floats each), updates running_mean / running_var (unbiased
+ * variance, `momentum` weight) and num_batches_tracked += 1 when those are non-NULL.  gamma / beta NULL: 1 / 0.  M >= 2. */
+int ssd_bn_train_stats(const float* x, int ldx, size_t M, int C, const float* gamma, const float* beta, float eps, float momentum,
+                       float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* invstd,
+                       float* scale, float* shift, void* workspace, size_t workspace_bytes, void* stream);
+
+/* y = drop( act( x*scale + shift [+ res*res_scale + res_shift  |  + res] ) ), act = ReLU if relu; res / res_scale / res_shift may
+ * be NULL (res_scale and res_shift together).  x may alias y (in place). */
+int ssd_bn_apply(const float* x, int ldx, size_t M, int C, const float* scale, const float* shift, const float* res, int ldr,
+                 const float* res_scale, const float* res_shift, int relu, int drop_mode, float p, uint64_t seed, int site, int HW,
+                 float* y, int ldy, void* stream);
+
+/* Backward of y = drop(BN(x)): g = dy * dropout factor, xhat = (x - mean)*invstd (mean / invstd from ssd_bn_train_stats);
+ * sums[0..C) = sum g (dbeta), sums[C..2C) = sum g*xhat (dgamma); dgamma / dbeta (optional) written, or added to if accumulate;
+ * dx (optional, may alias dy) = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)), zeroed where x <= 0 if relu_mask (the BatchNorm
+ * follows a ReLU and x is its output). */
+int ssd_bn_train_bwd(const float* dy, int ldd, const float* x, int ldx, size_t M, int C, const float* mean, const float* invstd,
+                     const float* gamma, int drop_mode, float p, uint64_t seed, int site, int HW, int relu_mask, float* sums,
+                     float* dgamma, float* dbeta, int accumulate, float* dx, int lddx, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* out[i] = 1 if dropout index i of (seed, site) is kept, else 0; n % 4 == 0.  A testing aid: the masks a forward used. */
+int ssd_dropout_mask(uint8_t* out, size_t n, float p, uint64_t seed, int site, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
 _Z = C.c_size_t
+_U64 = C.c_uint64
 _G = C.POINTER(ConvGeom)
 
 # name -> (restype, argtypes); must list every symbol declared in include/ssd_gfx950.h
@@ -181,6 +182,11 @@ SIGNATURES = {
     "ssd_decode_nms_batch_workspace": (_Z, [_I, _I, _I]),
     "ssd_decode_nms_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_sgd_momentum": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P, _I, _P]),
+    "ssd_bn_workspace": (_Z, [_Z, _I]),
+    "ssd_bn_train_stats": (_I, [_P, _I, _Z, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ssd_bn_apply": (_I, [_P, _I, _Z, _I, _P, _P, _P, _I, _P, _P, _I, _I, _F, _U64, _I, _I, _P, _I, _P]),
+    "ssd_bn_train_bwd": (_I, [_P, _I, _P, _I, _Z, _I, _P, _P, _P, _I, _F, _U64, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _Z, _P]),
+    "ssd_dropout_mask": (_I, [_P, _Z, _F, _U64, _I, _P]),
 }
 
 _lib = None

@@ -517,6 +517,132 @@ def channel_affine(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, re
     return out
 
 
+# ---- BatchNorm in training mode / dropout (csrc/batchnorm.hip) --------------------------------------------------------------------
+DROP_NONE, DROP_ELEMENT, DROP_CHANNEL = 0, 1, 2
+
+
+def _bn_rows(x: torch.Tensor, c: int, ld: Optional[int], name: str) -> Tuple[int, int]:
+    """(M, ld) of x seen as [M][ld] rows whose first c columns are the channels"""
+    _req(x, name)
+    ld = c if ld is None else ld
+    if c <= 0 or c % 4 != 0 or ld < c or ld % 4 != 0 or x.numel() % ld != 0:
+        raise ValueError(f"{name}: {x.numel()} elements are not rows of ld = {ld} holding C = {c} channels (C % 4 == 0, ld % 4 == 0)")
+    return x.numel() // ld, ld
+
+
+def _drop_args(drop) -> Tuple[int, float, int, int, int]:
+    """drop = None or (mode, p, seed, site, hw) -> the C arguments"""
+    if drop is None:
+        return DROP_NONE, 0.0, 0, 0, 1
+    mode, p, seed, site, hw = drop
+    if mode not in (DROP_NONE, DROP_ELEMENT, DROP_CHANNEL) or not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout mode {mode} / p {p}")
+    return int(mode), float(p), int(seed) & (2 ** 64 - 1), int(site), int(hw)
+
+
+def _per_channel(t: Optional[torch.Tensor], c: int, name: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _req(t, name)
+    if t.numel() != c:
+        raise ValueError(f"{name}: {t.numel()} entries for {c} channels")
+    return t
+
+
+def bn_train_stats(x: torch.Tensor, c: int, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float, momentum: float,
+                   running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
+                   num_batches_tracked: Optional[torch.Tensor] = None, ld: Optional[int] = None) -> torch.Tensor:
+    """Training-mode BatchNorm statistics of the first c columns of x's [M][ld] rows -> (4, c): mean, invstd, scale, shift.
+    Updates the running buffers in place (when given) on the device."""
+    m, ld = _bn_rows(x, c, ld, "x")
+    if m < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got {m} rows of {c} channels")
+    for t, n in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _per_channel(t, c, n)
+    if num_batches_tracked is not None:
+        _req(num_batches_tracked, "num_batches_tracked", torch.int64)
+    out = torch.empty((4, c), device=x.device, dtype=torch.float32)
+    lib = _lib.load()
+    nbytes = lib.ssd_bn_workspace(m, c)
+    ws = workspace(nbytes, x.device, "bn")
+    check(lib.ssd_bn_train_stats(x.data_ptr(), ld, m, c, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean),
+                                 _ptr(running_var), _ptr(num_batches_tracked), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                 out[3].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "bn_train_stats")
+    return out
+
+
+def bn_apply(x: torch.Tensor, c: int, scale: torch.Tensor, shift: torch.Tensor, relu: bool = False, res: Optional[torch.Tensor] = None,
+             res_scale: Optional[torch.Tensor] = None, res_shift: Optional[torch.Tensor] = None, drop=None,
+             out: Optional[torch.Tensor] = None, ld: Optional[int] = None, res_ld: Optional[int] = None,
+             out_ld: Optional[int] = None) -> torch.Tensor:
+    """out = drop(act(x*scale + shift [+ res*res_scale + res_shift | + res])) over the first c columns; out may be x.
+    drop = None or (mode, p, seed, site, hw) with mode DROP_ELEMENT / DROP_CHANNEL."""
+    m, ld = _bn_rows(x, c, ld, "x")
+    _per_channel(scale, c, "scale"); _per_channel(shift, c, "shift")
+    if res is not None:
+        mr, res_ld = _bn_rows(res, c, res_ld, "res")
+        if mr != m:
+            raise ValueError("res rows")
+    if (res_scale is None) != (res_shift is None) or (res_scale is not None and res is None):
+        raise ValueError("res_scale and res_shift go together, with res")
+    _per_channel(res_scale, c, "res_scale"); _per_channel(res_shift, c, "res_shift")
+    if out is None:
+        out = torch.empty((m, c), device=x.device, dtype=torch.float32) if out_ld is None else \
+            torch.zeros((m, out_ld), device=x.device, dtype=torch.float32)
+    mo, out_ld = _bn_rows(out, c, out_ld, "out")
+    if mo != m:
+        raise ValueError("out rows")
+    mode, p, seed, site, hw = _drop_args(drop)
+    if mode == DROP_CHANNEL and m % hw != 0:
+        raise ValueError("rows are not a whole number of samples")
+    check(_lib.load().ssd_bn_apply(x.data_ptr(), ld, m, c, scale.data_ptr(), shift.data_ptr(), _ptr(res), res_ld or 0, _ptr(res_scale),
+                                   _ptr(res_shift), int(relu), mode, p, seed, site, hw, out.data_ptr(), out_ld, _stream()), "bn_apply")
+    return out
+
+
+def bn_train_bwd(dy: torch.Tensor, x: torch.Tensor, c: int, mean: torch.Tensor, invstd: torch.Tensor, gamma: Optional[torch.Tensor],
+                 drop=None, relu_mask: bool = False, dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None,
+                 accumulate: bool = False, dx: Optional[torch.Tensor] = None, want_dx: bool = True, ld_dy: Optional[int] = None,
+                 ld_x: Optional[int] = None, ld_dx: Optional[int] = None):
+    """Backward of drop(BN_train(x)) (after a ReLU when relu_mask) -> (dx or None, sums (2, c): sum g, sum g*xhat).
+    dx may be dy (in place); dgamma / dbeta are written, or added to when accumulate."""
+    m, ld_dy = _bn_rows(dy, c, ld_dy, "dy")
+    mx, ld_x = _bn_rows(x, c, ld_x, "x")
+    if mx != m:
+        raise ValueError("x rows")
+    if m < 2:
+        raise ValueError("BatchNorm backward needs more than 1 value per channel")
+    for t, n in ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma"), (dgamma, "dgamma"), (dbeta, "dbeta")):
+        _per_channel(t, c, n)
+    if want_dx:
+        if dx is None:
+            dx = torch.empty((m, c), device=dy.device, dtype=torch.float32) if ld_dx is None else \
+                torch.zeros((m, ld_dx), device=dy.device, dtype=torch.float32)
+        md, ld_dx = _bn_rows(dx, c, ld_dx, "dx")
+        if md != m:
+            raise ValueError("dx rows")
+    else:
+        dx, ld_dx = None, 0
+    mode, p, seed, site, hw = _drop_args(drop)
+    if mode == DROP_CHANNEL and m % hw != 0:
+        raise ValueError("rows are not a whole number of samples")
+    sums = torch.empty((2, c), device=dy.device, dtype=torch.float32)
+    lib = _lib.load()
+    ws = workspace(lib.ssd_bn_workspace(m, c), dy.device, "bn")
+    check(lib.ssd_bn_train_bwd(dy.data_ptr(), ld_dy, x.data_ptr(), ld_x, m, c, mean.data_ptr(), invstd.data_ptr(), _ptr(gamma), mode, p,
+                               seed, site, hw, int(relu_mask), sums.data_ptr(), _ptr(dgamma), _ptr(dbeta), int(accumulate), _ptr(dx),
+                               ld_dx, ws.data_ptr(), ws.numel(), _stream()), "bn_train_bwd")
+    return dx, sums
+
+
+def dropout_mask(n: int, p: float, seed: int, site: int, device) -> torch.Tensor:
+    """bool keep flags of dropout indices 0..n-1 of (seed, site): the generator of bn_apply, materialised (n % 4 == 0)"""
+    out = torch.empty((n,), device=device, dtype=torch.uint8)
+    _, p, seed, site, _ = _drop_args((DROP_ELEMENT, p, seed, site, 1))
+    check(_lib.load().ssd_dropout_mask(out.data_ptr(), n, p, seed, site, _stream()), "dropout_mask")
+    return out.bool()
+
+
 def first_weight_rows(w_oihw: torch.Tensor) -> torch.Tensor:
     """(Co,3,3,3) OIHW -> (Co,1,32): rows ordered like im2col_first's columns, zero padded."""
     co = w_oihw.shape[0]
