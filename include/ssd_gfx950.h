@@ -402,8 +402,9 @@ size_t ssd_l2norm_bwd_workspace(int M, int C);
 int ssd_l2norm_bwd(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma,
                    int M, int C, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- head output <-> (bs,P,4)/(bs,P,21) (Model.py:212-235 permute+view+cat) ------------
- * packed[m][0:4A] = loc channels, packed[m][4A:25A] = conf channels of pixel m=(n,h,w);
+/* ---- head output <-> (bs,P,4)/(bs,P,n_classes) (Model.py:212-235 permute+view+cat) ------------
+ * n_classes = conf width C (foreground classes + background), 21 for VOC.
+ * packed[m][0:4A] = loc channels, packed[m][4A:(4+C)A] = conf channels of pixel m=(n,h,w);
  * prior index = prior_off + (h*W+w)*A + a. */
 int ssd_heads_scatter(const float* packed, int ld, float* loc, float* conf, int N, int HW, int A,
                       int prior_off, int P, int n_classes, void* stream);
@@ -411,7 +412,9 @@ int ssd_heads_gather(const float* dloc, const float* dconf, float* packed, int l
                      int prior_off, int P, int n_classes, void* stream);
 
 /* ---- MultiBox loss (Losses.py:119-199 ssd + ssd1_; Util.py:57-63,98-102,252-301) -------
- * gt_boxes (n_gt,4) xyxy f32, gt_classes (n_gt) f32 values 0..19, img_start (bs+1) int32
+ * n_classes = conf width C, 2..256 (foreground classes + background; background = C-1 is the last column).
+ * gt_boxes (n_gt,4) xyxy f32, gt_classes (n_gt) f32 values 0..C-2 (other values: unspecified losses, but every
+ * kernel clamps the label into the row -- no access outside the tensors), img_start (bs+1) int32
  * prefix offsets into them (every image needs >= 1 box: checked by the caller on the host,
  * the reference raises there).  priors_cxcywh/priors_xyxy (P,4).
  * Outputs: losses[0]=loc_loss, losses[1]=conf_loss, losses[2]=n_pos (as float);
@@ -421,7 +424,8 @@ int ssd_heads_gather(const float* dloc, const float* dconf, float* packed, int l
  * norm_mode 1: un-normalised sums (loc: sum|d|/4, conf: sum CE) and gradients of those,
  *              for data-parallel runs that divide by the global n_pos after the all-reduce.
  * Three kernel launches (per-prior matching + cross entropy, wide; per-image forced matches + hard-negative selection; losses +
- * gradients, wide); ssd_tune_set_loss_form(0) selects the four-launch form of rounds 1-3 (cross-check). */
+ * gradients, wide); ssd_tune_set_loss_form(0) selects the four-launch form of rounds 1-3 (cross-check).  C <= 64 stages conf rows
+ * in LDS; 64 < C <= 256 runs the wide-row forms of the first and last kernel (a wave across a row's classes, nothing staged per class). */
 int ssd_tune_set_loss_form(int three_launch);
 size_t ssd_multibox_loss_workspace(int bs, int P, int n_gt);
 int ssd_multibox_loss(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
@@ -431,8 +435,10 @@ int ssd_multibox_loss(const float* loc, const float* conf, const float* gt_boxes
                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- decode + per-class NMS + top-k (Losses.py:11-98 inference; Util.py:86-96) ----------
- * l_ (P,4), c_ (P,n_classes) of ONE image.  Outputs (capacity top_k): boxes (top_k,4) xyxy
- * scaled by (img_w,img_h,img_w,img_h), classes int64, probs f32, prior_ids int32, count int32[1]. */
+ * l_ (P,4), c_ (P,n_classes) of ONE image, n_classes = conf width C, 2..256 (background = C-1 is never a detection).
+ * Outputs (capacity top_k): boxes (top_k,4) xyxy scaled by (img_w,img_h,img_w,img_h), classes int64 (0..C-2), probs f32,
+ * prior_ids int32, count int32[1].  Workspace: about 52 bytes per (class, prior, image) -- (C-1) * P candidate slots per image;
+ * at P = 8732 and B = 32: 0.30 GB for C = 21, 1.17 GB for C = 81, 3.7 GB for C = 256. */
 size_t ssd_decode_nms_workspace(int P, int n_classes);
 int ssd_decode_nms(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
                    float min_score, float iou_threshold, int top_k, float img_w, float img_h,

@@ -89,8 +89,9 @@ def _pack_targets(tr_classes: Sequence[torch.Tensor], tr_bboxs: Sequence[torch.T
 
 
 def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = False):
-    """outputs = (loc (bs,8732,4), conf (bs,8732,21)); tr_classes: list of (n_i,) float tensors with values
-    0..19; tr_bboxs: list of (n_i,4) xyxy fractional boxes.  Returns (loc_loss, conf_loss) as 0-dim tensors
+    """outputs = (loc (bs,8732,4), conf (bs,8732,C)); tr_classes: list of (n_i,) float tensors with values
+    0..C-2 (C = conf.shape[-1] = foreground classes + background, 21 for VOC; background = C-1); tr_bboxs: list of
+    (n_i,4) xyxy fractional boxes.  Returns (loc_loss, conf_loss) as 0-dim tensors
     that support `+`, `.item()` and `.backward()` (train_function.py:82-94).
     with_n_pos: also return this call's number of positive priors (0-dim device tensor) -- the data-parallel step
     (ddp.py) takes it from here, not from the module global `last_match`, so two models / threads cannot mix theirs up."""
@@ -120,7 +121,8 @@ draw_hook = None      # optional callable(image_path_or_size, boxes, labels, pro
 
 
 def inference(l_, c_, index, top_k=200, phase='train', toDraw=True, min_score=0.2, iou_threshold=0.45):
-    """l_ (8732,4) predicted offsets, c_ (8732,21) class scores of ONE image.  `index` is either the
+    """l_ (8732,4) predicted offsets, c_ (8732,C) class scores of ONE image (C = foreground classes + background, 2..256;
+    detections carry class ids 0..C-2).  `index` is either the
     reference's dataset index (image size read from `all_images[phase][index]`) or an (img_w, img_h)
     pair.  Returns (boxes (K,4) pixel xyxy, classes (K,) int64, probs (K,)) with K <= top_k, or
     ([], [], []) when nothing reaches min_score (reference Losses.py:62-63).  Drawing (Losses.py:92-97) is
@@ -136,7 +138,9 @@ def inference(l_, c_, index, top_k=200, phase='train', toDraw=True, min_score=0.
         return [], [], []
     inference.last_prior_ids = ids[:k]
     if toDraw and draw_hook is not None:
-        draw_hook(index, boxes[:k], [class_to_label[int(i)] for i in classes[:k].tolist()], probs[:k])
+        ids_ = classes[:k].tolist()
+        # VOC names for the reference's 21-column model, integer class ids for any other class count
+        draw_hook(index, boxes[:k], [class_to_label[int(i)] for i in ids_] if c_.shape[-1] == len(class_to_label) else ids_, probs[:k])
     return boxes[:k], classes[:k], probs[:k]
 
 

@@ -1,6 +1,6 @@
 """`Model.SSD_300` with the reference's constructor, attribute / parameter names and
 `forward(x) -> (loc (bs,8732,4), conf (bs,8732,21))` contract (reference
-Model.py:128-235), computed by the gfx950 kernels of libssd_gfx950.so.
+Model.py:128-235; `SSD_300(n_classes=K)` gives conf rows of K + 1 columns), computed by the gfx950 kernels of libssd_gfx950.so.
 
 The module tree exists to own the `nn.Parameter`s under the reference's
 state-dict names (so `train.py`'s optimizer groups, `.to(device)`,
@@ -12,6 +12,7 @@ L2-norm kernels) through one `torch.autograd.Function`.
 """
 from __future__ import annotations
 
+import numbers
 from typing import Dict, List, Optional
 
 import torch
@@ -20,7 +21,8 @@ import torch.nn as nn
 from . import ops
 from .Util import ANCHORS_PER_CELL, ANCHORS_PER_CELL_512, subsampling
 
-N_CLASSES = 21
+N_CLASSES = 21            # width of `conf` of the default model: 20 VOC classes + background (the last column)
+MAX_FOREGROUND = 255      # SSD_300(n_classes=...) range: 1 .. 255 foreground classes, conf rows of 2 .. 256 columns
 _VGG_CFG = (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M")
 
 
@@ -171,8 +173,9 @@ class _SinkDict(dict):
 class _Engine:
     """Runs the op list on the current HIP stream.  Holds only caches (re-laid-out weights)."""
 
-    def __init__(self, variant: int = 300):
+    def __init__(self, variant: int = 300, n_conf: int = N_CLASSES):
         ops_ = build_ops(variant)
+        self.n_conf = n_conf                      # width of the conf rows (foreground classes + background)
         self.names = param_names(ops_)            # parameter order of the autograd Function: the reference's forward order
         # Schedule: [backbone ... seq8] then [L2-norm, c_4, c_7: big MFMA-bound head convolutions] then [c_8, seq9 ... c_11: a dozen tiny
         # maps (10x10 ... 1x1) whose ~60 launches per direction are latency-bound].  The last group runs on a second HIP stream beside
@@ -413,7 +416,7 @@ class _Engine:
                         hw[op["y"]] = (g.Ho, g.Wo)
                         tensors, co_pad = (P[op["p"] + ".weight"],), op["co"]
                     else:
-                        co = op["a"] * (4 + N_CLASSES)
+                        co = op["a"] * (4 + self.n_conf)
                         g = ops.make_geom(bs, h, w_, op["ci"], co, 3, 1, 1, 1)
                         tensors, co_pad = (P[op["p"] + "_bb.weight"], P[op["p"] + "_cl.weight"]), ops.pad32(co)
                     t16 = self._t16(g, None) and (b16[op["x"]] or (kind == "head" and self._head16(op, g)))
@@ -502,7 +505,7 @@ class _Engine:
         heads.sort(key=lambda h: h[0]["scale"])                   # prior order: c_4, c_7, c_8, ... (Model.py:235)
         P_total = sum(g.Ho * g.Wo * op["a"] for op, _, g in heads)
         loc = torch.empty((bs, P_total, 4), device=x.device, dtype=torch.float32)
-        conf = torch.empty((bs, P_total, N_CLASSES), device=x.device, dtype=torch.float32)
+        conf = torch.empty((bs, P_total, self.n_conf), device=x.device, dtype=torch.float32)
         off = 0
         offs = {}
         for op, packed, g in heads:
@@ -636,7 +639,7 @@ class _Engine:
             elif kind == "head":
                 xin = T[op["x"]]
                 a = op["a"]
-                co = a * (4 + N_CLASSES)
+                co = a * (4 + self.n_conf)
                 g = ops.make_geom(bs, xin.shape[1], xin.shape[2], op["ci"], co, 3, 1, 1, 1)
                 pre = op["p"]
                 bias = _cat_flat(P[pre + "_bb.bias"].detach(), P[pre + "_cl.bias"].detach())
@@ -1063,12 +1066,24 @@ class _SSD300Function(torch.autograd.Function):
         return (None, None) + tuple(grads.get(n) if need[n] else None for n in eng.names)
 
 
+def _check_n_classes(n_classes) -> int:
+    if isinstance(n_classes, bool) or not isinstance(n_classes, numbers.Integral):
+        raise ValueError(f"n_classes must be an integer, got {n_classes!r}")
+    if not 1 <= int(n_classes) <= MAX_FOREGROUND:
+        raise ValueError(f"n_classes must be in 1..{MAX_FOREGROUND} (foreground classes; background is added), got {n_classes}")
+    return int(n_classes)
+
+
 class SSD_300(nn.Module):
-    """Drop-in for reference Model.py:128-235 (same no-argument constructor, same parameter names)."""
+    """Drop-in for reference Model.py:128-235 (same no-argument constructor, same parameter names).
+    `n_classes` (keyword only): the number of FOREGROUND classes, 1..255; `conf` has n_classes + 1 columns, background last.
+    The default 20 is the reference's VOC model; any other value changes only the output channels of the `c_*_cl` heads."""
     _VARIANT = 300
 
-    def __init__(self):
+    def __init__(self, *, n_classes: int = 20):
         super().__init__()
+        self.n_classes = _check_n_classes(n_classes)
+        n_conf = self.n_classes + 1
         self.model = _VGG16()                                              # Model.py:131 (no download here)
         self.rescaling_conv_4_3 = nn.Parameter(torch.full((1, 512, 1, 1), 20.))   # Model.py:132-133
         feats = self.model.features
@@ -1097,9 +1112,9 @@ class SSD_300(nn.Module):
         self._head_names = ("c_4", "c_7") + tuple(f"c_{8 + i}" for i in range(len(aux)))
         for name, cin, a in zip(self._head_names, (512, 1024, 512) + (256,) * (len(aux) - 1), anchors):
             setattr(self, name + "_bb", nn.Conv2d(cin, 4 * a, 3, padding=1))
-            setattr(self, name + "_cl", nn.Conv2d(cin, N_CLASSES * a, 3, padding=1))
+            setattr(self, name + "_cl", nn.Conv2d(cin, n_conf * a, 3, padding=1))
         self.initialization()
-        self._engine = _Engine(self._VARIANT)
+        self._engine = _Engine(self._VARIANT, n_conf)
 
     @property
     def conv_dtype(self) -> str:

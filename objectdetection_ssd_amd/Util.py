@@ -136,15 +136,19 @@ def create_ancs_xywh_zoom_ratio() -> torch.Tensor:
     return torch.tensor(np.asarray(rows, np.float64), dtype=torch.float32)
 
 
-def get_map(det_boxes, det_classes, det_scores, gt_boxes, gt_classes):
+def get_map(det_boxes, det_classes, det_scores, gt_boxes, gt_classes, n_classes=20):
     """Per-class 11-point interpolated AP (reference Util.py:783-885; same arguments: per-image lists of (n,4) boxes,
     (n,) classes, (n,) scores and the ground-truth boxes / classes).  Matching, the per-class sort and the
     precision/recall scan run on the GPU (csrc/map_eval.hip); returns {class: numpy.float64 AP} like the reference
-    (which also prints each value).  Score ties are ordered lower flat index first."""
+    (which also prints each value).  Score ties are ordered lower flat index first.  `n_classes`: the foreground classes
+    (1..256), the keys of the result are range(n_classes)."""
     import numpy as np
     from . import ops
     if not torch.cuda.is_available():
         raise RuntimeError("get_map() runs on the gfx950 HIP kernels only (no CPU fallback)")
+    import numbers
+    if isinstance(n_classes, bool) or not isinstance(n_classes, numbers.Integral) or not 1 <= n_classes <= 256:
+        raise ValueError(f"n_classes must be an integer in 1..256, got {n_classes!r}")
     n_img = len(det_boxes)
     if not (n_img == len(det_classes) == len(det_scores) == len(gt_boxes) == len(gt_classes)) or n_img == 0:
         raise ValueError("get_map expects five lists with one entry per image")
@@ -161,6 +165,6 @@ def get_map(det_boxes, det_classes, det_scores, gt_boxes, gt_classes):
     gb, g_start = flat(gt_boxes, torch.float32, 4)
     gc, _ = flat(gt_classes, torch.int32, 0)
     levels = torch.arange(0, 1.1, 0.1).double().numpy()                # Util.py:874, float32 levels compared in float64
-    table, _, _ = ops.map_eval(db, dc, ds, d_start, gb, gc, g_start, levels, 20)
+    table, _, _ = ops.map_eval(db, dc, ds, d_start, gb, gc, g_start, levels, int(n_classes))
     t = table.cpu().numpy()
-    return {cls: np.float64(np.mean(t[cls])) for cls in range(20)}
+    return {cls: np.float64(np.mean(t[cls])) for cls in range(int(n_classes))}

@@ -22,6 +22,17 @@
 // to rounding).
 // All sums are reduced in a fixed order (no float atomics): results are bitwise reproducible.
 //
+// Wide rows (64 < C <= 256: COCO's 81 classes, own label sets): L1 and L3 above stage whole rows of 64 / 256 priors in LDS, 64 x 256 and
+// 256 x 256 floats at C = 256 -- more than a CU holds.  Their wide forms stage nothing per class:
+//   L1w loss_prior_wide_kernel   the same matching; the cross entropy walks the wave's 64 rows one at a time with the lanes across the
+//                                classes (four per lane, every load a whole coalesced row), max and sum of exp by butterfly (fixed order)
+//   L3w finalize_wide_kernel     64 priors per block: (max, 1/sum exp, class) of the selected rows by a wave per row, then the block's
+//                                64 x C dconf floats leave as ONE flat coalesced stream (consecutive threads, consecutive floats)
+// L2 (one workgroup per image, radix select) does not depend on C and is shared.  C <= 64 keeps L1 / L3 as they are.
+//
+// Class labels index conf rows: every kernel reads them through class_index(), which keeps any value (negative, >= C - 1, NaN)
+// inside the row.  Labels outside 0 .. C-2 are the caller's error and give unspecified losses, but no access outside the tensors.
+//
 // The IoU arithmetic must equal the reference's f32 op sequence bit for bit
 // (sub, max, min, mul, add, sub, IEEE divide): this file is compiled with
 // -ffp-contract=off and the pragma below keeps a*b+c from being fused.
@@ -42,6 +53,9 @@ __device__ __forceinline__ float iou_xyxy(float ax1, float ay1, float ax2, float
     const float uni = (area_a + area_b) - inter;          // Util.py:299: a1 + a2 - inter, left to right
     return inter / uni;                                   // no epsilon (Util.py:301)
 }
+
+// ground-truth label -> conf column, clamped into 0 .. C-1 (NaN -> 0); the identity (int)v for the valid labels 0 .. C-2
+__device__ __forceinline__ int class_index(float v, int C) { return v >= 0.f ? (v < (float)(C - 1) ? (int)v : C - 1) : 0; }
 
 // torch.max(dim) update rule: take v when it is larger, or when it is NaN and best is not.
 __device__ __forceinline__ bool better(float v, float best) { return v > best || (v != v && best == best); }
@@ -128,7 +142,7 @@ __global__ __launch_bounds__(LB) void match_ce_kernel(const MatchArgs a) {
         for (int k = s; k < e; ++k)            // Losses.py:164-167: sequential writes, last GT wins
             if (a.best_prior[k] == p) { idx = k; best = 1.f; }
         const int bg = a.C - 1;
-        const int c = best < a.thr ? bg : (int)a.gt_cls[idx];
+        const int c = best < a.thr ? bg : class_index(a.gt_cls[idx], a.C);
         const bool pos = c != bg;
         const size_t ip = (size_t)i * a.P + p;
         a.obj[ip] = idx;
@@ -278,39 +292,15 @@ struct ImageArgs {
 
 constexpr int SG = 128;        // GT boxes of an image kept in LDS (more are read from memory: correct, slower)
 
-// L1: grid (ceil(P / 256), bs), 256 threads; a wave owns 64 consecutive priors of image blockIdx.y
-__global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float stage_all[];       // [4][64 * C] conf rows
-    __shared__ f32x4 sg_box[SG];
-    __shared__ float sg_area[SG];
-    __shared__ int sg_cls[SG];
-    const int i = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int s = a.img_start[i], e = a.img_start[i + 1];
-    const int P = a.P, C = a.C;
-    const int ns = e - s < SG ? e - s : SG;
-    for (int t = tid; t < ns; t += 256) {
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
-        sg_box[t] = g4;
-        sg_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
-        sg_cls[t] = (int)a.gt_cls[s + t];
-    }
-    const int pb = blockIdx.x * 256 + wave * 64;          // this wave's first prior
-    const int rows = P - pb < 64 ? P - pb : 64;           // (<= 0: a wave past the end; it still reports "nothing" for every box)
-    float* const st = stage_all + (size_t)wave * 64 * C;
-    if (rows > 0) {
-        const int nfl = rows * C;
-        const float* src = a.conf + ((size_t)i * P + pb) * C;
-        for (int t = lane; t < nfl; t += 64) st[t] = src[t];
-    }
-    __syncthreads();                                      // boxes staged (and this wave's rows written)
-    const int p = pb + lane;
-    const bool live = lane < rows;
+// L1 / L1w: IoU of prior p (lane of a wave owning 64 consecutive priors) against the image's boxes [s, e) -> the prior's best box
+// (first index on ties) in (best, idx); and, per box, the wave's best prior into partv / parti[k][slot]
+__device__ __forceinline__ void match_wave(const ImageArgs& a, const f32x4* sg_box, const float* sg_area, int s, int e, int p, bool live,
+                                           int lane, int slot, float& best, int& idx) {
     f32x4 b = {0.f, 0.f, 0.f, 0.f};
     if (live) b = *reinterpret_cast<const f32x4*>(a.pri_xyxy + (size_t)p * 4);
     const float area_b = (b[2] - b[0]) * (b[3] - b[1]);
-    float best = 0.f;
-    int idx = s;
-    const int slot = blockIdx.x * 4 + wave;
+    best = 0.f;
+    idx = s;
     for (int k = s; k < e; ++k) {
         float v;
         if (k - s < SG) {
@@ -335,17 +325,128 @@ __global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a) {
             a.parti[(size_t)k * a.NPW + slot] = wii;
         }
     }
+}
+
+// A conf row of C <= 256 floats across one wave: lane l holds columns l, l + 64, l + 128, l + 192 (-inf past the end).  Returns the
+// row's max and sum of exp(x - max) (butterflies: the same value in every lane, the same bits on every run).
+struct RowStats { float m, se; };
+__device__ __forceinline__ void load_row_wave(const float* __restrict__ x, int C, int lane, float v[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int q = lane + 64 * j;
+        v[j] = q < C ? x[q] : -INFINITY;
+    }
+}
+__device__ __forceinline__ RowStats row_stats_wave(const float v[4], int C, int lane) {
+    float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    float e4 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (lane + 64 * j < C) e4 += expf(v[j] - m);
+    return RowStats{m, wave_sum(e4)};
+}
+__device__ __forceinline__ float col_wave(const float v[4], int c) {         // column c (wave-uniform) of the row, in every lane
+    const int j = c >> 6;
+    const float vj = j == 0 ? v[0] : (j == 1 ? v[1] : (j == 2 ? v[2] : v[3]));
+    return __shfl(vj, c & 63, 64);
+}
+
+// L1: grid (ceil(P / 256), bs), 256 threads; a wave owns 64 consecutive priors of image blockIdx.y
+__global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float stage_all[];       // [4][64 * C] conf rows
+    __shared__ f32x4 sg_box[SG];
+    __shared__ float sg_area[SG];
+    __shared__ int sg_cls[SG];
+    const int i = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = a.img_start[i], e = a.img_start[i + 1];
+    const int P = a.P, C = a.C;
+    const int ns = e - s < SG ? e - s : SG;
+    for (int t = tid; t < ns; t += 256) {
+        const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
+        sg_box[t] = g4;
+        sg_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
+        sg_cls[t] = class_index(a.gt_cls[s + t], C);
+    }
+    const int pb = blockIdx.x * 256 + wave * 64;          // this wave's first prior
+    const int rows = P - pb < 64 ? P - pb : 64;           // (<= 0: a wave past the end; it still reports "nothing" for every box)
+    float* const st = stage_all + (size_t)wave * 64 * C;
+    if (rows > 0) {
+        const int nfl = rows * C;
+        const float* src = a.conf + ((size_t)i * P + pb) * C;
+        for (int t = lane; t < nfl; t += 64) st[t] = src[t];
+    }
+    __syncthreads();                                      // boxes staged (and this wave's rows written)
+    const int p = pb + lane;
+    const bool live = lane < rows;
+    float best;
+    int idx;
+    match_wave(a, sg_box, sg_area, s, e, p, live, lane, blockIdx.x * 4 + wave, best, idx);
     if (live) {
         const size_t ip = (size_t)i * P + p;
         // cross entropy against the class the prior has unless a box claims it in L2 (Losses.py:164-167: those few are redone there);
         // torch log_softmax order: (x - max) - log(sum exp(x - max))
-        const int c = best < a.thr ? C - 1 : (idx - s < SG ? sg_cls[idx - s] : (int)a.gt_cls[idx]);
+        const int c = best < a.thr ? C - 1 : (idx - s < SG ? sg_cls[idx - s] : class_index(a.gt_cls[idx], C));
         const float* x = st + lane * C;
         float m = x[0];
         for (int q = 1; q < C; ++q) m = fmaxf(m, x[q]);
         float se = 0.f;
         for (int q = 0; q < C; ++q) se += expf(x[q] - m);
         a.cebg[ip] = -((x[c] - m) - logf(se));
+        a.bestv[ip] = best;
+        a.obj[ip] = idx;
+    }
+}
+
+// L1w (64 < C <= 256): L1 without the row staging; grid (ceil(P / 256), bs), 256 threads, a wave per 64 consecutive priors
+__global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a) {
+    __shared__ f32x4 sg_box[SG];
+    __shared__ float sg_area[SG];
+    __shared__ int sg_cls[SG];
+    const int i = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = a.img_start[i], e = a.img_start[i + 1];
+    const int P = a.P, C = a.C;
+    const int ns = e - s < SG ? e - s : SG;
+    for (int t = tid; t < ns; t += 256) {
+        const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
+        sg_box[t] = g4;
+        sg_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
+        sg_cls[t] = class_index(a.gt_cls[s + t], C);
+    }
+    __syncthreads();
+    const int pb = blockIdx.x * 256 + wave * 64;
+    const int rows = P - pb < 64 ? P - pb : 64;
+    const int p = pb + lane;
+    const bool live = lane < rows;
+    float best;
+    int idx;
+    match_wave(a, sg_box, sg_area, s, e, p, live, lane, blockIdx.x * 4 + wave, best, idx);
+    const int c = !live || best < a.thr ? C - 1 : (idx - s < SG ? sg_cls[idx - s] : class_index(a.gt_cls[idx], C));
+    // cross entropy (torch log_softmax order: (x - max) - log(sum exp(x - max))), a row at a time, two rows' loads in flight
+    float ce = 0.f;
+    const float* src = a.conf + ((size_t)i * P + pb) * C;
+    for (int r = 0; r < rows; r += 2) {                   // (rows <= 0: a wave past the end does nothing here)
+        float v0[4], v1[4];
+        load_row_wave(src + (size_t)r * C, C, lane, v0);
+        const bool two = r + 1 < rows;
+        if (two) load_row_wave(src + (size_t)(r + 1) * C, C, lane, v1);
+        {
+            const RowStats st = row_stats_wave(v0, C, lane);
+            const float xc = col_wave(v0, __shfl(c, r, 64));
+            const float cr = -((xc - st.m) - logf(st.se));
+            if (lane == r) ce = cr;
+        }
+        if (two) {
+            const RowStats st = row_stats_wave(v1, C, lane);
+            const float xc = col_wave(v1, __shfl(c, r + 1, 64));
+            const float cr = -((xc - st.m) - logf(st.se));
+            if (lane == r + 1) ce = cr;
+        }
+    }
+    if (live) {
+        const size_t ip = (size_t)i * P + p;
+        a.cebg[ip] = ce;
         a.bestv[ip] = best;
         a.obj[ip] = idx;
     }
@@ -366,7 +467,7 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a) {
     const int P = a.P, C = a.C;
     const int ns = e - s < SG ? e - s : SG;
     for (int t = tid; t < ns; t += NT) {
-        sg_cls[t] = (int)a.gt_cls[s + t];
+        sg_cls[t] = class_index(a.gt_cls[s + t], C);
         sg_box[t] = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
     }
     // ---- best prior of each box: a wave per box over the NPW per-wave results of L1 ----
@@ -422,7 +523,7 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a) {
                     if (sg_bp[k] == p) { idx = s + k; best = 1.f; forced = true; }
                 for (int k = s + ns; k < e; ++k)
                     if (a.best_prior[k] == p) { idx = k; best = 1.f; forced = true; }
-                const int c = best < a.thr ? bg : (idx - s < SG ? sg_cls[idx - s] : (int)a.gt_cls[idx]);
+                const int c = best < a.thr ? bg : (idx - s < SG ? sg_cls[idx - s] : class_index(a.gt_cls[idx], C));
                 const bool pos = c != bg;
                 a.obj[ip] = idx;
                 a.cls[ip] = c;
@@ -638,6 +739,78 @@ __global__ __launch_bounds__(LB) void finalize_kernel(const FinalArgs a) {
     for (int t = threadIdx.x; t < nfl; t += LB) dst[t] = fstage[t];
 }
 
+// L3w (64 < C <= 256): grid (ceil(P / 64), bs), 256 threads; block = 64 consecutive priors of image blockIdx.y
+constexpr int RW = 64;
+__global__ __launch_bounds__(LB) void finalize_wide_kernel(const FinalArgs a) {
+    __shared__ float tot[4];
+    __shared__ float s_m[RW], s_r[RW];
+    __shared__ int s_c[RW];                         // class of the row, -1 = row not selected (all-zero gradient)
+    if (threadIdx.x == 0) {
+        float npos = 0.f, ce = 0.f, l1 = 0.f, hn = 0.f;
+        for (int i = 0; i < a.bs; ++i) {
+            npos += a.stats[i * 4 + 0]; ce += a.stats[i * 4 + 1]; l1 += a.stats[i * 4 + 2]; hn += a.stats[i * 4 + 3];
+        }
+        tot[0] = npos; tot[1] = ce; tot[2] = l1; tot[3] = hn;
+    }
+    __syncthreads();
+    const float npos = tot[0];
+    const float inv = a.norm_mode == 0 ? 1.f / npos : 1.f;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        a.losses[0] = a.norm_mode == 0 ? tot[2] / (npos * 4.f) : tot[2] / 4.f;
+        a.losses[1] = a.norm_mode == 0 ? (tot[3] + tot[1]) / npos : (tot[3] + tot[1]);
+        a.losses[2] = npos;
+    }
+    if (a.dloc == nullptr || a.dconf == nullptr) return;
+    const int i = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pb = blockIdx.x * RW;
+    const int rows = a.P - pb < RW ? a.P - pb : RW;
+    const int C = a.C;
+    const float* const src = a.conf + ((size_t)i * a.P + pb) * C;
+    // (max, 1 / sum exp, class) of the selected rows: a wave per row (row index wave-uniform)
+    for (int r = wave; r < rows; r += LB / 64) {
+        const size_t ip = (size_t)i * a.P + pb + r;
+        const int c = a.cls[ip];
+        const bool on = c != C - 1 || a.sel[ip] != 0;
+        if (on) {
+            float v[4];
+            load_row_wave(src + (size_t)r * C, C, lane, v);
+            const RowStats st = row_stats_wave(v, C, lane);
+            if (lane == 0) { s_m[r] = st.m; s_r[r] = 1.f / st.se; s_c[r] = c; }
+        } else if (lane == 0) {
+            s_c[r] = -1;
+        }
+    }
+    if (tid < rows) {
+        const int p = pb + tid;
+        const size_t ip = (size_t)i * a.P + p;
+        f32x4 dl = {0.f, 0.f, 0.f, 0.f};
+        if (a.cls[ip] != C - 1) {
+            const f32x4 pr = *reinterpret_cast<const f32x4*>(a.pri + (size_t)p * 4);
+            float g[4];
+            encode_gt(a.gt, a.obj[ip], pr, g);
+            const f32x4 l = *reinterpret_cast<const f32x4*>(a.loc + ip * 4);
+            const float sc = inv * 0.25f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float d = l[q] - g[q];
+                dl[q] = d > 0.f ? sc : (d < 0.f ? -sc : 0.f);
+            }
+        }
+        *reinterpret_cast<f32x4*>(a.dloc + ip * 4) = dl;
+    }
+    __syncthreads();
+    // the block's rows x C floats of dconf as one contiguous stream; conf is read only where the row is selected
+    float* const dst = a.dconf + ((size_t)i * a.P + pb) * C;
+    const int nfl = rows * C;
+    for (int t = tid; t < nfl; t += LB) {
+        const int r = t / C, q = t - r * C;
+        const int c = s_c[r];
+        float d = 0.f;
+        if (c >= 0) d = (expf(src[t] - s_m[r]) * s_r[r] - (q == c ? 1.f : 0.f)) * inv;
+        dst[t] = d;
+    }
+}
+
 int g_loss_form = 1;      // 1 = three launches (L1 wide, L2 per image, L3), 0 = the four-launch form (ssd_tune_set_loss_form)
 
 struct LossWs {
@@ -683,7 +856,7 @@ extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const floa
         !cls || !workspace)
         return SSD_ERR_NULL;
     if ((dloc == nullptr) != (dconf == nullptr)) return SSD_ERR_NULL;
-    if (bs <= 0 || n_gt < bs || P <= 0 || P > 36000 || n_classes < 2 || n_classes > 64 || neg_pos_ratio < 0 ||
+    if (bs <= 0 || n_gt < bs || P <= 0 || P > 36000 || n_classes < 2 || n_classes > 256 || neg_pos_ratio < 0 ||
         (norm_mode != 0 && norm_mode != 1))
         return SSD_ERR_BAD_SHAPE;
     if (!ssd_aligned16(loc) || !ssd_aligned16(priors_cxcywh) || !ssd_aligned16(priors_xyxy) || (dloc && !ssd_aligned16(dloc)) ||
@@ -693,9 +866,10 @@ extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const floa
     hipStream_t st = (hipStream_t)stream;
     const LossWs w = carve(workspace, bs, P, n_gt);
     const int NB = ssd_cdiv(P, LB);
+    const bool wide_rows = n_classes > 64;          // L1w / L3w: nothing staged per class
     if (g_loss_form != 0) {
         // L1 wide (a wave per 64 priors), L2 one workgroup per image
-        const size_t l1_lds = (size_t)4 * 64 * n_classes * 4, l2_lds = (size_t)P * 4;
+        const size_t l1_lds = wide_rows ? 0 : (size_t)4 * 64 * n_classes * 4, l2_lds = (size_t)P * 4;
         static std::atomic<unsigned long long> raised_l12{0};     // one bit per device (common.h)
         int dev;
         if ((l1_lds > 48 * 1024 || l2_lds > 48 * 1024) && ssd_attr_needed(raised_l12, dev)) {
@@ -708,7 +882,10 @@ extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const floa
         }
         ImageArgs ia{loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, w.partv, w.parti, w.bestv, w.neg,
                      w.best_prior, obj, cls, w.sel, w.stats, P, n_classes, neg_pos_ratio, NB * 4, iou_threshold};
-        hipLaunchKernelGGL(loss_prior_kernel, dim3(NB, bs), dim3(256), l1_lds, st, ia);
+        if (wide_rows)
+            hipLaunchKernelGGL(loss_prior_wide_kernel, dim3(NB, bs), dim3(256), 0, st, ia);
+        else
+            hipLaunchKernelGGL(loss_prior_kernel, dim3(NB, bs), dim3(256), l1_lds, st, ia);
         SSD_CHECK_LAUNCH();
         hipLaunchKernelGGL(loss_image_kernel, dim3(bs), dim3(1024), l2_lds, st, ia);
         SSD_CHECK_LAUNCH();
@@ -735,6 +912,11 @@ extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const floa
     }
     FinalArgs fa{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode};
     const bool grads = dloc != nullptr;
+    if (wide_rows) {
+        hipLaunchKernelGGL(finalize_wide_kernel, grads ? dim3(ssd_cdiv(P, RW), bs) : dim3(1, 1), dim3(LB), 0, st, fa);
+        SSD_CHECK_LAUNCH();
+        return SSD_OK;
+    }
     const size_t fin_lds = grads ? (size_t)LB * n_classes * 4 : 0;
     if (fin_lds > 48 * 1024) {
         static std::atomic<unsigned long long> raised_fin{0};

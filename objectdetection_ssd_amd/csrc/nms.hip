@@ -1,8 +1,9 @@
 // Decode + softmax + per-class NMS + cross-class top-k for one image
 // (Losses.py:11-98 inference; Util.py:86-96 gcxgcy_to_cxcy, xywh_to_xyxy; Util.py:252-301 IoU).
 //
-//   D1 decode_compact  thread per prior: box (cxcywh -> xyxy), class probabilities (the 21 scores of 256 priors staged through LDS:
-//                      coalesced reads), and straight away the candidates prob >= min_score of every class as 64-bit keys
+//   D1 decode_compact  thread per prior: box (cxcywh -> xyxy), class probabilities (the C scores of NT priors staged through LDS:
+//                      coalesced reads; NT = 256 up to C = 47, fewer priors per block for wider rows so that NT rows stay in LDS --
+//                      C = 256: 64 rows of 257 floats, 66 KB -- and an odd row stride, C | 1, so that the lanes' rows hit distinct banks), and straight away the candidates prob >= min_score of every class as 64-bit keys
 //                      (prob bits << 32 | ~prior index): descending key order = descending prob, lower prior index first on ties
 //                      (the CPU sort order).  Slots come from one atomic per (wave, class) -- ballot + prefix --
 //                      so the order inside keys[] varies from run to run; the ranks D3 computes from the unique keys do not.
@@ -71,18 +72,27 @@ NmsWs carve(void* ws, int P, int C, int B) {
     return w;
 }
 
-// grid = (ceil(P/256), 1, B).  cand_cnt[(C-1)+1 per image] must be zero on entry (hipMemsetAsync in front of the launch).
-__global__ __launch_bounds__(256) void decode_compact_kernel(const float* __restrict__ l_, const float* __restrict__ c_, const float* __restrict__ pri,
-                                                             int P, int C, float min_score, float* __restrict__ boxes, uint64_t* __restrict__ keys,
-                                                             int32_t* __restrict__ cand_cnt) {
-    extern __shared__ float sc[];                                   // [256][C] class scores of this block's priors
-    const int p0 = blockIdx.x * 256, tid = threadIdx.x, lane = tid & 63;
+// grid = (ceil(P/NT), 1, B).  cand_cnt[(C-1)+1 per image] must be zero on entry (hipMemsetAsync in front of the launch).
+constexpr int decode_stride(int C) { return C | 1; }                 // odd row stride in LDS: 21 -> 21, 81 -> 81, 256 -> 257
+template <int NT>
+__global__ __launch_bounds__(NT) void decode_compact_kernel(const float* __restrict__ l_, const float* __restrict__ c_, const float* __restrict__ pri,
+                                                            int P, int C, float min_score, float* __restrict__ boxes, uint64_t* __restrict__ keys,
+                                                            int32_t* __restrict__ cand_cnt) {
+    extern __shared__ float sc[];                                   // [NT][S] class scores of this block's priors
+    const int p0 = blockIdx.x * NT, tid = threadIdx.x, lane = tid & 63;
     const int p = p0 + tid;
     const size_t img = blockIdx.z;
-    const int C1 = C - 1;
+    const int C1 = C - 1, S = decode_stride(C);
     l_ += img * P * 4; c_ += img * P * C; boxes += img * P * 4; keys += img * (size_t)C1 * P; cand_cnt += img * (C1 + 1);
-    const int rows = min(256, P - p0);
-    for (int e = tid; e < rows * C; e += 256) sc[e] = c_[(size_t)p0 * C + e];      // consecutive threads, consecutive floats
+    const int rows = min(NT, P - p0);
+    if (S == C) {
+        for (int e = tid; e < rows * C; e += NT) sc[e] = c_[(size_t)p0 * C + e];      // consecutive threads, consecutive floats
+    } else {
+        for (int e = tid; e < rows * C; e += NT) {
+            const int r = e / C;
+            sc[r * S + (e - r * C)] = c_[(size_t)p0 * C + e];
+        }
+    }
     __syncthreads();
     const bool live = p < P;
     float m = 0.f, se = 1.f;
@@ -96,8 +106,8 @@ __global__ __launch_bounds__(256) void decode_compact_kernel(const float* __rest
         f32x4 b;
         b[0] = cx - w / 2.f; b[1] = cy - h / 2.f; b[2] = cx + w / 2.f; b[3] = cy + h / 2.f;
         *reinterpret_cast<f32x4*>(boxes + (size_t)p * 4) = b;
-        const float* x = sc + tid * C;                              // row stride C = 21 floats: odd, conflict-free
-        float* xw = sc + tid * C;
+        const float* x = sc + tid * S;                              // odd row stride: conflict-free
+        float* xw = sc + tid * S;
         m = x[0];
         for (int q = 1; q < C; ++q) m = fmaxf(m, x[q]);
         se = 0.f;
@@ -114,8 +124,8 @@ __global__ __launch_bounds__(256) void decode_compact_kernel(const float* __rest
         const int nq = min(32, C1 - q0);
         unsigned hits = 0;
         for (int k = 0; k < nq; ++k) {
-            const float v = live ? sc[tid * C + q0 + k] / se : 0.f;
-            if (live) sc[tid * C + q0 + k] = v;
+            const float v = live ? sc[tid * S + q0 + k] / se : 0.f;
+            if (live) sc[tid * S + q0 + k] = v;
             hits |= (live && v >= min_score ? 1u : 0u) << k;        // Losses.py:32 (NaN fails, as in torch)
         }
         int cnt = 0;
@@ -131,7 +141,7 @@ __global__ __launch_bounds__(256) void decode_compact_kernel(const float* __rest
             const int b0 = __shfl(base, k, 64);
             if ((hits >> k) & 1u) {
                 const int pos = b0 + __popcll(mask & ((1ull << lane) - 1ull));
-                const float v = sc[tid * C + q0 + k];
+                const float v = sc[tid * S + q0 + k];
                 keys[(size_t)(q0 + k) * P + pos] = ((uint64_t)__float_as_uint(v) << 32) | (uint64_t)(0xffffffffu - (uint32_t)p);
             }
         }
@@ -546,9 +556,32 @@ extern "C" int ssd_decode_nms_batch(const float* l_, const float* c_, const floa
     const NmsWs w = carve(workspace, P, n_classes, B);
     const int C1 = n_classes - 1;
     if (hipMemsetAsync(w.cand_cnt, 0, (size_t)n_classes * 4 * B, st) != hipSuccess) return SSD_ERR_LAUNCH;     // the candidate counters of decode_compact
-    hipLaunchKernelGGL(decode_compact_kernel, dim3(ssd_cdiv(P, 256), 1, B), dim3(256), (size_t)256 * n_classes * 4, st, l_, c_, priors_cxcywh, P,
-                       n_classes, min_score, w.boxes, w.keys, w.cand_cnt);
-    SSD_CHECK_LAUNCH();
+    {
+        // priors per block: as many as keep the staged rows within 48 KB (256 up to C = 47, C = 21 as always), 64 beyond C = 95
+        const int S = decode_stride(n_classes);
+        const int nt = 256 * S * 4 <= 48 * 1024 ? 256 : (128 * S * 4 <= 48 * 1024 ? 128 : 64);
+        const size_t dlds = (size_t)nt * S * 4;                    // <= 64 x 257 x 4 = 66 KB
+        if (dlds > 48 * 1024) {
+            static std::atomic<unsigned long long> raised{0};
+            int dev;
+            if (ssd_attr_needed(raised, dev)) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(decode_compact_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)((size_t)64 * decode_stride(256) * 4)) != hipSuccess)
+                    return SSD_ERR_LAUNCH;
+                ssd_attr_done(raised, dev);
+            }
+        }
+        if (nt == 256)
+            hipLaunchKernelGGL(decode_compact_kernel<256>, dim3(ssd_cdiv(P, 256), 1, B), dim3(256), dlds, st, l_, c_, priors_cxcywh, P,
+                               n_classes, min_score, w.boxes, w.keys, w.cand_cnt);
+        else if (nt == 128)
+            hipLaunchKernelGGL(decode_compact_kernel<128>, dim3(ssd_cdiv(P, 128), 1, B), dim3(128), dlds, st, l_, c_, priors_cxcywh, P,
+                               n_classes, min_score, w.boxes, w.keys, w.cand_cnt);
+        else
+            hipLaunchKernelGGL(decode_compact_kernel<64>, dim3(ssd_cdiv(P, 64), 1, B), dim3(64), dlds, st, l_, c_, priors_cxcywh, P,
+                               n_classes, min_score, w.boxes, w.keys, w.cand_cnt);
+        SSD_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(rank_scatter_kernel, dim3(ssd_cdiv(P, 256), C1, B), dim3(256), 0, st, w.keys, w.cand_cnt, w.boxes, P, w.s_boxes, w.s_prob, w.s_idx);
     SSD_CHECK_LAUNCH();
     // Block size and LDS by batch: a single image is a latency problem (20 workgroups on 256 CUs: 16 waves each, 64-row chunks whatever
