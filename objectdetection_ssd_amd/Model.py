@@ -259,6 +259,20 @@ class _Engine:
         self.prof.append((label, tag, flops, e0, e1, executed))
         return out
 
+    def schedule_key(self) -> tuple:
+        """Every setting that decides which kernels a step runs, or in what form (dtype mode, Winograd and its thresholds, the fused
+        and adjoint forms, the library's limb-GEMM switch).  The training weight table is keyed by it, and so is a captured train
+        step (ddp.GraphedTrainStep): a flag flipped between two steps rebuilds the one and re-captures the other.  Stream placement
+        (`overlap_tail`, `defer_tail_wgrad`) is not in it: it changes where the kernels run, not which."""
+        return (self.bf16, self.bf16_tensors, self.x3, self.wino, self.WINO_TILE, self.WINO_MIN_CI, self.WINO_MIN_HW,
+                self.WINO_WGRAD_MAX_HW, self.WINO_WGRAD_MIN_CI, self.X31_MIN_PIXELS, ops.wino_x3(4, 256), self.adjoint_dgrad,
+                self.adjoint_chain, self.keep_planes, self.dual_dy, self.fuse_pool, self.lazy_pool_grad, self.relu_bits, self.wino_dilated,
+                self.first_fused, self.first_wino, self.overlap_wgrad, self.batch_weights)
+
+    def uses_weight_table(self) -> bool:
+        """A training forward lays out all its filters through the batched weight table (`_prepare_weights_batched`)."""
+        return self.batch_weights and not self.x3 and (not self.bf16 or self.bf16_tensors)
+
     # -- weights ----------------------------------------------------------------------------
     def _layouts(self, key: str, tensors, co_pad: int, need_bwd: bool):
         """Cached [Co_pad][T][Ci] / [Ci][T][Co_pad] copies, refreshed when a parameter changes."""
@@ -387,8 +401,7 @@ class _Engine:
         """Fill the weight cache for a training step with one launch.  The output buffers persist across steps (rewritten in place, on the
         caller's stream, after the previous step's last use); the job table is rebuilt only when a parameter's storage or the input
         size changes."""
-        sig = (x.shape[2], x.shape[3], self.wino, self.WINO_TILE, self.WINO_MIN_CI, self.WINO_MIN_HW, self.bf16, self.bf16_tensors,
-               ops.wino_x3(4, 256), self.adjoint_dgrad, self.keep_planes, self.dual_dy, self.overlap_wgrad) + tuple(P[n].data_ptr() for n in self.names)
+        sig = (x.shape[2], x.shape[3]) + self.schedule_key() + tuple(P[n].data_ptr() for n in self.names)
         if self._wtable is None or self._wtable[0] != sig:
             jobs, entries = [], []
             bs, hw, dev = x.shape[0], {"x": (x.shape[2], x.shape[3])}, x.device
@@ -481,7 +494,7 @@ class _Engine:
             # (data_ptr, _version) cannot see writes through `.data` (p.data.mul_(), dist.broadcast(p.data), EMA swaps).
             # The backward of this step reads what this forward stored.
             self._wcache.clear()
-            if self.batch_weights and not self.x3 and (not self.bf16 or self.bf16_tensors):
+            if self.uses_weight_table():
                 self._prepare_weights_batched(x, P)
         T = {"x": x}
         aux = {}
@@ -1201,24 +1214,41 @@ class GraphedForward:
     """Inference forward of a fixed input shape captured once into a HIP graph and replayed: at small batches the
     ~80 kernel launches of a forward cost more host time than GPU time, the replay is one launch.  Every kernel of the
     path only enqueues on the stream it is given (no allocation, no synchronisation inside the library), so the capture
-    needs nothing special.  The graph bakes in the weight layouts of the moment of capture: capture again after the
-    parameters change.  `__call__(x)` copies x into the static input and returns the static (loc, conf) tensors, which
-    the next call overwrites."""
+    needs nothing special.  `__call__(x)` copies x into the static input and returns the static (loc, conf) tensors, which
+    the next call overwrites.
+
+    What a replay holds: the graph runs on a copy of the parameters taken at capture (biases and the L2-norm scale are read
+    from it directly, the filters through layouts made from it and kept out of the engine's weight cache), on those layouts,
+    and on the workspaces the capture used (`ops.capture_workspaces`; the capture runs on a stream of its own).  This object keeps all of them alive for its own
+    lifetime -- one more copy of the parameters, of their layouts and of the scratch buffers than the eager path holds -- so
+    eager calls on the same net (other batch sizes, training steps, `invalidate_weight_cache()`, `load_state_dict`) may
+    replace the engine's caches without freeing memory the replay reads.  What it does not notice: ANY change of the
+    parameters after the capture (optimizer steps, writes through `.data`, `load_state_dict`) -- a replay returns the outputs
+    of the weights at capture.  Capture again (`net.graphed_forward(x)`) after the parameters change."""
 
     def __init__(self, net: "SSD_300", example: torch.Tensor):
-        if net.training and any(p.requires_grad for p in net.parameters()) and torch.is_grad_enabled():
-            pass                                               # captured under no_grad below either way
         self.net = net
         self.x = example.detach().clone().contiguous()
-        side = torch.cuda.Stream(device=self.x.device)
-        side.wait_stream(torch.cuda.current_stream(self.x.device))
-        with torch.no_grad(), torch.cuda.stream(side):        # warm-up: weight layouts, workspaces, allocator pools
-            for _ in range(2):
-                net(self.x)
-        torch.cuda.current_stream(self.x.device).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.loc, self.conf = net(self.x)
+        eng = net._engine
+        P = {n: p.detach().clone() for n, p in net._forward_params().items()}
+        self._stream = torch.cuda.Stream(device=self.x.device)
+        s = self._stream
+        # The copy's layouts go into a cache of their own, never into the engine's: entries keyed on (data_ptr, _version) of the
+        # copy would outlive it there, and a later copy allocated at the same addresses (version 0 again) would hit them.
+        shared, eng._wcache = eng._wcache, {}
+        try:
+            s.wait_stream(torch.cuda.current_stream(self.x.device))
+            with torch.no_grad(), torch.cuda.stream(s):       # warm-up: weight layouts, workspaces, allocator pools
+                for _ in range(2):
+                    eng.forward(self.x, P, save=False)
+            torch.cuda.current_stream(self.x.device).wait_stream(s)
+            self.graph = torch.cuda.CUDAGraph()
+            with ops.capture_workspaces() as ws, torch.no_grad(), torch.cuda.graph(self.graph, stream=s):
+                self.loc, self.conf, _ = eng.forward(self.x, P, save=False)
+            layouts = [t for ent in eng._wcache.values() for t in ent if torch.is_tensor(t)]
+        finally:
+            eng._wcache = shared
+        self._held = (P, ws, layouts)          # what the replay reads besides its own pool: the parameter copy, its layouts, the workspaces
 
     def __call__(self, x: torch.Tensor):
         if tuple(x.shape) != tuple(self.x.shape) or x.dtype != self.x.dtype:

@@ -422,10 +422,22 @@ class GraphedTrainStep:
       * the number of positive priors stays on the device (it is written into the flat gradient buffer's count slot inside the graph).
 
     The first `warmup` calls run the step eagerly (they are ordinary training steps: allocator pools, workspaces, weight tables and the
-    momentum buffers come into being), the next call captures and replays.  The graph bakes in lr / momentum / weight decay: it is
-    captured again when the optimizer's groups change (StepLR).  With more than one rank the gradient exchange is ONE all-reduce
-    issued after the graph (a collective started from inside the backward cannot be part of a replay), followed by the two SGD
-    launches; `FlatSGDDataParallel(overlap=...)` is switched off for the life of this object.
+    momentum buffers come into being), the next call captures and replays; while a group has a nonzero momentum whose buffer does not
+    exist yet the step stays eager (the first SGD step starts the buffer from the gradient, a different launch), with momentum 0 the
+    capture follows the warm-up.  With more than one rank the gradient exchange is ONE f32 all-reduce issued after the graph (a
+    collective started from inside the backward cannot be part of a replay), followed by the two SGD launches;
+    `FlatSGDDataParallel(overlap=...)` is switched off for the life of this object, and a trainer built with `grad_dtype=torch.bfloat16`
+    is refused at more than one rank (`ValueError`) rather than sending f32.
+
+    What forces a re-capture: a change of lr / momentum / weight decay of either group (StepLR), of the world size, of the engine's
+    stream placement (`overlap_tail`, `defer_tail_wgrad`), or of any engine setting in `_Engine.schedule_key()` (dtype mode, Winograd
+    and its thresholds, the fused and adjoint forms).  What a replay holds: the graph has baked in raw device pointers, so this object keeps,
+    for as long as the graph lives, every workspace the capture was handed (`ops.capture_workspaces`) and, where the step lays out its
+    filters through the batched weight table (`_Engine.uses_weight_table()`: the default), that table -- one more weight table and
+    set of scratch buffers than the eager step holds.  Eager calls on the
+    same net in between (an eval forward at another batch, a training step at another size, a flag flipped and back) may then
+    replace the engine's caches freely.  What it does not notice: a parameter moved to new storage (the flat buffer is the
+    parameters' storage; replacing `p.data` detaches it from the graph) and changed shapes (refused, `ValueError`).
 
     two_streams (default): the tiny-map group (c_8, seq9 ... c_11) is captured on the engine's second stream, as the eager step runs it
     -- the graph then has two parallel branches (fork / join by events inside the capture); False puts every node on one chain.
@@ -436,6 +448,9 @@ class GraphedTrainStep:
     un-normalised loss sums and positive count (`Losses.ssd(..., norm_mode=1, with_n_pos=True)`), overwritten by the next call."""
 
     def __init__(self, net, trainer: FlatSGDDataParallel, max_boxes_per_image: int = 8, warmup: int = 2, two_streams: bool = True):
+        if trainer.grad_dtype == torch.bfloat16 and trainer.world > 1:       # (before anything below touches the trainer or the net)
+            raise ValueError("GraphedTrainStep exchanges the f32 gradient buffer in one all-reduce behind the replay: a trainer built with "
+                             "grad_dtype=torch.bfloat16 would silently send f32 -- build it with the f32 default, or step it eagerly")
         self.net, self.trainer = net, trainer
         self.max_per_image, self.warmup = int(max_boxes_per_image), int(warmup)
         self.two_streams = bool(two_streams)
@@ -448,6 +463,7 @@ class GraphedTrainStep:
         net._engine.sink_early = False
         self._stream = None
         self._ring, self._ring_pos = [], 0
+        self._held = None                 # what the graph reads besides its own pool (workspaces, weight table): kept while it lives
 
     # -- static buffers ------------------------------------------------------------------------------------------------------------
     def _make_static(self, x: torch.Tensor):
@@ -513,7 +529,7 @@ class GraphedTrainStep:
         tr = self.trainer
         eng = self.net._engine
         return tuple((g["lr"], g["momentum"], g["weight_decay"]) for g in tr.param_groups) + (
-            tr.world, eng.bf16, eng.bf16_tensors, eng.x3, eng.wino, eng.WINO_TILE, ops.wino_x3(4, 256))
+            tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + eng.schedule_key()
 
     def _eager(self, x, classes, boxes):
         from . import Losses
@@ -546,9 +562,11 @@ class GraphedTrainStep:
                 g = torch.cuda.CUDAGraph(keep_graph=True)
             except TypeError:
                 g = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(g, stream=s):
+            with ops.capture_workspaces() as ws, torch.no_grad(), torch.cuda.graph(g, stream=s):
                 self.losses, self.obj, self.cls = self._body(with_sgd=single)
             self.graph = g
+            table = eng._wtable if eng.uses_weight_table() else None          # (otherwise a table of an earlier setting, not read)
+            self._held = (ws, table, [t for ent in eng._wcache.values() for t in ent if torch.is_tensor(t)])
             self.kernel_nodes = _graph_kernel_nodes(g)
             if single:
                 tr.steps -= 1                                 # apply_sgd's bookkeeping ran once during capture without a step being executed
@@ -559,7 +577,7 @@ class GraphedTrainStep:
     def __call__(self, x, classes, boxes):
         tr = self.trainer
         self._calls += 1
-        if self._calls <= self.warmup or not tr._has_momentum:
+        if self._calls <= self.warmup or not (tr._has_momentum or all(g["momentum"] == 0 for g in tr.param_groups)):
             return self._eager(x, classes, boxes)
         if self._static is None:
             self._make_static(x)

@@ -5,8 +5,9 @@ must never reach a hand-written kernel.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -381,16 +382,37 @@ def heads_gather_bf16(dloc: torch.Tensor, dconf: torch.Tensor, ld: int, n: int, 
 
 
 _ws_cache = {}
+_ws_capture: Optional[dict] = None      # set by `capture_workspaces`: id -> every workspace handed out meanwhile
 
 
 def workspace(nbytes: int, device, tag: str = "ws") -> torch.Tensor:
-    """Grow-only scratch buffer per (device, stream, tag); contents are dead between calls."""
+    """Grow-only scratch buffer per (device, stream, tag); contents are dead between calls.  A larger request replaces (and frees) the
+    buffer of its key: a captured graph that baked in the old one must hold it itself (`capture_workspaces`)."""
     key = (str(device), _stream(), tag)
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(nbytes, 1 << 20), device=device, dtype=torch.uint8)
         _ws_cache[key] = buf
+    if _ws_capture is not None:
+        _ws_capture[id(buf)] = buf
     return buf
+
+
+@contextlib.contextmanager
+def capture_workspaces():
+    """Yields a list that, when the block ends, holds every workspace `workspace()` handed out inside it (on any stream): the buffers
+    a graph captured in the block has baked in.  The graph's owner keeps the list for the graph's lifetime, so that a later, larger
+    eager call that regrows a workspace does not free memory a replay still reads and writes."""
+    global _ws_capture
+    prev, _ws_capture = _ws_capture, {}
+    held: List[torch.Tensor] = []
+    try:
+        yield held
+    finally:
+        mine, _ws_capture = _ws_capture, prev
+        held.extend(mine.values())
+        if prev is not None:
+            prev.update(mine)
 
 
 def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, g: ConvGeom, ldy: int, want_bias: bool = True, bf16: bool = False,

@@ -446,3 +446,46 @@ def test_data_parallel_optimizer_loads_a_single_gpu_checkpoint():
     dp2 = FlatSGDDataParallel(Model.SSD_300(), lr=1.0)
     dp2.load_state_dict(dp.state_dict())
     assert torch.equal(dp2.flat_mom, dp.flat_mom)
+
+
+def _graph_bf16_worker(rank, world, port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from objectdetection_ssd_amd.ddp import FlatSGDDataParallel, GraphedTrainStep
+        tr16 = FlatSGDDataParallel(_Tiny(), lr=0.1, grad_dtype=torch.bfloat16)
+        try:
+            GraphedTrainStep(tr16.model, tr16)
+            refused = None
+        except ValueError as e:
+            refused = str(e)
+        tr32 = FlatSGDDataParallel(_Tiny(), lr=0.1)
+        g32 = GraphedTrainStep(tr32.model, tr32)
+        untouched = tr16.overlap and tr16.model._engine.sink_early           # a refused construction leaves the trainer as it was
+        q.put((rank, refused, g32.graph is None and not tr32.overlap, untouched))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_graphed_step_refuses_a_bf16_exchange_it_would_send_as_f32_world2():
+    """ddp.GraphedTrainStep exchanges the f32 flat gradient buffer in one all-reduce behind the replay.  A trainer built to send bf16
+    gradients must therefore be refused at world 2 (ValueError at construction, the trainer left as it was), not run with an f32
+    payload nobody asked for; an f32 trainer at world 2 and a bf16 trainer at world 1 (no exchange at all) are accepted."""
+    from objectdetection_ssd_amd.ddp import FlatSGDDataParallel, GraphedTrainStep
+    world, port = 2, _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_graph_bf16_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    out = sorted([q.get(timeout=240) for _ in range(world)], key=lambda t: t[0])
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    for rank, refused, f32_ok, untouched in out:
+        assert refused is not None and "bfloat16" in refused, (rank, refused)
+        assert f32_ok and untouched, rank
+    tr = FlatSGDDataParallel(_Tiny(), lr=0.1, grad_dtype=torch.bfloat16)
+    assert tr.world == 1
+    g = GraphedTrainStep(tr.model, tr)
+    assert g.graph is None and g.trainer is tr
