@@ -1,6 +1,6 @@
 """bench.py -- SSD300-VGG16 train step throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = Model.SSD_300 forward + Losses.ssd (match, loss) + backward through every
@@ -8,11 +8,17 @@ kernel + ONE gradient all-reduce over RCCL (N > 1) + fused SGD, on one batch of 
 synthetic 300x300 images per GPU (BASELINE.json configs[1]; weak scaling), f32.
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run does only what the headline needs: set-up, the untimed spin-up, the warm-up and timed
+steps, --dump-outputs, the line.  --full adds everything else the benchmark measures, each in runs
+of its own after the timed steps (the live traffic passes before them):
   roofline     -- the dominant kernel (by summed time) of the step, timed per launch with HIP
-                  events on the stream the kernels run on, against the f32-MFMA peak;
-  cpu_baseline -- the oracle's torch-CPU restatement of the same step on this box's host cores
-                  (rank 0, N=1 only, bounded sample).
+                  events on the stream the kernels run on, against the f32-MFMA peak; its
+                  `traffic` from two rocprofv3 --pmc child runs (--live-traffic);
+  cpu_baseline -- the oracle's torch-CPU restatement of the same step on the host's cores
+                  (rank 0, N=1 only, bounded sample), and loss_delta_vs_cpu;
+  config.f32_mfma_only / bf16_operand_mode / graph_step -- the same step in other forms (N=1);
+  config.host_enqueue_ms_per_step -- host time to enqueue one step.
+The --no-cpu-baseline / --no-roofline / --no-bf16-leg / --live-traffic off switches trim a --full run.
 
 --dump-outputs DIR writes what rank 0's last timed step returned as DIR/<name>.npy (float32 /
 float64, under 64 MB; see dump_train_outputs).  The time-bounded spin-up leaves no SGD update
@@ -365,8 +371,9 @@ def aux_workload(args, world, rank, dev):
             import ssd_oracle as O
             with torch.no_grad():
                 O.ssd300_forward(torch.randn(2, 3, 300, 300), cpu_fn.params)
-        import ssd_oracle as _O
-        cpu_fn.params = _O.ssd300_random_params(0)
+        if not args.no_cpu_baseline:
+            import ssd_oracle as _O
+            cpu_fn.params = _O.ssd300_random_params(0)
         cpu_units, cpu_sample = 2, "oracle ssd300_forward (torch-CPU) on 2 images of 300x300"
     elif args.workload == "preprocess":
         # (f)-3: VOC-sized 8-bit images (375x500 / 500x375 / 333x500) already in HBM -> normalised (bs,3,300,300)
@@ -632,14 +639,17 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=PER_GPU_BATCH, help="images per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else (roofline, live traffic, cpu_baseline and loss_delta_vs_cpu, the "
+                         "f32-MFMA-only / bf16 / graph-step legs, host enqueue time); a plain run prints the headline line alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline / loss_delta_vs_cpu")
     ap.add_argument("--live-traffic", default="auto", choices=("auto", "on", "off"),
-                    help="roofline.traffic from two rocprofv3 --pmc passes run by this invocation as child processes BEFORE its timed run "
+                    help="--full: roofline.traffic from two rocprofv3 --pmc passes run by this invocation as child processes BEFORE its timed run "
                          "(auto: at N = 1 for the SSD300 train workload when a GPU and rocprofv3 are present; adds about half a minute); off: the committed "
                          "file of the round")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-bf16-leg", action="store_true", help="skip the short bf16-operand run reported in config.bf16_operand_mode")
-    ap.add_argument("--layers", action="store_true", help="print the per-launch table to stderr")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline pass")
+    ap.add_argument("--no-bf16-leg", action="store_true", help="--full without the short f32-MFMA-only, bf16-operand and graph-step runs")
+    ap.add_argument("--layers", action="store_true", help="--full: print the per-launch table of the roofline pass to stderr")
     ap.add_argument("--conv-dtype", default="f32", choices=("f32", "f32x3", "bf16"),
                     help="bf16 = BASELINE configs[2] (bf16-operand fwd/dgrad convs, f32 accumulate); not the headline bench line")
     ap.add_argument("--variant", type=int, default=300, choices=(300, 512), help="512 = build-defined SSD512 (not a bench line)")
@@ -677,7 +687,7 @@ def main():
     ap.add_argument("--graph-step", default="off", choices=("on", "off"),
                     help="time the train step as ONE captured HIP graph replay per step (ddp.GraphedTrainStep) instead of ~250 eager launches. "
                          "Default off: at batch 32 the step is GPU-bound and the replay measures slower on the device than the eager two-stream "
-                         "schedule; the default line reports the replay's numbers beside the headline (config.graph_step)")
+                         "schedule; a --full run reports the replay's numbers beside the headline (config.graph_step)")
     ap.add_argument("--graph-one-stream", action="store_true", help="capture the whole step on one stream (default: the tiny-map group on its second stream inside the graph, as in the eager step)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
@@ -694,6 +704,12 @@ def main():
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and args.workload != "train":
         raise SystemExit("--dump-outputs: only the train workload writes its outputs")
+    if not args.full:
+        if args.layers or args.live_traffic == "on":
+            raise SystemExit("--layers and --live-traffic on report on the roofline pass, which only a --full run makes")
+        # a plain run: the headline and nothing else (the switches below are how a --full run leaves a part out)
+        args.no_cpu_baseline = args.no_roofline = args.no_bf16_leg = True
+        args.live_traffic = "off"
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves, one process per GPU, BEFORE
     # anything in this process touches the GPU (a process that has initialised HIP must not be replaced or forked into ranks).
@@ -903,22 +919,24 @@ def main():
     if args.dump_outputs and rank == 0:                    # before anything below runs another step over the same buffers
         dumped = dump_train_outputs(args.dump_outputs, last if gstep is None else {}, l1, l2, n_pos_local, trainer)
         note(f"outputs of the last timed step: {dumped['bytes'] / 2**20:.1f} MB in {args.dump_outputs}")
-    # host-side enqueue time of ONE step into an empty queue (diagnostic: the step is GPU-bound while this stays below
+    # --full: host-side enqueue time of ONE step into an empty queue (diagnostic: the step is GPU-bound while this stays below
     # ms_per_step; several steps back to back would measure the queue's back-pressure instead)
-    host_ms = host_eager_ms = 0.0
-    for _ in range(3):
-        fence()
-        h0 = time.perf_counter()
-        step()
-        host_ms += (time.perf_counter() - h0) / 3 * 1e3
-    fence()
-    if gstep is not None:
+    host_ms = host_eager_ms = None
+    if args.full:
+        host_ms = host_eager_ms = 0.0
         for _ in range(3):
             fence()
             h0 = time.perf_counter()
-            eager_step()
-            host_eager_ms += (time.perf_counter() - h0) / 3 * 1e3
+            step()
+            host_ms += (time.perf_counter() - h0) / 3 * 1e3
         fence()
+        if gstep is not None:
+            for _ in range(3):
+                fence()
+                h0 = time.perf_counter()
+                eager_step()
+                host_eager_ms += (time.perf_counter() - h0) / 3 * 1e3
+            fence()
     n_pos = float(trainer.flat_grad[trainer.n].item())
     loss = (float(l1.item()) + float(l2.item())) / max(float(n_pos_local.item()), 1.0)
     # self-check of the collective path: every rank adds 1 and its own rank id; rank 0 prints what arrived
@@ -959,7 +977,7 @@ def main():
                       "direct_conv_tflops_per_gpu": round(train_gflop * ips / world / 1e3, 2),
                       "direct_conv_flops_over_f32_mfma_peak": round(train_gflop * ips / world / 1e3 / PEAK_F32_MFMA_TFLOPS, 4),
                       "direct_conv_note": "algorithmic (direct-convolution) FLOPs of the step / time: a speed-up-over-direct figure, NOT a roofline "
-                                          "fraction (Winograd executes 1/4 .. 4/9 of them); the executed fraction is roofline.step_executed_frac",
+                                          "fraction (Winograd executes 1/4 .. 4/9 of them); the executed fraction is roofline.step_executed_frac of a --full line",
                       "last_loss_per_rank": round(loss, 5), "n_pos_global_last": n_pos,
                       "conv_algorithm": ("f32 throughout; Winograd F(%dx%d,3x3) for forward / dgrad of the 3x3 stride-1 layers with >= %d input "
                                          "channels (the 2x2 max pools fused into its output transform) and for the weight gradients of those with >= %d channels on maps <= %d px, direct MFMA "
@@ -972,11 +990,11 @@ def main():
                       "spinup": {"seconds": args.spinup_seconds, "untimed_steps": spin_steps,
                                  "note": "untimed steps run before the warm-up steps so that the timed region sees the shader clock the device HOLDS under "
                                          "this load, not the ramp from idle (bench.py --spinup-seconds; 0 disables)"},
-                      "host_enqueue_ms_per_step": round(host_ms, 2),
+                      "host_enqueue_ms_per_step": None if host_ms is None else round(host_ms, 2),
                       "step_launch": ({"form": "one HIP graph replay per step (ddp.GraphedTrainStep: forward + loss + backward"
                                                + (" + SGD" if world == 1 else "; all-reduce + SGD issued behind it") + ")",
                                        "kernel_launches_in_graph": gstep.kernel_nodes,
-                                       "host_enqueue_ms_per_step_eager": round(host_eager_ms, 2),
+                                       "host_enqueue_ms_per_step_eager": None if host_eager_ms is None else round(host_eager_ms, 2),
                                        "note": "bitwise equal to the eager step (tests/test_gpu_path.py::test_graphed_train_step_is_bitwise_the_eager_step)"}
                                       if gstep is not None else {"form": "eager: every kernel launched from Python"}),
                       "shader_clock_mhz_during_timed_steps": round(mhz, 0),

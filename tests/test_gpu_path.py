@@ -1673,3 +1673,26 @@ def test_rccl_calls_of_the_data_parallel_step_run_with_one_rank():
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "nccl_single_rank.py")], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0 and "rccl single-rank path ok" in r.stdout, (r.returncode, r.stdout[-600:], r.stderr[-1200:])
     assert r.stdout.count("backend nccl") == 2
+
+
+def test_plain_bench_run_prints_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line, and none of the passes that only --full makes
+    (roofline, CPU baseline, loss delta against the CPU, the f32-MFMA-only / bf16 / graph-step legs, host enqueue time)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spinup-seconds", "0"],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(line) == 1, r.stdout
+    out = json.loads(line[0])
+    assert out["metric"] == "images/sec SSD300-VGG16 train step" and out["unit"] == "images/sec" and out["higher_is_better"] is True
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["n_gpus"] == 1 and out["dtype"].startswith("f32")
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 32e3 / out["ms_per_step"]) <= 1e-3 * out["value"] + 0.02
+    assert not {"roofline", "cpu_baseline", "loss_delta_vs_cpu"} & set(out), sorted(out)
+    assert not {"f32_mfma_only", "bf16_operand_mode", "graph_step"} & set(out["config"]), sorted(out["config"])
+    assert out["config"]["host_enqueue_ms_per_step"] is None
+    assert "rocprofv3" not in r.stderr and "roofline pass" not in r.stderr and "cpu baseline" not in r.stderr

@@ -319,6 +319,17 @@ def test_bench_refuses_arguments_it_cannot_honour():
         assert '"metric"' not in r.stdout
 
 
+def test_bench_plain_run_refuses_switches_of_full_runs():
+    """--layers prints the table of the roofline pass and --live-traffic on feeds its traffic figure: without --full there is no such
+    pass, so a plain run with either stops before any GPU is touched instead of quietly leaving it out."""
+    import subprocess
+    import sys
+    for argv in (["--layers"], ["--live-traffic", "on"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and "only a --full run makes" in (r.stderr + r.stdout), (argv, r.stderr[-2000:])
+        assert '"metric"' not in r.stdout
+
+
 @pytest.mark.parametrize("bs", [2, 32, 96])
 def test_bench_dump_outputs_files(tmp_path, bs):
     """bench.py --dump-outputs: float32 / float64 .npy files under 64 MB in all; the parameter and gradient samples sit at the same

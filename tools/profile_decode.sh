@@ -12,5 +12,5 @@ for B in 32 1; do
   cp $(ls $OUT/s$B/*/*kernel_stats.csv | head -1) $OUT/b${B}_kernel_stats.csv
   rm -rf $OUT/s$B
 done
-python3 $ROOT/bench.py --workload decode --batch 32 --steps 50 --warmup 5 > $OUT/b32_bench_plain.json 2> $OUT/b32_plain.err
+python3 $ROOT/bench.py --full --workload decode --batch 32 --steps 50 --warmup 5 > $OUT/b32_bench_plain.json 2> $OUT/b32_plain.err
 ls -la $OUT
