@@ -1139,7 +1139,8 @@ class SSD_300(nn.Module):
     @conv_dtype.setter
     def conv_dtype(self, value: str) -> None:
         """"f32x3": forward / dgrad products formed from three exact bf16 limbs per f32 operand (six bf16 MFMAs per
-        block, f32 accumulate): f32-accurate (measured against f64: not worse than the exact-f32 MFMA kernels)."""
+        block, f32 accumulate, sign-dithered against the bf16 MFMA's truncation): f32-accurate -- kernel errors within 2x of the exact-f32
+        MFMA kernels', and the whole step within the direct engine's decision-pinned bar (1e-5)."""
         if value not in ("f32", "bf16", "f32x3"):
             raise ValueError("conv_dtype must be 'f32', 'f32x3' or 'bf16'")
         self._engine.bf16 = value == "bf16"

@@ -704,6 +704,15 @@ __device__ __forceinline__ void split3(const f32x4 v, bf16x4& hi, bf16x4& mid, b
     }
 }
 
+// Sign dither of the limb products, as in csrc/gemm_x3.hip's gemm_planes_x3_kernel (whose header gives the measurements).  The bf16
+// MFMA truncates its internal sum: a bias of about -1.7e-10 of the magnitude per MFMA, always the same way.  Far below one rounding
+// error, but coherent: a bias gradient sums it over every pixel of a map, and the data-gradient chain carries it from layer to layer
+// (f32x3 step, decision-pinned against f64: conv1_1.bias 4.2e-5 without the dither).  So output row m (a pixel) takes its A operand
+// with sign s(m) and the finished row is multiplied by s(m) again -- limbs of -x are minus the limbs of x, so nothing else changes --
+// and the bias takes the sign s(m) = (-1)^(bit 2 ^ bit 5 of m): zero mean over any 8 consecutive rows.
+__device__ __forceinline__ bool x3_neg_row(int m) { return ((m >> 2) ^ (m >> 5)) & 1; }
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256) void igemm_x3_kernel(const X3Params q) {
     const IgemmParams& p = q.g;
@@ -728,10 +737,12 @@ __global__ __launch_bounds__(256) void igemm_x3_kernel(const X3Params q) {
 
     int a_h[A_ROWS], a_w[A_ROWS];
     unsigned a_base[A_ROWS], voff_a[A_ROWS];
+    bool a_neg[A_ROWS];                             // sign dither of this thread's A rows
     const int HoWo = p.Ho * p.Wo;
 #pragma unroll
     for (int j = 0; j < A_ROWS; ++j) {
         const int m = m0 + row0 + 32 * j;
+        a_neg[j] = x3_neg_row(m);
         const bool ok = m < p.M;
         const int mm = ok ? m : 0;
         const int n = div_small_q(mm, HoWo, p.rcp_howo), rem = mm - n * HoWo;
@@ -803,7 +814,7 @@ __global__ __launch_bounds__(256) void igemm_x3_kernel(const X3Params q) {
 #pragma unroll
         for (int j = 0; j < A_ROWS; ++j) {
             bf16x4 hi, mid, lo;
-            split3(ra[j], hi, mid, lo);
+            split3(a_neg[j] ? -ra[j] : ra[j], hi, mid, lo);
             const int o = (row0 + 32 * j) * LDH + chunk * 4;
             *reinterpret_cast<bf16x4*>(&As[o]) = hi;
             *reinterpret_cast<bf16x4*>(&As[PLANE_A + o]) = mid;
@@ -856,6 +867,14 @@ __global__ __launch_bounds__(256) void igemm_x3_kernel(const X3Params q) {
         }
     }
 
+    // undo the sign dither: accumulator element r of block (i, j) is row m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (x3_neg_row(m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh)) acc[i][j][r] = -acc[i][j][r];
     igemm_epilogue<BM, TM, TN>(p, acc, m0, n0, wm, wn, lr, lh);
 }
 
@@ -866,7 +885,9 @@ __global__ __launch_bounds__(256) void igemm_x3_kernel(const X3Params q) {
 // (tap = an LDS row offset), so the global A traffic and the limb-splitting VALU work drop 9x against the generic
 // kernel, where they -- not the MFMA -- bound the "f32x3" and bf16 variants.  Only the weight tile (pre-split bf16
 // planes, L2-resident) is re-staged per tap, double-buffered: one barrier per tap, one more per channel chunk.
-// PLANES = 3: "f32x3" (six limb products per block); PLANES = 1: plain bf16 operands (plane 0 = RNE bf16 of the weight).
+// PLANES = 3: "f32x3" (six limb products per block, with the sign dither of igemm_x3_kernel: a halo pixel serves several output
+// pixels, so the sign of output row m is applied to the A fragment in registers); PLANES = 1: plain bf16 operands (plane 0 = RNE bf16
+// of the weight).
 // ---------------------------------------------------------------------------------------------
 template <int PH_, int PW_, int BN, int PLANES>
 __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const X3Params q) {
@@ -956,6 +977,8 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const X3Params q) {
     const int pix = wm * 32 + lr, py = pix / PW_, px = pix % PW_;
     const __bf16* a_rd = As + (py * HW_ + px) * LDH + lh * 8;
     const __bf16* b_rd = Bs + (wn * TN * 32 + lr) * LDH + lh * 8;
+    // sign dither (f32x3): this lane's A fragments are rows of output pixel `pix` (eight bf16 of one row per lane)
+    const unsigned a_flip = (PLANES == 3 && x3_neg_row(pix)) ? 0x80008000u : 0u;
 
     issue_a(0);
     issue_b(0);
@@ -977,6 +1000,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const X3Params q) {
 #pragma unroll
             for (int pl = 0; pl < PLANES; ++pl) {
                 af[pl] = *reinterpret_cast<const bf16x8*>(a_rd + pl * PLANE_A + hoff + ks * 16);
+                if constexpr (PLANES == 3) af[pl] = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, af[pl]) ^ a_flip);
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bf[pl][j] = *reinterpret_cast<const bf16x8*>(bb + pl * PLANE_B + j * 32 * LDH + ks * 16);
             }
@@ -1000,6 +1024,13 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const X3Params q) {
         }
     }
 
+    if constexpr (PLANES == 3) {                       // undo the sign dither, row by row
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (x3_neg_row(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh)) acc[j][r] = -acc[j][r];
+    }
     // ---- epilogue: this lane's accumulator rows are patch pixels (wm*32 + row) -------------------------------------------
     // Patches that lie inside the map take straight-line paths (no per-element bounds test; the loads of eight rows in flight
     // before their first use): vector instructions next to the resident MFMA loops are the expensive part of a block's edges.

@@ -400,44 +400,64 @@ def bf16_spacing(t):
     return torch.pow(torch.full_like(a, 2.0), torch.floor(torch.log2(a)) - 7.0)
 
 
-def _pin_store(name, fwd, bwd, report, kind, gate):
+def _norms(t):
+    """(rms, max|t|) of a tensor, in f64"""
+    import torch
+    if t.numel() == 0:
+        return 0.0, 0.0
+    return float(torch.linalg.vector_norm(t, dtype=torch.float64)) / math.sqrt(t.numel()), float(t.abs().max())
+
+
+def pin_scales(pinned):
+    """TESTS ONLY.  {report key: (rms, max|.|)} of every stored tensor of a `pinned` dict (`ssd300_forward`; tensors on any device): the
+    norms `_pin_store` measures against, taken once over the whole batch for an evaluation in chunks of images."""
+    out = {n + ":fwd": _norms(t) for n, t in pinned["fwd"].items()}
+    out.update({n + ":bwd": _norms(t) for n, t in pinned["bwd"].items()})
+    return out
+
+
+def _pin_store(name, fwd, bwd, report, kind, gate, scale=None):
     """TESTS ONLY (the rounding-pinned comparison of the bf16-tensor mode).  An identity that REPLACES what flows through it by the
     values ANOTHER evaluation of the same network stored at this point: on the way forward the activation tensor `fwd`, on the way
     back the gradient tensor `bwd` (None: pass the gradient through).  Every layer of this evaluation then sees exactly the other
     evaluation's inputs -- the stored bf16 / f32 values, i.e. its rounding DIRECTIONS are pinned like its ReLU / arg-max decisions --
     and `report[name + ':fwd' | ':bwd']` records how far this evaluation's own value was from the one it is replaced by:
 
-        max over elements of (|own - stored| - 2e-5 * rms(own)) / spacing,   spacing = the bf16 spacing at |stored| (kind 'bf16')
-                                                                              or 1e-5 * max|stored|            (kind 'f32')
+        max over elements of (|own - stored| - 2e-5 * rms(stored)) / spacing,   spacing = the bf16 spacing at |stored| (kind 'bf16')
+                                                                                 or 1e-5 * max|stored|            (kind 'f32')
 
     -- for a correct layer <= 0.5 (one rounding to nearest) on a bf16 tensor, <= 1 on an f32 tensor; the rms term covers sums that
     cancel to (almost) nothing, whose f32 accumulation error is set by the size of the terms, not of the result.
     gate: bool tensor or None -- the gradient is compared where gate is set only (a post-ReLU tensor's stored gradient is already
-    masked by the ReLU that follows on the way back)."""
+    masked by the ReLU that follows on the way back).
+    scale: {report key: (rms, max|.|)} or None -- the tensor-wide norms of the stored tensors over the WHOLE batch (`pin_scales`), given
+    when this evaluation sees only a chunk of its images: the report then does not depend on how the batch was split.  An entry
+    already in `report` (from an earlier chunk) is kept where it is the larger one."""
     import torch
 
-    def dev(own, stored, mask):
+    def dev(own, stored, mask, key):
         own, stored = own.detach().double(), stored.double()
-        rms = float(own.pow(2).mean().sqrt())
-        space = bf16_spacing(stored) if kind == "bf16" else torch.full_like(stored, 1e-5 * max(float(stored.abs().max()), 1e-30))
+        rms, amax = scale[key] if scale is not None and key in scale else _norms(stored)
+        space = bf16_spacing(stored) if kind == "bf16" else torch.full_like(stored, 1e-5 * max(amax, 1e-30))
         d = ((own - stored).abs() - 2e-5 * rms) / space
         if mask is not None:
             d = d * mask.to(d.dtype)
-        return float(d.max()) if d.numel() else 0.0
+        v = float(d.max()) if d.numel() else 0.0
+        report[key] = max(report.get(key, v), v)
 
     class PinStore(torch.autograd.Function):
         @staticmethod
         def forward(ctx, z):
             if fwd is None:                      # a branch pin: only the gradient flowing back through THIS reader is replaced
                 return z.view_as(z)
-            report[name + ":fwd"] = dev(z, fwd, None)
+            dev(z, fwd, None, name + ":fwd")
             return fwd.to(z.dtype)
 
         @staticmethod
         def backward(ctx, g):
             if bwd is None:
                 return g
-            report[name + ":bwd"] = dev(g if gate is None else g * gate.to(g.dtype), bwd, gate)
+            dev(g if gate is None else g * gate.to(g.dtype), bwd, gate, name + ":bwd")
             return bwd.to(g.dtype)
     return PinStore.apply
 
@@ -484,6 +504,9 @@ def _conv_bf16_operands():
     return conv
 
 
+# the heads that run the bf16-tensor kernels in the bf16-tensor mode of the build, SSD300 and SSD512 alike: c_4 on the bf16 trunk, c_7 on a
+# bf16 copy of fc7's output (the last reader of a 19x19 / 32x32 map; c_8 on SSD512's 16x16 map is not the last reader of a8)
+BF16_TENSOR_HEADS = ("c_4", "c_7")
 _VGG_ACT = ("a1_1", "a1_2", "a2_1", "a2_2", "a3_1", "a3_2", "a3_3", "a4_1", "a4_2", "a4_3", "a5_1", "a5_2", "a5_3")
 
 
@@ -502,7 +525,7 @@ def pinned_max_pool(z, code, k: int, stride: int, pad: int):
 
 
 def ssd300_forward(x, params, return_features: bool = False, variant: int = 300, operand_round: str = None, acts: dict = None,
-                   decisions: dict = None, store_round: bool = False, pinned: dict = None):
+                   decisions: dict = None, store_round: bool = False, pinned: dict = None, act_grads: dict = None):
     """x (bs,3,300,300) f32 NCHW torch tensor -> loc (bs,8732,4), conf (bs,8732,21).
     store_round (with operand_round="bf16"): the bf16-TENSOR mode -- the VGG trunk's tensors (conv1_1 .. conv5_3 outputs, the pools'
     outputs, the L2-norm's output) are stored in bf16, and so are their gradients (`_round_store`); fc6 onwards keeps f32 tensors.
@@ -513,13 +536,15 @@ def ssd300_forward(x, params, return_features: bool = False, variant: int = 300,
     fixed linear-in-pieces function: two evaluations differ by arithmetic only, not by a ReLU / arg-max that flipped on a last-bit
     difference (which is a discrete jump of one gradient path).
     pinned (tests only, with decisions): {"fwd": {tensor name: NCHW values}, "bwd": {tensor name: NCHW gradient}, "bf16": set of the
-    names stored in bf16, "report": {}} -- every named tensor (a1_1 .. a11, p1 .. p5, n4_3) and its gradient are REPLACED by the
+    names stored in bf16, "report": {}, optional "scale": `pin_scales` of the whole batch} -- every named tensor (a1_1 .. a11, p1 .. p5, n4_3) and its gradient are REPLACED by the
     given values of another evaluation as they pass (`_pin_store`), and `report` receives this evaluation's distance to them,
     tensor by tensor.  Replaces `store_round`'s own rounding: the other evaluation's rounding directions are followed.
     operand_round="bf16": every convolution multiplies bf16-rounded operands with f32 accumulation (`_conv_bf16_operands`:
     BASELINE.json configs[2]); pools, L2-norm, biases, ReLU and the tensors between layers stay f32.
     acts: optional dict, filled with every post-ReLU activation (NCHW, detached) under the build's tensor names
     (a1_1 .. a5_3, a6, a7, a8a, a8, ... , n4_3): lets a test follow the two computations layer by layer.
+    act_grads (tests only, with acts): receives the same tensors NOT detached, with retain_grad(): after a backward, `.grad` is the
+    gradient of each stored tensor (before the ReLU mask of its producer and, in store_round mode, before its rounding).
 
     Model.py:203-235: conv1_1..conv4_3 with 2x2/s2 pools (third one
     ceil_mode, :137); L2-norm over channels * gamma, no epsilon (:206-209);
@@ -544,10 +569,16 @@ def ssd300_forward(x, params, return_features: bool = False, variant: int = 300,
         if pinned is not None and name in pinned["fwd"]:
             relu_gate = (pinned["fwd"][name] > 0) if name[0] == "a" else None        # a*: post-ReLU activations; p*, n4_3: no ReLU of their own
             return _pin_store(name, pinned["fwd"][name], pinned["bwd"].get(name), pinned["report"],
-                              "bf16" if name in pinned["bf16"] else "f32", relu_gate)(t)
+                              "bf16" if name in pinned["bf16"] else "f32", relu_gate, pinned.get("scale"))(t)
         return rs_plain(t) if trunk else t
     feats = {}
     h = x
+
+    def note(name, t):
+        acts[name] = t.detach()
+        if act_grads is not None and t.requires_grad:
+            t.retain_grad()
+            act_grads[name] = t
     pin_relu = None if decisions is None else decisions["relu"]
     pin_pool = None if decisions is None else decisions["pool"]
 
@@ -571,7 +602,7 @@ def ssd300_forward(x, params, return_features: bool = False, variant: int = 300,
                            params[f"model.features.{idx}.bias"], padding=1, **(first if li == 0 else {})), _VGG_ACT[li]), _VGG_ACT[li])
         n = li + 1
         if acts is not None:
-            acts[_VGG_ACT[li]] = h.detach()
+            note(_VGG_ACT[li], h)
         if n == 10:
             feats["conv4_3"] = h
         if n in pools_after:
@@ -582,31 +613,32 @@ def ssd300_forward(x, params, return_features: bool = False, variant: int = 300,
     if pinned is not None and "a4_3:1" in pinned["bwd"]:
         # conv4_3's output has two readers; the other evaluation stored the L2-norm's contribution to its gradient (rounded to bf16) before
         # the pool's was added to it: follow that intermediate value too, so that each of the two roundings is compared on its own
-        c43 = _pin_store("a4_3:1", None, pinned["bwd"]["a4_3:1"], pinned["report"], "bf16" if "a4_3" in pinned["bf16"] else "f32", None)(c43)
+        c43 = _pin_store("a4_3:1", None, pinned["bwd"]["a4_3:1"], pinned["report"], "bf16" if "a4_3" in pinned["bf16"] else "f32", None,
+                         pinned.get("scale"))(c43)
     norm = c43.pow(2).sum(dim=1, keepdim=True).sqrt()
     c43n = rs(c43 / norm * params["rescaling_conv_4_3"], "n4_3")
     h = rs(relu(conv2d(h, params["conv_fc6.weight"], params["conv_fc6.bias"], padding=4, dilation=4), "a6"), "a6", trunk=False)
     if acts is not None:
-        acts["n4_3"], acts["a6"] = c43n.detach(), h.detach()
+        note("n4_3", c43n)
+        note("a6", h)
     h = rs(relu(conv2d(h, params["conv_fc7.weight"], params["conv_fc7.bias"]), "a7"), "a7", trunk=False)
     if acts is not None:
-        acts["a7"] = h.detach()
+        note("a7", h)
     srcs = [c43n, h]
     for name, _, _, _, stride, pad in (AUX if variant == 300 else AUX_512):
         h = rs(relu(conv2d(h, params[f"{name}.0.weight"], params[f"{name}.0.bias"]), "a" + name[3:] + "a"), "a" + name[3:] + "a", trunk=False)
         if acts is not None:
-            acts["a" + name[3:] + "a"] = h.detach()
+            note("a" + name[3:] + "a", h)
         h = rs(relu(conv2d(h, params[f"{name}.2.weight"], params[f"{name}.2.bias"], stride=stride, padding=pad), "a" + name[3:]), "a" + name[3:],
                trunk=False)
         if acts is not None:
-            acts["a" + name[3:]] = h.detach()
+            note("a" + name[3:], h)
         srcs.append(h)
     bs = x.shape[0]
     locs, confs = [], []
     for (name, _, _), s in zip(HEADS if variant == 300 else HEADS_512, srcs):
-        # the heads that run the bf16-tensor kernels (c_4 on the bf16 trunk, c_7 on a bf16 copy of fc7's output): their packed gradient
-        # exists in bf16 only, so the bias gradient sums the rounded values
-        hk = {"dy_bf16": True} if (store_round and name in ("c_4", "c_7")) else {}
+        # the heads that run the bf16-tensor kernels: their packed gradient exists in bf16 only, so the bias gradient sums the rounded values
+        hk = {"dy_bf16": True} if (store_round and name in BF16_TENSOR_HEADS) else {}
         bb = conv2d(s, params[f"{name}_bb.weight"], params[f"{name}_bb.bias"], padding=1, **hk)
         cl = conv2d(s, params[f"{name}_cl.weight"], params[f"{name}_cl.bias"], padding=1, **hk)
         locs.append(bb.permute(0, 2, 3, 1).reshape(bs, -1, 4))
@@ -617,9 +649,11 @@ def ssd300_forward(x, params, return_features: bool = False, variant: int = 300,
     return loc, conf
 
 
-def multibox_loss_torch(loc, conf, boxes, classes, pri_cxcywh=None, neg_select=None):
+def multibox_loss_torch(loc, conf, boxes, classes, pri_cxcywh=None, neg_select=None, n_pos=None):
     """Differentiable torch-CPU form of multibox_loss (same selection logic,
     matching done by match_priors) used as the CPU train-step baseline.
+    n_pos (tests only): the positive count both losses are divided by, instead of this call's own -- a batch evaluated in chunks of
+    images, each chunk divided by the WHOLE batch's count, sums to the loss of the batch.
     neg_select (tests only): bool (bs, P), the hard negatives ANOTHER evaluation picked; used instead of this one's own top-k
     (the decision-pinned comparison: a negative that enters or leaves the top-k on a last-bit difference of its cross-entropy is a
     discrete jump of the conf gradient)."""
@@ -636,7 +670,10 @@ def multibox_loss_torch(loc, conf, boxes, classes, pri_cxcywh=None, neg_select=N
                        np.broadcast_to(pri_cxcywh[None], (bs, P, 4))[pos_np])
     pos = torch.from_numpy(pos_np)
     cls_t = torch.from_numpy(cls)
-    loc_loss = (loc[pos] - torch.from_numpy(g)).abs().mean()
+    if n_pos is None:
+        loc_loss = (loc[pos] - torch.from_numpy(g)).abs().mean()
+    else:
+        loc_loss = (loc[pos] - torch.from_numpy(g)).abs().sum() / (4.0 * n_pos)
     cce = F.cross_entropy(conf.reshape(-1, C), cls_t.reshape(-1), reduction="none").view(bs, P)
     neg = cce.clone()
     neg[pos] = 0.
@@ -644,12 +681,12 @@ def multibox_loss_torch(loc, conf, boxes, classes, pri_cxcywh=None, neg_select=N
         sel = torch.as_tensor(neg_select, dtype=torch.bool)
         if tuple(sel.shape) != (bs, P) or bool((sel & pos).any()) or not bool((sel.sum(1) == torch.clamp(3 * pos.sum(1), max=P - pos.sum(1))).all()):
             raise ValueError("neg_select must pick min(3 * n_pos, n_neg) negatives per image")
-        conf_loss = (cce[sel].sum() + cce[pos].sum()) / pos.sum().to(cce.dtype)
+        conf_loss = (cce[sel].sum() + cce[pos].sum()) / (pos.sum().to(cce.dtype) if n_pos is None else float(n_pos))
         return loc_loss, conf_loss
     neg_sorted, _ = neg.sort(dim=1, descending=True)
     k = 3 * pos.sum(dim=1, keepdim=True)
     hn = torch.arange(P)[None, :] < k
-    conf_loss = (neg_sorted[hn].sum() + cce[pos].sum()) / pos.sum().float()
+    conf_loss = (neg_sorted[hn].sum() + cce[pos].sum()) / (pos.sum().float() if n_pos is None else float(n_pos))
     return loc_loss, conf_loss
 
 

@@ -630,3 +630,65 @@ def test_oracle_pinned_to_its_own_stored_tensors_is_the_unpinned_oracle():
     # a3_2 itself is off, a3_3 was computed from the perturbed a3_2 and is off too; a4_1 sees the stored (clean) a3_3 / p3 again
     assert pin2["report"]["a3_2:fwd"] > 1.0 and pin2["report"]["a3_3:fwd"] > 1.0
     assert pin2["report"]["a3_1:fwd"] <= 0.5 and pin2["report"]["a4_1:fwd"] <= 0.5
+
+
+def test_chunked_pinned_f64_evaluation_equals_the_whole_batch():
+    """tests/grad_measure.py evaluates the pinned f64 oracle in chunks of images (a whole f64 graph of bench.py's batch of 32 would need
+    tens of GB of host memory), each chunk's losses divided by the positive count of the WHOLE batch.  On a batch of 3 pinned to the
+    oracle's OWN decisions, stored tensors and stored gradients (which carry the whole batch's normalisation, as the HIP step's do), one
+    chunk of 1 and one of 2 images must give what the batch in one piece gives: both losses and all 71 gradients within 1e-12, the same
+    per-layer report, every layer within its own rounding; and the losses equal the unpinned run's."""
+    import grad_measure as M
+    params = O.ssd300_random_params(5)
+    x = torch.randn(3, 3, 300, 300, generator=torch.Generator().manual_seed(6))
+    boxes = [np.array([[.1, .2, .6, .7], [.5, .4, .9, .95]], np.float32), np.array([[.05, .05, .95, .95]], np.float32),
+             np.array([[.3, .1, .7, .5], [.0, .6, .3, 1.], [.42, .42, .52, .55]], np.float32)]
+    classes = [np.array([3., 11.], np.float32), np.array([0.], np.float32), np.array([19., 7., 2.], np.float32)]
+    decisions, neg, pinned, (u1, u2) = M.oracle_self_decisions(params, x, boxes, classes, bf16=True)
+    assert M.chunk_spans(3, 300, [1, 2]) == [(0, 1), (1, 3)] and M.chunk_spans(32, 300) == [(i, i + 4) for i in range(0, 32, 4)]
+    out = []
+    for chunk in (3, [1, 2]):
+        pin = dict(pinned, report={})
+        out.append(M.f64_rounding_pinned_grads(params, decisions, neg, pin, case=(x, boxes, classes), chunk=chunk) + (pin["report"],))
+    (a1, a2, ga, ra), (b1, b2, gb, rb) = out
+    for whole, part, unpinned in ((a1, b1, u1), (a2, b2, u2)):
+        assert abs(whole - part) <= 1e-12 * abs(whole) and abs(whole - unpinned) <= 1e-12 * abs(whole), (whole, part, unpinned)
+    assert set(ga) == set(gb) == set(params) and len(ga) == 71
+    for k in ga:
+        assert float(ga[k].norm()) > 0, k
+        assert float((ga[k] - gb[k]).norm()) <= 1e-12 * float(ga[k].norm()), k
+    assert len(pinned["bwd"]) == len(pinned["fwd"]) == 24
+    assert set(ra) == set(rb) == {n + ":fwd" for n in pinned["fwd"]} | {n + ":bwd" for n in pinned["bwd"]}
+    assert all(abs(ra[k] - rb[k]) <= 1e-9 for k in ra), {k: (ra[k], rb[k]) for k in ra if ra[k] != rb[k]}
+    # its own stored values: within half a bf16 spacing of its own result on the trunk, and equal to it elsewhere
+    assert all(v <= (0.5 if k.split(":")[0] in pinned["bf16"] else 0.0) for k, v in ra.items()), ra
+
+
+def test_loss_normaliser_argument_scales_losses_and_gradients_exactly():
+    """O.multibox_loss_torch(n_pos=...): both losses and every gradient are the default ones times (own positive count / n_pos), with
+    the oracle's own hard negatives and with given ones; the default is the call without the argument"""
+    rng = np.random.default_rng(8)
+    boxes = [np.array([[.1, .2, .6, .7], [.5, .4, .9, .95]], np.float32), np.array([[.3, .1, .7, .5]], np.float32)]
+    classes = [np.array([3., 11.], np.float32), np.array([19.], np.float32)]
+    pri = O.create_priors_ssd300()
+    _, cls, _, _, _ = O.match_priors(boxes, classes, O.xywh_to_xyxy(pri))
+    own = int((cls != O.BG_CLASS).sum())
+    loc0 = torch.from_numpy(rng.standard_normal((2, 8732, 4)))
+    conf0 = torch.from_numpy(rng.standard_normal((2, 8732, 21)) * 2)
+    neg = torch.from_numpy(O.multibox_loss(loc0.float().numpy(), conf0.float().numpy(), boxes, classes, want_grads=False)["hn_mask"])
+    bt, ct = [torch.from_numpy(b) for b in boxes], [torch.from_numpy(c) for c in classes]
+
+    def run(**kw):
+        loc, conf = loc0.clone().requires_grad_(True), conf0.clone().requires_grad_(True)
+        a1, a2 = O.multibox_loss_torch(loc, conf, bt, ct, **kw)
+        (a1 + a2).backward()
+        return float(a1), float(a2), loc.grad, conf.grad
+    for sel in (None, neg):
+        ref = run(neg_select=sel)
+        assert ref[:2] == run(neg_select=sel, n_pos=None)[:2]
+        for n in (own, 37):
+            got = run(neg_select=sel, n_pos=n)
+            s = own / n
+            assert abs(got[0] - s * ref[0]) <= 1e-14 * ref[0] and abs(got[1] - s * ref[1]) <= 1e-14 * ref[1], (n, got[:2], ref[:2])
+            for g, r in zip(got[2:], ref[2:]):
+                assert float((g - s * r).abs().max()) <= 1e-14 * float(r.abs().max()), n
