@@ -159,6 +159,19 @@ int ssd_conv2d_wgrad(const float* x, const float* dy, int ldy, float* dw_oihw, f
  * timings to kernel instantiations; no effect on results. */
 int ssd_conv2d_igemm_tile(const ssd_conv_geom* g, int direction, int* bm, int* bn);
 int ssd_conv2d_wgrad_tile(const ssd_conv_geom* g, int* bt, int* nsplit);
+/* Host-only plan queries (no GPU needed); each reports what the entry point launches under the current tuning aids, from the same function
+ * the dispatcher calls.
+ * ssd_conv2d_wgrad_plan: plan[8] = kernel (0 one tap per block, 1 f32 nine-tap, 2 bf16 patch kernel), tile edge, LDS stages, f32 nine-tap
+ *   patch shape (0 = 4x8, 1 = 1x38, 2 = 2x19; -1 otherwise), bf16 patch form (0 = 3x3, 1 = dilation 4, 2 = 1x1; -1 otherwise), nsplit,
+ *   positions (or patches) per split, slab reduction (1 = one block per tap, 0 = per output channel and 64 input channels); bf16 selects
+ *   ssd_conv2d_wgrad_bf16 / ssd_conv3x3_wgrad_bf16t (the latter takes bf16 patch-kernel plans only).
+ * ssd_conv3x3_bf16_plan: plan[4] = position space (0 = 8x32 patches, 1 = 16x16, 2 = flat), N tile (64 / 128), halo pieces per wave,
+ *   persistent K = 64 kernel (0 / 1) of ssd_conv3x3_bf16 on an N x H x W map with K input and n_out output channels.
+ * ssd_conv3x3_halo_shape: the halo kernel's patch shape for a forward (direction 0) or data gradient (1) with 1 (bf16-operand) or 3
+ *   (f32x3) weight planes: 0 = not taken (the igemm runs), 1 = 8x8, 2 = 8x16 patches. */
+int ssd_conv2d_wgrad_plan(const ssd_conv_geom* g, int bf16, int* plan);
+int ssd_conv3x3_bf16_plan(int N, int H, int W, int K, int n_out, int* plan);
+int ssd_conv3x3_halo_shape(const ssd_conv_geom* g, int direction, int planes);
 /* Tuning aids (process-global, not thread-safe, results unchanged): force the igemm tile
  * (0 = 256x64, 1 = 128x128, 2 = 128x64, 3 = 64x64) / LDS stage count (1|2), and the wgrad tile edge
  * (64|128) / stage count / split-K target in blocks per CU.  -1 = automatic. */

@@ -691,23 +691,45 @@ int launch_shape(HaloParams& p, hipStream_t st) {
     return SSD_OK;
 }
 
-int dispatch(HaloParams& p, hipStream_t st) {
+// The launch of conv3x3_bf16 for an N x H x W map, K input and n_out output channels under the current tuning aids: position space
+// (mode), N tile (bn), halo pieces per wave (apw) and whether the persistent K = 64 kernel takes it.  dispatch launches exactly this
+// plan and ssd_conv3x3_bf16_plan reports it, so the two cannot drift.
+struct Bf16Plan {
+    int mode, bn, apw, persistent;
+};
+
+Bf16Plan plan_bf16(int N, int H, int W, int K, int Nout) {
+    Bf16Plan pl{};
     int mode = g_force_mode;
     // flat space (mode 2) while the halo of a 256-position tile -- 256 + 2 (W + 1) + 2 rows -- fits the buffers: 6 pieces per wave (384 rows)
     // up to W = 62, 7 pieces (448 rows; two such buffers + the weight ring are exactly the CU's 160 KB) up to W = 94.  Round 4: the
     // 75 x 75 maps (conv3_x) moved here from the 16 x 16 patches: 1 444 blocks instead of 1 600 (no 80 x 80 cover of a 75 x 75 map);
     // measured interleaved (tools/conv_bf16_bench.py): conv3_2 forward 0.290 -> 0.274 ms, data gradient 0.265 -> 0.245, conv3_1's 0.140 -> 0.120.
-    const int flat_rows = 256 + 2 * (p.W + g_flat_gap) + 2;
-    if (mode < 0) mode = flat_rows <= 448 ? 2 : ((p.W >= 128 && p.H >= 128) ? 0 : 1);
+    const int flat_rows = 256 + 2 * (W + g_flat_gap) + 2;
+    if (mode < 0) mode = flat_rows <= 448 ? 2 : ((W >= 128 && H >= 128) ? 0 : 1);
     if (mode == 2 && flat_rows > 448) mode = 1;
     int bn = g_force_bn;
-    if (bn < 0) bn = p.Nout <= 64 ? 64 : 128;
+    if (bn < 0) bn = Nout <= 64 ? 64 : 128;
     // a launch whose 128-channel tiles would occupy at most half of the CUs (the c_7 head's forward: 50 position tiles x 2 = 100 blocks with
     // 144 stages each) takes 64-channel tiles: 150 blocks of half the length (measured 0.107 -> 0.072 ms)
     if (g_force_bn < 0 && bn == 128 && mode == 2 && flat_rows <= 384 &&
-        ssd_cdiv(p.N * (p.H + 1) * (p.W + g_flat_gap), 256) * ssd_cdiv(p.Nout, 128) <= 128)
+        ssd_cdiv(N * (H + 1) * (W + g_flat_gap), 256) * ssd_cdiv(Nout, 128) <= 128)
         bn = 64;
-    if (bn == 64 && mode == 0 && p.K == 64 && p.Nout <= 64 && g_k64 != 0) {
+    if (bn == 64 && mode == 0 && K == 64 && Nout <= 64 && g_k64 != 0) {
+        pl.mode = 0; pl.bn = 64; pl.persistent = 1;
+        pl.apw = (((8 + 2) * (32 + 2) + 7) / 8 + 7) / 8;       // conv3x3_bf16_k64_kernel's APW: the 10 x 34 halo of an 8 x 32 patch
+        return pl;
+    }
+    if (bn == 64 && mode == 2 && flat_rows > 384) mode = 1;    // (the 64-channel flat form has the 6-piece buffers only)
+    pl.mode = mode; pl.bn = bn; pl.persistent = 0;
+    if (bn == 64) pl.apw = mode == 0 ? 10 : 6;
+    else pl.apw = (mode == 2 && flat_rows > 384) ? 7 : 6;
+    return pl;
+}
+
+int dispatch(HaloParams& p, hipStream_t st) {
+    const Bf16Plan pl = plan_bf16(p.N, p.H, p.W, p.K, p.Nout);
+    if (pl.persistent) {
         p.npw = ssd_cdiv(p.W, 32);
         p.nph = ssd_cdiv(p.H, 8);
         p.tiles_m = p.N * p.npw * p.nph;
@@ -718,20 +740,28 @@ int dispatch(HaloParams& p, hipStream_t st) {
         SSD_CHECK_LAUNCH();
         return SSD_OK;
     }
-    if (bn == 64) {
-        if (mode == 2 && flat_rows > 384) mode = 1;               // (the 64-channel flat form has the 6-piece buffers only)
+    if (pl.bn == 64) {
         // 64 output channels: wave tile 64 x 64 over 512 positions (16 x 32 patches; one halo buffer, K has one or two chunks here)
-        if (mode == 0) return launch<2, 2, 8, 1, 0, 16, 10, false>(p, st);
-        if (mode == 1) return launch<2, 1, 4, 2, 1, 16, 6, true>(p, st);
+        if (pl.mode == 0) return launch<2, 2, 8, 1, 0, 16, 10, false>(p, st);
+        if (pl.mode == 1) return launch<2, 1, 4, 2, 1, 16, 6, true>(p, st);
         return launch<2, 1, 4, 2, 2, 0, 6, true>(p, st);
     }
-    if (mode == 0) return launch<2, 2, 4, 2, 0, 8, 6, true>(p, st);
-    if (mode == 1) return launch<2, 2, 4, 2, 1, 16, 6, true>(p, st);
-    if (flat_rows > 384) return launch<2, 2, 4, 2, 2, 0, 7, true>(p, st);
+    if (pl.mode == 0) return launch<2, 2, 4, 2, 0, 8, 6, true>(p, st);
+    if (pl.mode == 1) return launch<2, 2, 4, 2, 1, 16, 6, true>(p, st);
+    if (pl.apw == 7) return launch<2, 2, 4, 2, 2, 0, 7, true>(p, st);
     return launch<2, 2, 4, 2, 2, 0, 6, true>(p, st);
 }
 
 }  // namespace
+
+// see include/ssd_gfx950.h
+extern "C" int ssd_conv3x3_bf16_plan(int N, int H, int W, int K, int n_out, int* plan) {
+    if (!plan) return SSD_ERR_NULL;
+    if (N <= 0 || H <= 0 || W <= 0 || K <= 0 || n_out <= 0) return SSD_ERR_BAD_SHAPE;
+    const Bf16Plan pl = plan_bf16(N, H, W, K, n_out);
+    plan[0] = pl.mode; plan[1] = pl.bn; plan[2] = pl.apw; plan[3] = pl.persistent;
+    return SSD_OK;
+}
 
 // Tuning aid (tools/conv_bf16_bench.py): force the position space / N tile; -1 = automatic.
 extern "C" int ssd_tune_set_conv_bf16(int mode, int bn) {

@@ -1096,19 +1096,24 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const X3Params q) {
 
 int g_halo = -1;             // tuning aid: 0 = never use the halo kernel, 1 = 8x8 patches, 2 = 8x16 patches; -1 = automatic
 
+// Patch shape the halo kernel takes for a launch whose output map is ho x wo (the data gradient's output is the input map):
+// 0 = not a halo case, 1 = 8x8 patches, 2 = 8x16 patches.  try_halo and ssd_conv3x3_halo_shape both ask this function.
+int halo_shape(const ssd_conv_geom* g, int ho, int wo, int planes) {
+    if (g_halo == 0 || g->R != 3 || g->S != 3 || g->stride != 1 || g->dil != 1 || g->pad != 1) return 0;
+    if (g_halo > 0) return g_halo;
+    // measured (tools/conv_bench.py x3 / halobf16): with three limbs the halo tile only wins on the 150^2 and 300^2 maps;
+    // with one bf16 plane it wins down to 38^2.  8x16 patches beat 8x8 everywhere.
+    if (ho < 30 || wo < (planes == 3 ? 64 : 30)) return 0;
+    return 2;
+}
+
 // returns SSD_OK when launched, 1 when the geometry is not a halo case
 template <int PLANES>
 int try_halo(X3Params& q, const ssd_conv_geom* g, hipStream_t st) {
-    if (g_halo == 0 || g->R != 3 || g->S != 3 || g->stride != 1 || g->dil != 1 || g->pad != 1) return 1;
     IgemmParams& p = q.g;
+    const int shape = halo_shape(g, p.Ho, p.Wo, PLANES);
+    if (shape == 0) return 1;
     const int images = p.M / (p.Ho * p.Wo);
-    int shape = g_halo;
-    if (shape < 0) {
-        // measured (tools/conv_bench.py x3 / halobf16): with three limbs the halo tile only wins on the 150^2 and 300^2 maps;
-        // with one bf16 plane it wins down to 38^2.  8x16 patches beat 8x8 everywhere.
-        if (p.Ho < 30 || p.Wo < (PLANES == 3 ? 64 : 30)) return 1;
-        shape = 2;
-    }
     p.tiles_n = ssd_cdiv(p.Nout, 64);
     if (shape == 2) {
         p.tiles_m = images * ssd_cdiv(p.Ho, 8) * ssd_cdiv(p.Wo, 16);
@@ -1573,6 +1578,12 @@ extern "C" int ssd_tune_set_igemm_x3(int tile) {
     if (tile < -1 || tile > 3 || tile == 0) return SSD_ERR_BAD_SHAPE;
     g_x3_tile = tile;
     return SSD_OK;
+}
+// see include/ssd_gfx950.h
+extern "C" int ssd_conv3x3_halo_shape(const ssd_conv_geom* g, int direction, int planes) {
+    if (!g) return SSD_ERR_NULL;
+    if ((direction != 0 && direction != 1) || (planes != 1 && planes != 3)) return SSD_ERR_BAD_SHAPE;
+    return direction == 0 ? halo_shape(g, g->Ho, g->Wo, planes) : halo_shape(g, g->H, g->W, planes);
 }
 extern "C" int ssd_tune_set_halo(int mode) {
     if (mode < -1 || mode > 2) return SSD_ERR_BAD_SHAPE;

@@ -653,14 +653,16 @@ int g_force_bt = -1, g_force_wnbuf = -1, g_force_blocks_per_cu = -1;   // tuning
 
 struct WgradPlan {
     int bt, nbuf, fused, shape, tiles_co, tiles_ci, nsplit, m_per_split;      // shape: 0 = 4x8 patches, 1 = 1x38, 2 = 2x19
+    int form;              // bf16 patch kernel: 0 = 3x3, 1 = dilation 4, 2 = 1x1
+    int tap_reduce;        // slab reduction: 1 = one block per (output channel, 64 input channels, tap), 0 = per (output channel, 64 input channels)
     size_t slab_floats, bias_floats;
 };
 
 int g_force_fused = -1;          // tuning aid: 0 = never use the fused 3x3 kernel, 1 = whenever applicable
 int g_force_shape = -1;          // tuning aid: patch shape of the f32 fused kernel (0 = 4x8, 1 = 1x38, 2 = 2x19); -1 = least padding
 
-WgradPlan plan_wgrad(const ssd_conv_geom* g, bool bf16 = false) {
-    WgradPlan pl;
+WgradPlan plan_kernel(const ssd_conv_geom* g, bool bf16) {
+    WgradPlan pl{};
     const int T = g->R * g->S;
     const int M = g->N * g->Ho * g->Wo;
     // fused nine-tap kernel: measured 117-130 TFLOP/s on conv1_2..conv4_3 against 92-123 for one tap per block.  Its K loop
@@ -740,6 +742,16 @@ WgradPlan plan_wgrad(const ssd_conv_geom* g, bool bf16 = false) {
     return pl;
 }
 
+// Everything the weight gradient launches for this geometry and `bf16` under the current tuning aids: conv2d_wgrad_impl launches this
+// plan and ssd_conv2d_wgrad_plan reports it, so the two cannot drift.
+WgradPlan plan_wgrad(const ssd_conv_geom* g, bool bf16 = false) {
+    WgradPlan pl = plan_kernel(g, bf16);
+    pl.form = g->R == 1 ? 2 : (g->dil == 4 ? 1 : 0);
+    const int rblocks = g->Co * ssd_cdiv(g->Ci, 64);
+    pl.tap_reduce = rblocks < 512 && pl.nsplit >= 32;           // few blocks, long sums: one block per tap as well
+    return pl;
+}
+
 }  // namespace
 
 extern "C" size_t ssd_conv2d_wgrad_workspace(const ssd_conv_geom* g) {
@@ -776,7 +788,7 @@ static int conv2d_wgrad_impl(const float* x, const float* dy, int ldy, float* dw
     if (in_bf16 && !(pl.fused && bf16)) return SSD_ERR_BAD_SHAPE;       // bf16 tensors: the patch kernel only
     if (pl.fused && bf16) {
         const dim3 grid(pl.tiles_co * pl.tiles_ci * pl.nsplit);
-        const int form = g->R == 1 ? 2 : (g->dil == 4 ? 1 : 0);
+        const int form = pl.form;
         if (in_bf16) {
             if (form == 0) hipLaunchKernelGGL((wgrad3x3_bf16_kernel<true, 9, 1>), grid, dim3(256), 0, st, p);
             else if (form == 1) hipLaunchKernelGGL((wgrad3x3_bf16_kernel<true, 9, 4>), grid, dim3(256), 0, st, p);
@@ -801,7 +813,7 @@ static int conv2d_wgrad_impl(const float* x, const float* dy, int ldy, float* dw
     SSD_CHECK_LAUNCH();
     if (T > 49) return SSD_ERR_BAD_SHAPE;                      // the reduction's LDS tile holds up to 7x7 taps
     const int rblocks = g->Co * ssd_cdiv(g->Ci, 64);
-    if (rblocks < 512 && pl.nsplit >= 32)                       // few blocks, long sums: one block per tap as well
+    if (pl.tap_reduce)
         hipLaunchKernelGGL(wgrad_reduce_tap_kernel, dim3(rblocks * T), dim3(256), 0, st, p.slab, dw_oihw, g->Co, g->Ci, T, pl.nsplit,
                            dbias ? p.bias_slab : nullptr, dbias);
     else
@@ -816,6 +828,16 @@ extern "C" int ssd_conv2d_wgrad_tile(const ssd_conv_geom* g, int* bt, int* nspli
     const WgradPlan pl = plan_wgrad(g);
     *bt = pl.fused ? 3 : pl.bt;
     *nsplit = pl.nsplit;
+    return SSD_OK;
+}
+
+// see include/ssd_gfx950.h
+extern "C" int ssd_conv2d_wgrad_plan(const ssd_conv_geom* g, int bf16, int* plan) {
+    if (!g || !plan) return SSD_ERR_NULL;
+    const WgradPlan pl = plan_wgrad(g, bf16 != 0);
+    plan[0] = pl.fused ? (bf16 ? 2 : 1) : 0;
+    plan[1] = pl.bt; plan[2] = pl.nbuf; plan[3] = pl.fused && !bf16 ? pl.shape : -1; plan[4] = pl.fused && bf16 ? pl.form : -1;
+    plan[5] = pl.nsplit; plan[6] = pl.m_per_split; plan[7] = pl.tap_reduce;
     return SSD_OK;
 }
 
