@@ -478,6 +478,32 @@ int ssd_map_eval(const float* det_boxes, const int32_t* det_classes, const float
                  int n_classes, const double* recall_levels_host, int n_levels, uint8_t* tp, double* table,
                  int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- detection evaluator (Util.DetectionEvaluator; not in the reference): PASCAL VOC 'difficult' objects, up to 16 IoU
+ * thresholds settled in ONE matching pass, 11- / 101-point and all-point AP with integer recall.
+ * ssd_eval_match scores one batch of B images.  Detections are either concatenated (det_start[B+1], det_count NULL) or padded
+ * (det_count[B], det_start NULL: image b owns rows b*K .. b*K + count[b] - 1 of the D = B*K rows; the rest is never read).
+ * Ground truth is concatenated (gt_start[B+1]); gt_difficult (G bytes, 0/1) may be NULL = none difficult.  thresholds is a HOST
+ * array of n_thresholds <= 16 ascending floats in (0, 1), compared as iou > thr.  Per detection, in descending (score, lower row
+ * first) order inside its (image, class): the best-IoU box of ALL boxes of the class (first index on ties; any NaN IoU among
+ * them = false positive) decides every threshold at once -- above = thresholds below that IoU; box difficult: ignored = above;
+ * else tp = above & ~claimed[box], claimed[box] |= above.  Outputs per row: rec_classes (int32: the class, -1 = class outside
+ * [0, n_classes), -2 = padding row), tp / ignored (uint16, bit t = thresholds[t]); n_gt (n_classes int32) is ADDED to: the
+ * non-difficult boxes per class.  Start / count values are clamped to the arrays.
+ * ssd_eval_ap orders D such rows per class (descending score, lower row first), drops the ignored ones per threshold and
+ * writes, for n_levels = L in {10, 100}: out[(t*n_classes + c)*(L+1) + k] = max of cumTP/(cumTP+cumFP) over the positions with
+ * cumTP*L >= k*n_gt (64-bit integers), 0 if none; for n_levels = 0: out[t*n_classes + c] = (sum over the true positives of the
+ * running maximum of precision from the end) / n_gt, 0 where n_gt = 0.  n_det (n_classes int32) = rows per class. */
+size_t ssd_eval_match_workspace(int G);
+int ssd_eval_match(const float* det_boxes, const int32_t* det_classes, const float* det_scores, const int32_t* det_start,
+                   const int32_t* det_count, int K, int D, const float* gt_boxes, const int32_t* gt_classes,
+                   const uint8_t* gt_difficult, const int32_t* gt_start, int G, int B, int n_classes,
+                   const float* thresholds_host, int n_thresholds, int32_t* rec_classes, uint16_t* tp, uint16_t* ignored,
+                   int32_t* n_gt, void* workspace, size_t workspace_bytes, void* stream);
+size_t ssd_eval_ap_workspace(int D);
+int ssd_eval_ap(const int32_t* rec_classes, const float* det_scores, const uint16_t* tp, const uint16_t* ignored, int D,
+                const int32_t* n_gt, int n_classes, int n_thresholds, int n_levels, double* out, int32_t* n_det,
+                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- input pipeline (Dataset.py:10-13,24-39 Resize((300,300)) + ToTensor + Normalize; Util.py:610-749 expand /
  * random_crop / flip as geometry) on 8-bit HWC RGB images packed in one device arena.  The resize reproduces
  * Pillow's Image.resize(BILINEAR) on 8-bit images bit for bit.  Geometry per image, in this order: the source is

@@ -4,7 +4,8 @@ reference's Util.py (names and argument meaning kept; bodies are ours).
 What `Losses.py` / `train_function.py` pull in through `from Util import *` and what
 `train.py:6` / `Dataset.py:4` import by name lives here: prior boxes, box coders, the
 class table, `device`, the (empty) VOC lists, `transform` (as a geometry plan: the
-pixels are made on the GPU) and `get_map`.  VOC XML parsing and drawing are out of
+pixels are made on the GPU) and `get_map`; `DetectionEvaluator` / `evaluate_detections` are build additions
+beside it (VOC difficult objects, IoU sweeps, all-point AP).  VOC XML parsing and drawing are out of
 scope.
 """
 from __future__ import annotations
@@ -168,3 +169,202 @@ def get_map(det_boxes, det_classes, det_scores, gt_boxes, gt_classes, n_classes=
     table, _, _ = ops.map_eval(db, dc, ds, d_start, gb, gc, g_start, levels, int(n_classes))
     t = table.cpu().numpy()
     return {cls: np.float64(np.mean(t[cls])) for cls in range(int(n_classes))}
+
+
+# ---- detection evaluator: VOC 'difficult' objects, IoU-threshold sweep, 11- / 101- / all-point AP (not in the reference) ----------
+COCO_IOU_THRESHOLDS = tuple(0.5 + 0.05 * k for k in range(10))
+_INTERPOLATION_LEVELS = {"11point": 10, "101point": 100, "all": 0}
+
+
+def _check_eval_args(n_classes, iou_thresholds, interpolation):
+    import numbers
+    import numpy as np
+    if isinstance(n_classes, bool) or not isinstance(n_classes, numbers.Integral) or not 1 <= n_classes <= 256:
+        raise ValueError(f"n_classes must be an integer in 1..256, got {n_classes!r}")
+    try:
+        thr = [float(t) for t in iou_thresholds]
+    except TypeError:
+        raise ValueError(f"iou_thresholds must be a sequence of 1..16 floats, got {iou_thresholds!r}") from None
+    if not 1 <= len(thr) <= 16:
+        raise ValueError(f"iou_thresholds must hold 1..16 values, got {len(thr)}")
+    thr32 = np.asarray(thr, np.float32)                                  # converted once; the kernels compare iou > float32(thr)
+    if not all(0.0 < float(t) < 1.0 for t in thr32):
+        raise ValueError(f"iou_thresholds must lie in (0, 1), got {iou_thresholds!r}")
+    if any(not thr32[i] < thr32[i + 1] for i in range(len(thr) - 1)):
+        raise ValueError(f"iou_thresholds must be ascending and distinct, got {iou_thresholds!r}")
+    if interpolation not in _INTERPOLATION_LEVELS:
+        raise ValueError(f"interpolation must be '11point', '101point' or 'all', got {interpolation!r}")
+    return int(n_classes), thr32
+
+
+class DetectionEvaluator:
+    """Average precision under the PASCAL VOC devkit's matching rule, on the GPU (csrc/map_eval.hip E1-E4), with what `get_map`
+    lacks: 'difficult' objects, up to 16 IoU thresholds settled in one matching pass, 11-point, 101-point or all-point
+    (VOC2010+) interpolation, and batch-wise accumulation without host synchronisation.
+
+        ev = DetectionEvaluator(n_classes=20, iou_thresholds=(0.5,), interpolation="11point")
+        ev.add_batch(boxes, classes, scores, count, gt_boxes, gt_classes, gt_difficult)      # per batch: enqueues only
+        res = ev.compute()                                                                   # the only call that synchronises
+
+    Protocol.  Per class and image the detections are visited in descending score order (ties: the one added first).  The best-IoU
+    box among ALL ground-truth boxes of the class in the image, difficult ones included (first on ties; a NaN IoU among them makes
+    the detection a false positive), does not depend on the threshold.  At threshold t: not `iou > t` -> false positive; the box
+    is difficult -> ignored (neither true nor false positive, the box is never claimed); the box is unclaimed at t -> true positive
+    and claimed at t; else false positive.  n_gt counts the non-difficult boxes.  Per class and threshold the detections of all
+    images in descending (score, added first) order with the ignored ones removed give precision = cumTP / (cumTP + cumFP) in
+    float64; recall is never formed in floating point: level k of L is reached iff cumTP * L >= k * n_gt in integers.  "11point" /
+    "101point": AP = mean over k = 0..L of the maximum precision at the positions reaching level k (0 if none).  "all": AP = (sum
+    over the true positives of the running maximum of precision from the end of the list) / n_gt, the area under the monotone
+    precision-recall envelope.  A class without non-difficult ground truth has AP NaN and is left out of the mean.
+    Example: one class, two objects, three detections scored TP, FP, TP -> precisions 1, 1/2, 2/3 -> "all" 0.8333333333333333,
+    "11point" 0.8484848484848484, "101point" 0.8349834983498351; with the middle detection ignored, 1.0.
+
+    With no difficult flags and thresholds (0.5,), bit 0 of `tp` and `n_gt` equal `get_map`'s true-positive flags and counts.  The AP
+    values deliberately do NOT equal `get_map`'s, which keeps the reference's float32-reciprocal recall and scores a class without
+    ground truth 0.
+
+    Detection and ground-truth boxes must be in the SAME coordinate system; nothing is rescaled here.  `Losses.inference_batch_padded`
+    emits pixel xyxy of the sizes it is given, the dataset yields fractions of the image: scale one of them, or decode with sizes (1, 1).
+
+    Out of scope: COCO's own matching rule (best still-unmatched object, crowd regions, area ranges, maxDets) -- a sweep here is "AP
+    averaged over IoU thresholds under the VOC matching rule", not COCO mAP --; precision-recall curve export, per-image reports.
+    GPU only, like `get_map`: there is no CPU fallback."""
+
+    def __init__(self, n_classes=20, iou_thresholds=(0.5,), interpolation="11point"):
+        self.n_classes, self._thr32 = _check_eval_args(n_classes, iou_thresholds, interpolation)
+        if not torch.cuda.is_available():
+            raise RuntimeError("DetectionEvaluator runs on the gfx950 HIP kernels only (no CPU fallback)")
+        self.iou_thresholds = tuple(float(t) for t in iou_thresholds)
+        self.interpolation = interpolation
+        self.reset()
+
+    def reset(self):
+        """Forget every batch added so far."""
+        self._rec, self._score, self._tp, self._ign = [], [], [], []
+        self._n_gt = None
+        self._padded = False
+        self._dev = None
+
+    @staticmethod
+    def _starts(counts, dev):
+        start = [0]
+        for n in counts:
+            start.append(start[-1] + int(n))
+        return torch.tensor(start, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+
+    @staticmethod
+    def _cat(items, dtype, width, dev):
+        parts = [torch.as_tensor(t).reshape((-1, width) if width else (-1,)).to(device=dev, dtype=dtype) for t in items]
+        if not parts:
+            return torch.zeros((0, width) if width else (0,), device=dev, dtype=dtype), []
+        return torch.cat(parts).contiguous(), [int(p.shape[0]) for p in parts]
+
+    def add_batch(self, boxes, classes, scores, count, gt_boxes, gt_classes, gt_difficult=None, gt_offsets=None):
+        """Score one batch of images against its ground truth and keep the per-detection records.
+
+        Detections: the padded device tensors of `Losses.inference_batch_padded` -- boxes (B,K,4), classes (B,K) integer, scores
+        (B,K), count (B,) int32; rows >= count[b] are not detections and are never read -- or, with count=None, per-image lists of
+        (n,4) boxes, (n,) classes, (n,) scores as `get_map` takes them.  Ground truth: per-image lists of (n,4) boxes, (n,) classes
+        and optionally (n,) 0/1 difficult flags, or packed device tensors (G,4), (G,), (G,) with gt_offsets = (B+1,) int32 device
+        tensor of each image's first row.  Same coordinate system on both sides (see the class docstring).
+        With padded device detections and packed device ground truth nothing here waits for the device."""
+        from . import ops
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if count is not None:
+            if not (torch.is_tensor(boxes) and boxes.is_cuda and boxes.dim() == 3 and boxes.shape[-1] == 4):
+                raise ValueError("add_batch: with `count`, boxes must be a (B,K,4) device tensor")
+            dev = boxes.device
+            n_img = int(boxes.shape[0])
+            db = boxes.detach().to(torch.float32).contiguous()
+            dc = classes.detach().to(device=dev, dtype=torch.int32).contiguous()
+            ds = scores.detach().to(device=dev, dtype=torch.float32).contiguous()
+            d_count = count.detach().to(device=dev, dtype=torch.int32).contiguous()
+            d_start = None
+            self._padded = True
+        else:
+            if not (len(boxes) == len(classes) == len(scores)):
+                raise ValueError("add_batch expects one entry per image in boxes, classes and scores")
+            n_img = len(boxes)
+            dev = next((t.device for t in list(boxes) + (list(gt_boxes) if gt_offsets is None else [gt_boxes])
+                        if torch.is_tensor(t) and t.is_cuda), dev)
+            db, per = self._cat(boxes, torch.float32, 4, dev)
+            dc, per_c = self._cat(classes, torch.int32, 0, dev)
+            ds, per_s = self._cat(scores, torch.float32, 0, dev)
+            if per != per_c or per != per_s:
+                raise ValueError("add_batch: boxes, classes and scores disagree on the detections per image")
+            d_start, d_count = self._starts(per, dev), None
+        if n_img == 0:
+            raise ValueError("add_batch expects at least one image")
+        if self._dev is not None and dev != self._dev:
+            raise ValueError(f"add_batch: this evaluator accumulates on {self._dev}, the batch is on {dev}")
+        if gt_offsets is not None:
+            if not (torch.is_tensor(gt_boxes) and gt_boxes.is_cuda and torch.is_tensor(gt_offsets) and gt_offsets.is_cuda):
+                raise ValueError("add_batch: packed ground truth (gt_offsets given) must be device tensors")
+            gb = gt_boxes.detach().reshape(-1, 4).to(torch.float32).contiguous()
+            gc = gt_classes.detach().reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+            gd = None if gt_difficult is None else gt_difficult.detach().reshape(-1).to(device=dev, dtype=torch.uint8).contiguous()
+            g_start = gt_offsets.detach().to(torch.int32).contiguous()
+            if g_start.numel() != n_img + 1:
+                raise ValueError("add_batch: gt_offsets must have one entry per image plus one")
+        else:
+            if len(gt_boxes) != n_img or len(gt_classes) != n_img or (gt_difficult is not None and len(gt_difficult) != n_img):
+                raise ValueError("add_batch expects one ground-truth entry per image")
+            gb, per = self._cat(gt_boxes, torch.float32, 4, dev)
+            gc, per_c = self._cat(gt_classes, torch.int32, 0, dev)
+            gd = None
+            if gt_difficult is not None:
+                gd, per_d = self._cat(gt_difficult, torch.uint8, 0, dev)
+                if per_d != per:
+                    raise ValueError("add_batch: gt_boxes and gt_difficult disagree on the objects per image")
+            if per != per_c:
+                raise ValueError("add_batch: gt_boxes and gt_classes disagree on the objects per image")
+            g_start = self._starts(per, dev)
+        with torch.cuda.device(dev):
+            if self._n_gt is None:
+                self._n_gt = torch.zeros(self.n_classes, device=dev, dtype=torch.int32)
+                self._dev = dev
+            rec, tp, ign = ops.eval_match(db, dc, ds, d_start, d_count, gb, gc, gd, g_start, self._n_gt, self._thr32, self.n_classes)
+        self._rec.append(rec); self._tp.append(tp); self._ign.append(ign)
+        self._score.append(ds.reshape(-1).clone() if count is not None else ds)      # the caller may reuse its padded buffers
+
+    def compute(self):
+        """-> dict: `ap` float64 (T, n_classes), NaN where a class has no non-difficult ground truth; `mean_ap` float64 (T,), nanmean
+        over the classes; `mean_ap_over_thresholds`; `n_gt`, `n_det` int64 (n_classes,); `tp`, `ignored` device uint16 (D,), bit t =
+        true positive / ignored at iou_thresholds[t], in the order the detections were added; `iou_thresholds`; `interpolation`.
+        May be called repeatedly; more batches may be added afterwards."""
+        import numpy as np
+        from . import ops
+        if self._n_gt is None:
+            raise RuntimeError("DetectionEvaluator.compute(): no batch has been added")
+        T, C, L = len(self._thr32), self.n_classes, _INTERPOLATION_LEVELS[self.interpolation]
+        with torch.cuda.device(self._dev):
+            rec, score = torch.cat(self._rec), torch.cat(self._score)
+            tp, ign = torch.cat(self._tp), torch.cat(self._ign)
+            if self._padded:
+                keep = rec != -2                                              # rows past count[b] of the padded batches
+                rec, score, tp, ign = rec[keep].contiguous(), score[keep].contiguous(), tp[keep].contiguous(), ign[keep].contiguous()
+            out, n_det = ops.eval_ap(rec, score, tp, ign, self._n_gt, T, L, C)
+            out = out.cpu().numpy()
+            n_gt = self._n_gt.cpu().numpy().astype(np.int64)
+            n_det = n_det.cpu().numpy().astype(np.int64)
+        ap = np.full((T, C), np.nan, np.float64)
+        for t in range(T):
+            for c in range(C):
+                if n_gt[c] > 0:
+                    ap[t, c] = np.mean(out[t, c]) if L else out[t, c]
+        mean_ap = np.asarray([np.nanmean(ap[t]) if (n_gt > 0).any() else np.nan for t in range(T)], np.float64)
+        return {"ap": ap, "mean_ap": mean_ap, "mean_ap_over_thresholds": np.float64(np.mean(mean_ap)), "n_gt": n_gt, "n_det": n_det,
+                "tp": tp.view(torch.uint16), "ignored": ign.view(torch.uint16), "iou_thresholds": self.iou_thresholds,
+                "interpolation": self.interpolation}
+
+
+def evaluate_detections(det_boxes, det_classes, det_scores, gt_boxes, gt_classes, gt_difficulties=None, n_classes=20,
+                        iou_thresholds=(0.5,), interpolation="11point"):
+    """One-shot `DetectionEvaluator` over `get_map`'s per-image lists (plus optional per-image 0/1 difficult flags): the dict of
+    `DetectionEvaluator.compute()`.  See the class for the protocol and for how its AP differs from `get_map`'s on purpose."""
+    _check_eval_args(n_classes, iou_thresholds, interpolation)
+    if not torch.cuda.is_available():
+        raise RuntimeError("evaluate_detections() runs on the gfx950 HIP kernels only (no CPU fallback)")
+    ev = DetectionEvaluator(n_classes, iou_thresholds, interpolation)
+    ev.add_batch(det_boxes, det_classes, det_scores, None, gt_boxes, gt_classes, gt_difficulties)
+    return ev.compute()

@@ -282,3 +282,488 @@ extern "C" int ssd_map_eval(const float* det_boxes, const int32_t* det_classes, 
     SSD_CHECK_LAUNCH();
     return SSD_OK;
 }
+
+// ---- Detection evaluator (Util.DetectionEvaluator): VOC 'difficult' objects, an IoU-threshold sweep in one matching pass, 11- /
+// 101-point and all-point AP with integer recall ---------------------------------------------------------------------------
+//   E1 prep      per batch: claimed mask per ground-truth box := 0, tp / ignored := 0, the record class of every detection row
+//                (-2 = padding row past count[b], -1 = class outside [0, n_classes)), non-difficult objects per class += (atomics)
+//   E2 match     one wave per (image, class), selection and arg-max as M2; the best box and its IoU do not depend on the
+//                threshold, so all thresholds are settled at once: above = bits of the thresholds below the IoU;
+//                difficult box -> ignored = above; else tp = above & ~claimed[g], claimed[g] |= above.  The claimed masks of
+//                an (image, class) pair are touched by lane 0 of its one wave only.
+//   E3 order     M3-M5's per-class descending order (count, bucket, rank) scattering the two 16-bit masks; the bucket pass takes
+//                eight rows per thread and the rank pass streams the class's keys through LDS
+//   E4 ap        block per (class, threshold): scan of the TP / kept bits in sorted order with the ignored detections removed;
+//                precision = cumTP / kept position (one division of two integers); level k of L reached iff
+//                cumTP * L >= k * n_gt in 64-bit integers; or the backward envelope pass for all-point AP.
+namespace {
+
+constexpr int MAX_THRESHOLDS = 16;
+constexpr int MAX_EVAL_LEVELS = 100;
+
+struct ThresholdArgs {
+    float thr[MAX_THRESHOLDS];
+};
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__global__ void eval_prep_kernel(const int32_t* __restrict__ det_classes, const int32_t* __restrict__ det_count, int K, int D,
+                                 const int32_t* __restrict__ gt_classes, const uint8_t* __restrict__ gt_difficult, int G, int n_classes,
+                                 int32_t* __restrict__ rec_classes, uint16_t* __restrict__ tp, uint16_t* __restrict__ ignored,
+                                 uint16_t* __restrict__ claimed, int32_t* __restrict__ n_gt) {
+    const int n = D > G ? D : G;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        if (i < G) {
+            claimed[i] = 0;
+            const int c = gt_classes[i];
+            if (c >= 0 && c < n_classes && !(gt_difficult && gt_difficult[i])) atomicAdd(&n_gt[c], 1);
+        }
+        if (i < D) {
+            tp[i] = 0;
+            ignored[i] = 0;
+            const bool row = !det_count || (i % K) < clampi(det_count[i / K], 0, K);
+            const int c = row ? det_classes[i] : -1;                                // padding rows are never read
+            rec_classes[i] = !row ? -2 : ((c >= 0 && c < n_classes) ? c : -1);
+        }
+    }
+}
+
+constexpr int MATCH_SLOTS = 4;
+
+// Rows of image b: [det_start[b], det_start[b+1]) of the concatenated layout, or [b*K, b*K + count[b]) of the padded one.
+__global__ __launch_bounds__(256) void eval_match_kernel(const float* __restrict__ det_boxes, const int32_t* __restrict__ det_classes,
+                                                         const float* __restrict__ det_scores, const int32_t* __restrict__ det_start,
+                                                         const int32_t* __restrict__ det_count, int K, int D,
+                                                         const float* __restrict__ gt_boxes, const int32_t* __restrict__ gt_classes,
+                                                         const uint8_t* __restrict__ gt_difficult, const int32_t* __restrict__ gt_start,
+                                                         int G, int B, int n_classes, const ThresholdArgs th, int n_thr,
+                                                         uint16_t* __restrict__ claimed, uint16_t* __restrict__ tp,
+                                                         uint16_t* __restrict__ ignored) {
+    const int lane = threadIdx.x & 63;
+    const long pair = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= (long)B * n_classes) return;                 // whole wave leaves together
+    const int b = (int)(pair / n_classes), c = (int)(pair % n_classes);
+    int ds, de;
+    if (det_count) {
+        ds = b * K;
+        de = ds + clampi(det_count[b], 0, K);
+    } else {
+        ds = clampi(det_start[b], 0, D);
+        de = clampi(det_start[b + 1], ds, D);
+    }
+    const int gs = clampi(gt_start[b], 0, G), ge = clampi(gt_start[b + 1], gs, G);
+    uint64_t prev = ~0ull;
+    if (de - ds <= 64 * MATCH_SLOTS && ge - gs <= 64) {
+        // The usual image (at most 256 rows, at most 64 boxes) lives in registers: keys and boxes of the class's detections in
+        // MATCH_SLOTS slots per lane, one ground-truth box and its claimed mask per lane.  The selection loop below then touches
+        // memory only to store its flags; the dependent loads of the general loop further down made a batch of 32 images cost
+        // as much as its longest (image, class) list times seven round trips.
+        uint64_t key[MATCH_SLOTS];
+        f32x4 dbox[MATCH_SLOTS];
+#pragma unroll
+        for (int s = 0; s < MATCH_SLOTS; ++s) {
+            const int i = ds + s * 64 + lane;
+            key[s] = 0;
+            dbox[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (i < de && det_classes[i] == c) {
+                key[s] = det_key(det_scores[i], i);
+                dbox[s] = *reinterpret_cast<const f32x4*>(det_boxes + (size_t)i * 4);
+            }
+        }
+        const int g_mine = gs + lane;
+        const bool has = g_mine < ge && gt_classes[g_mine] == c;
+        const f32x4 gbox = has ? *reinterpret_cast<const f32x4*>(gt_boxes + (size_t)g_mine * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const bool difficult = has && gt_difficult && gt_difficult[g_mine];
+        uint32_t claimed_mine = 0;
+        for (;;) {
+            uint64_t best = 0;
+#pragma unroll
+            for (int s = 0; s < MATCH_SLOTS; ++s)
+                if (key[s] < prev && key[s] > best) best = key[s];
+            best = wave_max_u64(best);
+            if (best == 0) break;                              // uniform: no detection of this class left
+            prev = best;
+            const int d = (int)(0xFFFFFFFFu - (uint32_t)best);
+            const int slot = (d - ds) >> 6, src = (d - ds) & 63;   // uniform
+            f32x4 sel = dbox[0];
+#pragma unroll
+            for (int s = 1; s < MATCH_SLOTS; ++s)
+                if (slot == s) sel = dbox[s];
+            f32x4 box;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) box[j] = __shfl(sel[j], src, 64);
+            const float v = has ? iou_boxes(box, gbox) : -1.f;
+            const bool nan = has && v != v;
+            float v_best = -1.f;
+            int g_best = 0x7FFFFFFF;
+            if (has && v > -1.f) { v_best = v; g_best = g_mine; }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(v_best, o, 64);
+                const int og = __shfl_xor(g_best, o, 64);
+                if (ov > v_best || (ov == v_best && og < g_best)) { v_best = ov; g_best = og; }
+            }
+            const bool any_nan = __ballot(nan) != 0ull;
+            if (!any_nan && g_best == g_mine) {                // the lane that owns the best box settles the detection
+                uint32_t above = 0;
+                for (int t = 0; t < n_thr; ++t) above |= (v_best > th.thr[t]) ? (1u << t) : 0u;
+                if (above) {
+                    if (difficult) {
+                        ignored[d] = (uint16_t)above;
+                    } else {
+                        tp[d] = (uint16_t)(above & ~claimed_mine);
+                        claimed_mine |= above;
+                    }
+                }
+            }
+        }
+        return;
+    }
+    for (;;) {
+        uint64_t best = 0;
+        for (int i = ds + lane; i < de; i += 64) {
+            if (det_classes[i] == c) {
+                const uint64_t k = det_key(det_scores[i], i);
+                if (k < prev && k > best) best = k;
+            }
+        }
+        best = wave_max_u64(best);
+        if (best == 0) break;                                  // uniform: no detection of this class left
+        prev = best;
+        const int d = (int)(0xFFFFFFFFu - (uint32_t)best);
+        const f32x4 box = *reinterpret_cast<const f32x4*>(det_boxes + (size_t)d * 4);
+        float v_best = -1.f;
+        int g_best = 0x7FFFFFFF;
+        bool nan = false;
+        for (int g = gs + lane; g < ge; g += 64) {
+            if (gt_classes[g] == c) {
+                const float v = iou_boxes(box, *reinterpret_cast<const f32x4*>(gt_boxes + (size_t)g * 4));
+                nan |= (v != v);
+                if (v > v_best) { v_best = v; g_best = g; }     // ascending g per lane: strict > keeps the first
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(v_best, o, 64);
+            const int og = __shfl_xor(g_best, o, 64);
+            if (ov > v_best || (ov == v_best && og < g_best)) { v_best = ov; g_best = og; }
+        }
+        const bool any_nan = __ballot(nan) != 0ull;           // a NaN among the candidates: false positive everywhere
+        if (lane == 0 && !any_nan && g_best != 0x7FFFFFFF) {
+            uint32_t above = 0;
+            for (int t = 0; t < n_thr; ++t) above |= (v_best > th.thr[t]) ? (1u << t) : 0u;
+            if (above) {
+                if (gt_difficult && gt_difficult[g_best]) {
+                    ignored[d] = (uint16_t)above;              // neither TP nor FP; the box is never claimed
+                } else {
+                    const uint32_t cl = claimed[g_best];
+                    tp[d] = (uint16_t)(above & ~cl);
+                    claimed[g_best] = (uint16_t)(cl | above);
+                }
+            }
+        }
+    }
+}
+
+// M3 for the detections alone, through a per-block LDS histogram: a million rows on twenty global counters serialise otherwise.
+__global__ __launch_bounds__(256) void eval_count_kernel(const int32_t* __restrict__ det_classes, int D, int n_classes,
+                                                         int32_t* __restrict__ counts) {
+    __shared__ int hist[256];
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D; i += gridDim.x * blockDim.x) {
+        const int c = det_classes[i];
+        if (c >= 0 && c < n_classes) atomicAdd(&hist[c], 1);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < n_classes && hist[threadIdx.x] != 0) atomicAdd(&counts[threadIdx.x], hist[threadIdx.x]);
+}
+
+// M4 with eight consecutive rows per thread: an eighth of the barriers of map_bucket_kernel on the same stable compaction.
+constexpr int BUCKET_ROWS = 8;
+
+__global__ __launch_bounds__(256) void eval_bucket_kernel(const int32_t* __restrict__ det_classes, const float* __restrict__ det_scores,
+                                                          int D, const int32_t* __restrict__ counts, int32_t* __restrict__ list,
+                                                          uint64_t* __restrict__ keys) {
+    __shared__ int wave_cnt[4];
+    const int c = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int off = 0;
+    for (int k = 0; k < c; ++k) off += counts[k];
+    int base = 0;
+    for (int i0 = 0; i0 < D; i0 += 256 * BUCKET_ROWS) {
+        const int first = i0 + threadIdx.x * BUCKET_ROWS;
+        uint32_t mask = 0;
+#pragma unroll
+        for (int j = 0; j < BUCKET_ROWS; ++j)
+            if (first + j < D && det_classes[first + j] == c) mask |= 1u << j;
+        const int cnt = __popc(mask);
+        int incl = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int w = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += w;
+        }
+        if (lane == 63) wave_cnt[wv] = incl;
+        __syncthreads();
+        int before = 0;
+        for (int k = 0; k < wv; ++k) before += wave_cnt[k];
+        const int total = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        int pos = off + base + before + incl - cnt;
+#pragma unroll
+        for (int j = 0; j < BUCKET_ROWS; ++j) {
+            if (mask & (1u << j)) {
+                list[pos] = first + j;
+                keys[pos] = det_key(det_scores[first + j], first + j);
+                ++pos;
+            }
+        }
+        base += total;
+        __syncthreads();
+    }
+}
+
+// M5 through LDS: a block owns 256 consecutive positions of the bucketed list and, for each class that reaches into them, streams
+// that class's keys through a tile; every thread counts the keys above its own (keys are unique: the count is its rank).  The same
+// number of comparisons as map_rank_kernel, but the keys come from LDS broadcasts instead of one L1 access per comparison.
+constexpr int RANK_TILE = 2048;
+
+__global__ __launch_bounds__(256) void eval_rank_kernel(const int32_t* __restrict__ counts, int n_classes, const int32_t* __restrict__ list,
+                                                        const uint64_t* __restrict__ keys, const uint16_t* __restrict__ tp,
+                                                        const uint16_t* __restrict__ ignored, uint16_t* __restrict__ sorted_tp,
+                                                        uint16_t* __restrict__ sorted_ign) {
+    __shared__ uint64_t tile[RANK_TILE];
+    const int p0 = blockIdx.x * 256, p = p0 + threadIdx.x;
+    int hi = 0;
+    for (int c = 0; c < n_classes; ++c) {                                           // every branch on lo / hi is block-uniform
+        const int lo = hi;
+        hi = lo + counts[c];
+        if (hi <= p0 || hi == lo) continue;
+        if (lo >= p0 + 256) break;
+        const bool mine = p >= lo && p < hi;
+        const uint64_t key = mine ? keys[p] : ~0ull;
+        int rank = 0;
+        for (int t0 = lo; t0 < hi; t0 += RANK_TILE) {
+            const int m = hi - t0 < RANK_TILE ? hi - t0 : RANK_TILE;
+            const int m4 = (m + 3) & ~3;
+            __syncthreads();
+            for (int k = threadIdx.x; k < m4; k += 256) tile[k] = k < m ? keys[t0 + k] : 0ull;
+            __syncthreads();
+            for (int k = 0; k < m4; k += 4) {
+                rank += tile[k] > key ? 1 : 0;
+                rank += tile[k + 1] > key ? 1 : 0;
+                rank += tile[k + 2] > key ? 1 : 0;
+                rank += tile[k + 3] > key ? 1 : 0;
+            }
+        }
+        if (mine) {
+            const int i = list[p];
+            sorted_tp[lo + rank] = tp[i];
+            sorted_ign[lo + rank] = ignored[i];
+        }
+    }
+}
+
+// L > 0: out[(t * n_classes + c) * (L + 1) + k] = max precision over the positions that reach level k (0 if none).
+// L == 0: out[t * n_classes + c] = (sum over the true positives of the precision envelope) / n_gt  (0 when n_gt == 0: the host
+// writes NaN there).  Only true-positive positions can hold a maximum: a false positive has the cumTP (so the levels) of the
+// true positive before it and a lower precision, or cumTP = 0 and precision 0, the table's default.
+__global__ __launch_bounds__(256) void eval_ap_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ n_gt_all,
+                                                      int n_classes, const uint16_t* __restrict__ sorted_tp,
+                                                      const uint16_t* __restrict__ sorted_ign, int L, double* __restrict__ out) {
+    __shared__ int wave_cnt[2][4];
+    __shared__ unsigned long long lvl[MAX_EVAL_LEVELS + 1];
+    __shared__ double wave_max[4];
+    __shared__ double wave_sum[4];
+    const int c = blockIdx.x, t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t bit = 1u << t;
+    int off = 0;
+    for (int k = 0; k < c; ++k) off += counts[k];
+    const int n = counts[c], n_gt = n_gt_all[c];
+    for (int k = threadIdx.x; k <= MAX_EVAL_LEVELS; k += 256) lvl[k] = 0ull;       // bits of +0.0
+    __syncthreads();
+    // forward: running true positives / kept positions; the level table on the way
+    int run_tp = 0, run_kept = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + threadIdx.x;
+        const bool in = i < n;
+        const bool is_tp = in && (sorted_tp[off + i] & bit) != 0;
+        const bool kept = in && (sorted_ign[off + i] & bit) == 0;
+        const uint64_t bal_tp = __ballot(is_tp), bal_k = __ballot(kept);
+        if (lane == 0) { wave_cnt[0][wv] = __popcll(bal_tp); wave_cnt[1][wv] = __popcll(bal_k); }
+        __syncthreads();
+        int before_tp = 0, before_k = 0;
+        for (int k = 0; k < wv; ++k) { before_tp += wave_cnt[0][k]; before_k += wave_cnt[1][k]; }
+        const int total_tp = wave_cnt[0][0] + wave_cnt[0][1] + wave_cnt[0][2] + wave_cnt[0][3];
+        const int total_k = wave_cnt[1][0] + wave_cnt[1][1] + wave_cnt[1][2] + wave_cnt[1][3];
+        if (L > 0 && is_tp && n_gt > 0) {
+            const uint64_t upto = (lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1ull);
+            const int cum_tp = run_tp + before_tp + __popcll(bal_tp & upto);
+            const int pos = run_kept + before_k + __popcll(bal_k & upto);         // cumTP + cumFP, exactly
+            const double prec = (double)cum_tp / (double)pos;
+            long long k = (long long)cum_tp * L / n_gt;                             // highest level with cumTP * L >= k * n_gt
+            if (k > L) k = L;
+            atomicMax(&lvl[k], (unsigned long long)__double_as_longlong(prec));     // non-negative doubles order as integers
+        }
+        run_tp += total_tp;
+        run_kept += total_k;
+        __syncthreads();
+    }
+    if (L > 0) {
+        __syncthreads();
+        if (threadIdx.x <= L) {
+            unsigned long long v = 0ull;
+            for (int k = threadIdx.x; k <= L; ++k) v = lvl[k] > v ? lvl[k] : v;     // reaching level k reaches every lower one
+            out[((size_t)t * n_classes + c) * (L + 1) + threadIdx.x] = __longlong_as_double((long long)v);
+        }
+        return;
+    }
+    // backward: envelope = running maximum of precision from the end; sum it over the true positives
+    double carry = 0.0, sum = 0.0;
+    int after_tp = 0, after_kept = 0;                                              // in the chunks behind this one
+    for (int i0 = ((n - 1) / 256) * 256; n > 0 && i0 >= 0; i0 -= 256) {
+        const int i = i0 + threadIdx.x;
+        const bool in = i < n;
+        const bool is_tp = in && (sorted_tp[off + i] & bit) != 0;
+        const bool kept = in && (sorted_ign[off + i] & bit) == 0;
+        const uint64_t bal_tp = __ballot(is_tp), bal_k = __ballot(kept);
+        if (lane == 0) { wave_cnt[0][wv] = __popcll(bal_tp); wave_cnt[1][wv] = __popcll(bal_k); }
+        __syncthreads();
+        int behind_tp = 0, behind_k = 0;
+        for (int k = wv + 1; k < 4; ++k) { behind_tp += wave_cnt[0][k]; behind_k += wave_cnt[1][k]; }
+        const int total_tp = wave_cnt[0][0] + wave_cnt[0][1] + wave_cnt[0][2] + wave_cnt[0][3];
+        const int total_k = wave_cnt[1][0] + wave_cnt[1][1] + wave_cnt[1][2] + wave_cnt[1][3];
+        const uint64_t above = (lane == 63) ? 0ull : (~0ull << (lane + 1));       // lanes after this one
+        double v = 0.0;
+        if (is_tp) {
+            const int cum_tp = run_tp - (after_tp + behind_tp + __popcll(bal_tp & above));
+            const int pos = run_kept - (after_kept + behind_k + __popcll(bal_k & above));
+            v = (double)cum_tp / (double)pos;
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {                                          // inclusive max-scan towards lane 0
+            const double w = __shfl_down(v, o, 64);
+            if (lane + o < 64) v = w > v ? w : v;
+        }
+        if (lane == 0) wave_max[wv] = v;
+        __syncthreads();
+        double env = v > carry ? v : carry;
+        double chunk = carry;
+        for (int k = 0; k < 4; ++k) {
+            if (k > wv) env = wave_max[k] > env ? wave_max[k] : env;
+            chunk = wave_max[k] > chunk ? wave_max[k] : chunk;
+        }
+        if (is_tp) sum += env;
+        carry = chunk;
+        after_tp += total_tp;
+        after_kept += total_k;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == 0) wave_sum[wv] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double s = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+        out[(size_t)t * n_classes + c] = n_gt > 0 ? s / (double)n_gt : 0.0;
+    }
+}
+
+struct EvalApWs {
+    uint64_t* keys;
+    int32_t* list;
+    uint16_t* sorted_tp;
+    uint16_t* sorted_ign;
+    size_t bytes;
+};
+EvalApWs carve_eval(void* base, int D) {
+    EvalApWs w;
+    size_t o = 0;
+    char* b = static_cast<char*>(base);
+    const size_t n = (size_t)(D > 0 ? D : 1);
+    w.keys = reinterpret_cast<uint64_t*>(b + o); o += align256(n * 8);
+    w.list = reinterpret_cast<int32_t*>(b + o); o += align256(n * 4);
+    w.sorted_tp = reinterpret_cast<uint16_t*>(b + o); o += align256(n * 2);
+    w.sorted_ign = reinterpret_cast<uint16_t*>(b + o); o += align256(n * 2);
+    w.bytes = o;
+    return w;
+}
+
+}  // namespace
+
+extern "C" size_t ssd_eval_match_workspace(int G) {
+    if (G < 0) return 0;
+    return align256((size_t)(G > 0 ? G : 1) * 2);
+}
+
+extern "C" int ssd_eval_match(const float* det_boxes, const int32_t* det_classes, const float* det_scores, const int32_t* det_start,
+                              const int32_t* det_count, int K, int D, const float* gt_boxes, const int32_t* gt_classes,
+                              const uint8_t* gt_difficult, const int32_t* gt_start, int G, int B, int n_classes,
+                              const float* thresholds_host, int n_thresholds, int32_t* rec_classes, uint16_t* tp, uint16_t* ignored,
+                              int32_t* n_gt, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!gt_start || !thresholds_host || !n_gt || (!det_start == !det_count)) return SSD_ERR_NULL;
+    if ((D > 0 && (!det_boxes || !det_classes || !det_scores || !rec_classes || !tp || !ignored)) || (G > 0 && (!gt_boxes || !gt_classes)))
+        return SSD_ERR_NULL;
+    if (D < 0 || D > (1 << 30) || G < 0 || G > (1 << 30) || B <= 0 || n_classes <= 0 || n_classes > 256 || n_thresholds <= 0 ||
+        n_thresholds > MAX_THRESHOLDS)
+        return SSD_ERR_BAD_SHAPE;
+    if (det_count && (K <= 0 || (long)B * K != (long)D)) return SSD_ERR_BAD_SHAPE;
+    if ((long)B * n_classes >= (1L << 31)) return SSD_ERR_BAD_SHAPE;
+    for (int t = 0; t < n_thresholds; ++t) {
+        const float v = thresholds_host[t];
+        if (!(v > 0.f && v < 1.f) || (t > 0 && !(v > thresholds_host[t - 1]))) return SSD_ERR_BAD_SHAPE;
+    }
+    if (!workspace || workspace_bytes < ssd_eval_match_workspace(G)) return SSD_ERR_WORKSPACE;
+    if ((D > 0 && !ssd_aligned16(det_boxes)) || (G > 0 && !ssd_aligned16(gt_boxes))) return SSD_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    uint16_t* claimed = static_cast<uint16_t*>(workspace);
+    ThresholdArgs th{};
+    for (int t = 0; t < n_thresholds; ++t) th.thr[t] = thresholds_host[t];
+    if (D + G > 0) {
+        const int n = D > G ? D : G;
+        const int blocks = ssd_cdiv(n, 256) > 1024 ? 1024 : ssd_cdiv(n, 256);
+        hipLaunchKernelGGL(eval_prep_kernel, dim3(blocks), dim3(256), 0, st, det_classes, det_count, K > 0 ? K : 1, D, gt_classes,
+                           gt_difficult, G, n_classes, rec_classes, tp, ignored, claimed, n_gt);
+        SSD_CHECK_LAUNCH();
+    }
+    if (D > 0) {
+        hipLaunchKernelGGL(eval_match_kernel, dim3((unsigned)(((long)B * n_classes + 3) / 4)), dim3(256), 0, st, det_boxes, det_classes,
+                           det_scores, det_start, det_count, K, D, gt_boxes, gt_classes, gt_difficult, gt_start, G, B, n_classes, th,
+                           n_thresholds, claimed, tp, ignored);
+        SSD_CHECK_LAUNCH();
+    }
+    return SSD_OK;
+}
+
+extern "C" size_t ssd_eval_ap_workspace(int D) {
+    if (D < 0) return 0;
+    return carve_eval(nullptr, D).bytes;
+}
+
+extern "C" int ssd_eval_ap(const int32_t* rec_classes, const float* det_scores, const uint16_t* tp, const uint16_t* ignored, int D,
+                           const int32_t* n_gt, int n_classes, int n_thresholds, int n_levels, double* out, int32_t* n_det,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (!n_gt || !out || !n_det) return SSD_ERR_NULL;
+    if (D > 0 && (!rec_classes || !det_scores || !tp || !ignored)) return SSD_ERR_NULL;
+    if (D < 0 || D > (1 << 30) || n_classes <= 0 || n_classes > 256 || n_thresholds <= 0 || n_thresholds > MAX_THRESHOLDS) return SSD_ERR_BAD_SHAPE;
+    if (n_levels != 0 && n_levels != 10 && n_levels != 100) return SSD_ERR_BAD_SHAPE;
+    if (!workspace || workspace_bytes < ssd_eval_ap_workspace(D)) return SSD_ERR_WORKSPACE;
+    if (!ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const EvalApWs w = carve_eval(workspace, D);
+    hipLaunchKernelGGL(map_init_kernel, dim3(1), dim3(256), 0, st, (uint8_t*)nullptr, 0, n_det, n_classes);
+    SSD_CHECK_LAUNCH();
+    if (D > 0) {
+        int blocks = ssd_cdiv(D, 256) > 1024 ? 1024 : ssd_cdiv(D, 256);
+        hipLaunchKernelGGL(eval_count_kernel, dim3(blocks), dim3(256), 0, st, rec_classes, D, n_classes, n_det);
+        SSD_CHECK_LAUNCH();
+        hipLaunchKernelGGL(eval_bucket_kernel, dim3(n_classes), dim3(256), 0, st, rec_classes, det_scores, D, n_det, w.list, w.keys);
+        SSD_CHECK_LAUNCH();
+        hipLaunchKernelGGL(eval_rank_kernel, dim3(ssd_cdiv(D, 256)), dim3(256), 0, st, n_det, n_classes, w.list, w.keys, tp, ignored,
+                           w.sorted_tp, w.sorted_ign);
+        SSD_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(eval_ap_kernel, dim3(n_classes, n_thresholds), dim3(256), 0, st, n_det, n_gt, n_classes, w.sorted_tp, w.sorted_ign,
+                       n_levels, out);
+    SSD_CHECK_LAUNCH();
+    return SSD_OK;
+}

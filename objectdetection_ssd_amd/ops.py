@@ -930,6 +930,83 @@ def map_eval(det_boxes, det_classes, det_scores, det_start, gt_boxes, gt_classes
     return table, tp[:D], counts
 
 
+# launches of the evaluator's entry points since import: the matching pass runs once per batch whatever the number of thresholds
+launch_counts = {"eval_match": 0, "eval_ap": 0}
+
+
+def eval_match(det_boxes, det_classes, det_scores, det_start, det_count, gt_boxes, gt_classes, gt_difficult, gt_start, n_gt,
+               thresholds, n_classes):
+    """One batch of the detection evaluator (include/ssd_gfx950.h ssd_eval_match).  Detections: concatenated (D,4)/(D,)/(D,) with
+    det_start (B+1,) int32 and det_count None, or padded (B,K,4)/(B,K)/(B,K) with det_count (B,) int32 and det_start None; classes
+    int32.  Ground truth: (G,4), (G,) int32, optional (G,) uint8 difficult flags, gt_start (B+1,) int32.  n_gt (n_classes,) int32 is
+    added to.  thresholds: host sequence of floats.  -> (rec_classes int32, tp int16, ignored int16), one entry per detection row
+    (the 16-bit masks are bit patterns: view them as uint16).  Enqueues only; no host synchronisation."""
+    import numpy as np
+    _req(det_boxes, "det_boxes"); _req(det_scores, "det_scores"); _req(gt_boxes, "gt_boxes")
+    _req(det_classes, "det_classes", torch.int32); _req(gt_classes, "gt_classes", torch.int32)
+    _req(gt_start, "gt_start", torch.int32); _req(n_gt, "n_gt", torch.int32)
+    if (det_start is None) == (det_count is None):
+        raise ValueError("eval_match: give det_start (concatenated rows) or det_count (padded rows), not both")
+    if det_count is not None:
+        _req(det_count, "det_count", torch.int32)
+        if det_boxes.dim() != 3 or det_boxes.shape[2] != 4 or det_boxes.shape[1] < 1:
+            raise ValueError("eval_match: padded detections must be (B,K,4) with K >= 1")
+        B, K = int(det_boxes.shape[0]), int(det_boxes.shape[1])
+        D = B * K
+        if tuple(det_classes.shape) != (B, K) or tuple(det_scores.shape) != (B, K) or det_count.numel() != B:
+            raise ValueError("eval_match: inconsistent padded shapes")
+    else:
+        _req(det_start, "det_start", torch.int32)
+        if det_boxes.dim() != 2 or det_boxes.shape[1] != 4:
+            raise ValueError("eval_match: concatenated detections must be (D,4)")
+        B, K, D = int(det_start.numel()) - 1, 0, int(det_boxes.shape[0])
+        if det_classes.numel() != D or det_scores.numel() != D:
+            raise ValueError("eval_match: inconsistent array lengths")
+    G = int(gt_boxes.shape[0])
+    if B < 1 or gt_boxes.dim() != 2 or gt_boxes.shape[1] != 4 or gt_classes.numel() != G or gt_start.numel() != B + 1 \
+            or n_gt.numel() != n_classes:
+        raise ValueError("eval_match: inconsistent array lengths")
+    if gt_difficult is not None:
+        _req(gt_difficult, "gt_difficult", torch.uint8)
+        if gt_difficult.numel() != G:
+            raise ValueError("eval_match: gt_difficult must have one flag per ground-truth box")
+    dev = gt_start.device
+    thr = np.ascontiguousarray(np.asarray(thresholds, np.float32))
+    rec = torch.empty(max(D, 1), device=dev, dtype=torch.int32)
+    tp = torch.empty(max(D, 1), device=dev, dtype=torch.int16)
+    ign = torch.empty(max(D, 1), device=dev, dtype=torch.int16)
+    lib = _lib.load()
+    ws = workspace(lib.ssd_eval_match_workspace(G), dev, "eval_match")
+    check(lib.ssd_eval_match(_ptr(det_boxes), _ptr(det_classes), _ptr(det_scores), _ptr(det_start), _ptr(det_count), K, D,
+                             _ptr(gt_boxes), _ptr(gt_classes), _ptr(gt_difficult), gt_start.data_ptr(), G, B, int(n_classes),
+                             thr.ctypes.data, int(thr.size), rec.data_ptr(), tp.data_ptr(), ign.data_ptr(), n_gt.data_ptr(),
+                             ws.data_ptr(), ws.numel(), _stream()), "eval_match")
+    launch_counts["eval_match"] += 1
+    return rec[:D], tp[:D], ign[:D]
+
+
+def eval_ap(rec_classes, det_scores, tp, ignored, n_gt, n_thresholds, n_levels, n_classes):
+    """Per-class order and AP tables of the detection evaluator (include/ssd_gfx950.h ssd_eval_ap) over D detection rows.
+    n_levels: 10, 100 or 0 (all-point).  -> (out float64 (T, n_classes, n_levels + 1) or (T, n_classes), n_det (n_classes,) int32)."""
+    _req(rec_classes, "rec_classes", torch.int32); _req(det_scores, "det_scores"); _req(n_gt, "n_gt", torch.int32)
+    _req(tp, "tp", torch.int16); _req(ignored, "ignored", torch.int16)
+    D = int(rec_classes.numel())
+    if det_scores.numel() != D or tp.numel() != D or ignored.numel() != D or n_gt.numel() != n_classes:
+        raise ValueError("eval_ap: inconsistent array lengths")
+    dev = n_gt.device
+    shape = (n_thresholds, n_classes, n_levels + 1) if n_levels else (n_thresholds, n_classes)
+    out = torch.empty(shape, device=dev, dtype=torch.float64)
+    n_det = torch.empty(n_classes, device=dev, dtype=torch.int32)
+    lib = _lib.load()
+    ws = workspace(lib.ssd_eval_ap_workspace(D), dev, "eval_ap")
+    nz = D > 0
+    check(lib.ssd_eval_ap(_ptr(rec_classes) if nz else None, _ptr(det_scores) if nz else None, _ptr(tp) if nz else None,
+                          _ptr(ignored) if nz else None, D, n_gt.data_ptr(), int(n_classes), int(n_thresholds), int(n_levels),
+                          out.data_ptr(), n_det.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "eval_ap")
+    launch_counts["eval_ap"] += 1
+    return out, n_det
+
+
 def preprocess_u8(arena: torch.Tensor, descs, out_hw=(300, 300), mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
                   filler=(123, 116, 103)) -> torch.Tensor:
     """arena: uint8 device tensor holding the HWC RGB images; descs: ctypes array of _lib.ImageDesc (host).

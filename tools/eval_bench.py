@@ -1,0 +1,139 @@
+"""Cost of the detection evaluator (Util.DetectionEvaluator) beside get_map's device core (ops.map_eval) on the shape of
+`bench.py --workload map` -- 4952 images x 200 detections, seeded as that workload seeds them -- at 20 and at 80 classes, in one
+process, old and new alternating round by round after a warm-up:
+
+  * map_eval                 get_map's kernels on the concatenated arrays (HIP events)
+  * compute() at (0.5,) 11point and at the ten-threshold sweep: wall time of the call (it ends with the copy to the host) and the
+    device time of its kernels alone (ops.eval_ap between HIP events)
+  * add_batch                per batch of 32 x 200 padded detections with packed device ground truth: host time per call (enqueue
+    only) and device time per call, at one threshold and at the sweep
+  * the number of matching launches per pass (one per add_batch whatever the number of thresholds)
+
+min / median / max over the rounds, the shader clock between two probes; one JSON line.  To attribute the time to kernels:
+
+    rocprofv3 --kernel-trace --stats -d OUT -o eval -- python tools/eval_bench.py --rounds 3
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from objectdetection_ssd_amd import Util, ops
+
+DEV = torch.device("cuda:0")
+N_IMG, PER = 4952, 200
+
+
+def workload(n_classes, seed=1234):
+    rng = np.random.default_rng(seed)
+    D = N_IMG * PER
+    gcnt = 1 + np.minimum(rng.poisson(1.4, N_IMG), 7)
+    G = int(gcnt.sum())
+    gx = rng.uniform(0, .6, (G, 2)); gwh = rng.uniform(.08, .4, (G, 2))
+    gb = np.concatenate([gx, gx + gwh], 1).astype(np.float32)
+    gstart = np.concatenate([[0], np.cumsum(gcnt)])
+    pick = (gstart[:-1, None] + rng.integers(0, 1 << 30, (N_IMG, PER)) % gcnt[:, None]).reshape(-1)
+    db = (gb[pick] + rng.normal(0, .05, (D, 4))).astype(np.float32)
+    gc = rng.integers(0, n_classes, G)
+    dc = np.where(rng.uniform(size=D) < .7, gc[pick], rng.integers(0, n_classes, D))
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dt)     # noqa: E731
+    return dict(db=t(db, torch.float32), dc=t(dc, torch.int32), ds=t(rng.uniform(0, 1, D), torch.float32),
+                dstart=t(np.arange(N_IMG + 1) * PER, torch.int32), gb=t(gb, torch.float32), gc=t(gc, torch.int32),
+                gstart=t(gstart, torch.int32), gstart_host=gstart)
+
+
+def events(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) * 1e3
+
+
+def fill(ev, w, bs=32):
+    """The whole set in padded batches of `bs` images with packed device ground truth; -> (host ms per call, calls)."""
+    db, dc, ds = w["db"].view(N_IMG, PER, 4), w["dc"].view(N_IMG, PER), w["ds"].view(N_IMG, PER)
+    full = torch.full((N_IMG,), PER, device=DEV, dtype=torch.int32)
+    host = w["gstart_host"]
+    offs = [(w["gstart"][s:s + bs + 1] - w["gstart"][s]).contiguous() for s in range(0, N_IMG, bs)]      # made before the clock starts
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for k, s in enumerate(range(0, N_IMG, bs)):
+        e = min(s + bs, N_IMG)
+        ev.add_batch(db[s:e], dc[s:e], ds[s:e], full[s:e], w["gb"][host[s]:host[e]], w["gc"][host[s]:host[e]], None, gt_offsets=offs[k])
+    return (time.perf_counter() - t) * 1e3 / len(offs), len(offs)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    args = ap.parse_args()
+    sweep = Util.COCO_IOU_THRESHOLDS
+    levels = torch.arange(0, 1.1, 0.1).double().numpy()
+    out = {"rounds": args.rounds, "images": N_IMG, "detections": N_IMG * PER}
+    p0 = ops.clock_probe(DEV)
+    for C in (20, 80):
+        w = workload(C)
+        evs = {"t1": Util.DetectionEvaluator(C, (0.5,), "11point"), "t10": Util.DetectionEvaluator(C, sweep, "11point")}
+        res = {}
+
+        def rec(k, v):
+            res.setdefault(k, []).append(v)
+
+        def old():
+            ops.map_eval(w["db"], w["dc"], w["ds"], w["dstart"], w["gb"], w["gc"], w["gstart"], levels, C)
+
+        def kernels(ev):
+            rec_, score = torch.cat(ev._rec), torch.cat(ev._score)
+            tp, ign = torch.cat(ev._tp), torch.cat(ev._ign)
+            return lambda: ops.eval_ap(rec_, score, tp, ign, ev._n_gt, len(ev._thr32), 10, C)
+
+        for r in range(args.rounds + 1):                                    # round 0 is the warm-up
+            keep = r > 0
+            t_old = events(old)
+            for name, ev in evs.items():
+                ev.reset()
+                before = ops.launch_counts["eval_match"]
+                host_ms = [None]
+                dev_ms = events(lambda: host_ms.__setitem__(0, fill(ev, w)))
+                per_call, calls = host_ms[0]
+                t_compute = wall(ev.compute)
+                t_kernels = events(kernels(ev))
+                if keep:
+                    rec(f"add_batch_host_ms_{name}", per_call)
+                    rec(f"add_batch_device_ms_{name}", dev_ms / calls)
+                    rec(f"compute_wall_ms_{name}", t_compute)
+                    rec(f"compute_kernels_ms_{name}", t_kernels)
+                out[f"C{C}_match_launches_per_pass_{name}"] = ops.launch_counts["eval_match"] - before
+                out[f"C{C}_add_batch_calls"] = calls
+            if keep:
+                rec("map_eval_ms", t_old)
+        for k, v in res.items():
+            out[f"C{C}_{k}"] = {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
+        r1 = evs["t1"].compute()
+        out[f"C{C}_mean_ap_t50"] = float(r1["mean_ap"][0])
+    out["shader_mhz"] = round(ops.shader_mhz(p0, ops.clock_probe(DEV)), 1)
+    out["note"] = ("map_eval = get_map's kernels (match + order + AP); compute = order + AP of the evaluator (its matching ran in add_batch); "
+                   "add_batch device time = events around the whole pass / calls: the serial selection of the longest (image, class) "
+                   "list of each batch, plus the prep kernel and the score copy")
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
