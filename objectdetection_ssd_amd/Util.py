@@ -156,16 +156,12 @@ def get_map(det_boxes, det_classes, det_scores, gt_boxes, gt_classes, n_classes=
         raise ValueError("get_map expects five lists with one entry per image")
     dev = next((t.device for t in list(det_boxes) + list(gt_boxes) if torch.is_tensor(t) and t.is_cuda), device)
 
-    def flat(items, dtype, width):
-        parts = [torch.as_tensor(t).reshape((-1, width) if width else (-1,)).to(device=dev, dtype=dtype) for t in items]
-        start = torch.tensor([0] + [int(p.shape[0]) for p in parts], dtype=torch.int64).cumsum(0).to(device=dev, dtype=torch.int32)
-        return torch.cat(parts).contiguous(), start
-
-    db, d_start = flat(det_boxes, torch.float32, 4)
-    dc, _ = flat(det_classes, torch.int32, 0)
-    ds, _ = flat(det_scores, torch.float32, 0)
-    gb, g_start = flat(gt_boxes, torch.float32, 4)
-    gc, _ = flat(gt_classes, torch.int32, 0)
+    db, per_det = _cat(det_boxes, torch.float32, 4, dev)
+    dc, _ = _cat(det_classes, torch.int32, 0, dev)
+    ds, _ = _cat(det_scores, torch.float32, 0, dev)
+    gb, per_gt = _cat(gt_boxes, torch.float32, 4, dev)
+    gc, _ = _cat(gt_classes, torch.int32, 0, dev)
+    d_start, g_start = _starts(per_det, dev), _starts(per_gt, dev)
     levels = torch.arange(0, 1.1, 0.1).double().numpy()                # Util.py:874, float32 levels compared in float64
     table, _, _ = ops.map_eval(db, dc, ds, d_start, gb, gc, g_start, levels, int(n_classes))
     t = table.cpu().numpy()
@@ -274,8 +270,47 @@ def _eval_batch_inputs(boxes, classes, scores, count, gt_boxes, gt_classes, gt_e
     return db, dc, ds, d_start, d_count, gb, gc, extras, g_start, dev
 
 
-class DetectionEvaluator:
-    """Average precision under the PASCAL VOC devkit's matching rule, on the GPU (csrc/map_eval.hip E1-E4), with what `get_map`
+class _BatchRecords:
+    """What the two evaluators keep between `add_batch` and `compute`: per batch the record class, score and protocol fields of every
+    detection row (`_FIELDS`, device tensors, one list per field), and the objects per class `_n_gt`, made on the first batch's
+    device."""
+    _FIELDS = ()
+
+    def reset(self):
+        """Forget every batch added so far."""
+        for name in ("rec", "score") + self._FIELDS:
+            setattr(self, "_" + name, [])
+        self._n_gt = None
+        self._padded = False
+        self._dev = None
+
+    def _n_gt_on(self, dev, shape):
+        if self._n_gt is None:
+            self._n_gt = torch.zeros(shape, device=dev, dtype=torch.int32)
+            self._dev = dev
+        return self._n_gt
+
+    def _keep(self, padded, scores, rec, *fields):
+        self._padded = self._padded or padded
+        self._rec.append(rec)
+        self._score.append(scores.reshape(-1).clone() if padded else scores)        # the caller may reuse its padded buffers
+        for name, value in zip(self._FIELDS, fields):
+            getattr(self, "_" + name).append(value)
+
+    def _records(self):
+        """-> [rec, score, *fields] over all batches in the order added, without the rows past count[b] of the padded batches."""
+        if self._n_gt is None:
+            raise RuntimeError(f"{type(self).__name__}.compute(): no batch has been added")
+        with torch.cuda.device(self._dev):
+            cols = [torch.cat(getattr(self, "_" + name)) for name in ("rec", "score") + self._FIELDS]
+            if self._padded:
+                keep = cols[0] != -2
+                cols = [c[keep].contiguous() for c in cols]
+        return cols
+
+
+class DetectionEvaluator(_BatchRecords):
+    """Average precision under the PASCAL VOC devkit's matching rule, on the GPU (csrc/map_eval.hip, the VOC rule), with what `get_map`
     lacks: 'difficult' objects, up to 16 IoU thresholds settled in one matching pass, 11-point, 101-point or all-point
     (VOC2010+) interpolation, and batch-wise accumulation without host synchronisation.
 
@@ -308,6 +343,8 @@ class DetectionEvaluator:
     `CocoEvaluator`.
     GPU only, like `get_map`: there is no CPU fallback."""
 
+    _FIELDS = ("tp", "ign")
+
     def __init__(self, n_classes=20, iou_thresholds=(0.5,), interpolation="11point"):
         self.n_classes, self._thr32 = _check_eval_args(n_classes, iou_thresholds, interpolation)
         if not torch.cuda.is_available():
@@ -315,13 +352,6 @@ class DetectionEvaluator:
         self.iou_thresholds = tuple(float(t) for t in iou_thresholds)
         self.interpolation = interpolation
         self.reset()
-
-    def reset(self):
-        """Forget every batch added so far."""
-        self._rec, self._score, self._tp, self._ign = [], [], [], []
-        self._n_gt = None
-        self._padded = False
-        self._dev = None
 
     def add_batch(self, boxes, classes, scores, count, gt_boxes, gt_classes, gt_difficult=None, gt_offsets=None):
         """Score one batch of images against its ground truth and keep the per-detection records.
@@ -335,14 +365,10 @@ class DetectionEvaluator:
         from . import ops
         db, dc, ds, d_start, d_count, gb, gc, (gd,), g_start, dev = _eval_batch_inputs(
             boxes, classes, scores, count, gt_boxes, gt_classes, [(gt_difficult, torch.uint8, "gt_difficult")], gt_offsets, self._dev)
-        self._padded = self._padded or count is not None
         with torch.cuda.device(dev):
-            if self._n_gt is None:
-                self._n_gt = torch.zeros(self.n_classes, device=dev, dtype=torch.int32)
-                self._dev = dev
-            rec, tp, ign = ops.eval_match(db, dc, ds, d_start, d_count, gb, gc, gd, g_start, self._n_gt, self._thr32, self.n_classes)
-        self._rec.append(rec); self._tp.append(tp); self._ign.append(ign)
-        self._score.append(ds.reshape(-1).clone() if count is not None else ds)      # the caller may reuse its padded buffers
+            n_gt = self._n_gt_on(dev, self.n_classes)
+            rec, tp, ign = ops.eval_match(db, dc, ds, d_start, d_count, gb, gc, gd, g_start, n_gt, self._thr32, self.n_classes)
+        self._keep(count is not None, ds, rec, tp, ign)
 
     def compute(self):
         """-> dict: `ap` float64 (T, n_classes), NaN where a class has no non-difficult ground truth; `mean_ap` float64 (T,), nanmean
@@ -351,15 +377,9 @@ class DetectionEvaluator:
         May be called repeatedly; more batches may be added afterwards."""
         import numpy as np
         from . import ops
-        if self._n_gt is None:
-            raise RuntimeError("DetectionEvaluator.compute(): no batch has been added")
         T, C, L = len(self._thr32), self.n_classes, _INTERPOLATION_LEVELS[self.interpolation]
+        rec, score, tp, ign = self._records()
         with torch.cuda.device(self._dev):
-            rec, score = torch.cat(self._rec), torch.cat(self._score)
-            tp, ign = torch.cat(self._tp), torch.cat(self._ign)
-            if self._padded:
-                keep = rec != -2                                              # rows past count[b] of the padded batches
-                rec, score, tp, ign = rec[keep].contiguous(), score[keep].contiguous(), tp[keep].contiguous(), ign[keep].contiguous()
             out, n_det = ops.eval_ap(rec, score, tp, ign, self._n_gt, T, L, C)
             out = out.cpu().numpy()
             n_gt = self._n_gt.cpu().numpy().astype(np.int64)
@@ -445,9 +465,9 @@ def coco_stats(ap, recall, iou_thresholds32, area_names, max_dets):
     return stats
 
 
-class CocoEvaluator:
+class CocoEvaluator(_BatchRecords):
     """COCO detection metrics for boxes -- pycocotools' `COCOeval` protocol: crowd regions, area ranges, maxDets, AP and AR -- on the
-    GPU (csrc/map_eval.hip C1-C3), accumulated batch-wise without host synchronisation.
+    GPU (csrc/map_eval.hip, the COCO rule), accumulated batch-wise without host synchronisation.
 
         ev = CocoEvaluator(n_classes=80, iou_thresholds=COCO_IOU_THRESHOLDS, area_ranges=COCO_AREA_RANGES, max_dets=COCO_MAX_DETS)
         ev.add_batch(boxes, classes, scores, count, gt_boxes, gt_classes, gt_crowd, gt_area)   # per batch: enqueues only
@@ -481,6 +501,8 @@ class CocoEvaluator:
     epsilon (there: `+ eps` in the denominator); a NaN overlap never matches (there: it would); boxes are xyxy in the caller's units
     (there: xywh).  GPU only: there is no CPU fallback."""
 
+    _FIELDS = ("tp", "ign", "rank")
+
     def __init__(self, n_classes=80, iou_thresholds=COCO_IOU_THRESHOLDS, area_ranges=COCO_AREA_RANGES, max_dets=COCO_MAX_DETS):
         self.n_classes, self._thr32, self.area_ranges, self._lo32, self._hi32, self.max_dets = _check_coco_args(
             n_classes, iou_thresholds, area_ranges, max_dets)
@@ -488,13 +510,6 @@ class CocoEvaluator:
             raise RuntimeError("CocoEvaluator runs on the gfx950 HIP kernels only (no CPU fallback)")
         self.iou_thresholds = tuple(float(t) for t in iou_thresholds)
         self.reset()
-
-    def reset(self):
-        """Forget every batch added so far."""
-        self._rec, self._score, self._tp, self._ign, self._rank = [], [], [], [], []
-        self._n_gt = None
-        self._padded = False
-        self._dev = None
 
     def add_batch(self, boxes, classes, scores, count, gt_boxes, gt_classes, gt_crowd=None, gt_area=None, gt_offsets=None):
         """Score one batch of images against its ground truth and keep the per-detection records.  The layouts are those of
@@ -504,15 +519,11 @@ class CocoEvaluator:
         db, dc, ds, d_start, d_count, gb, gc, (gcrowd, garea), g_start, dev = _eval_batch_inputs(
             boxes, classes, scores, count, gt_boxes, gt_classes,
             [(gt_crowd, torch.uint8, "gt_crowd"), (gt_area, torch.float32, "gt_area")], gt_offsets, self._dev)
-        self._padded = self._padded or count is not None
         with torch.cuda.device(dev):
-            if self._n_gt is None:
-                self._n_gt = torch.zeros((len(self.area_ranges), self.n_classes), device=dev, dtype=torch.int32)
-                self._dev = dev
-            rec, tp, ign, rank = ops.coco_match(db, dc, ds, d_start, d_count, gb, gc, gcrowd, garea, g_start, self._n_gt, self._thr32,
+            n_gt = self._n_gt_on(dev, (len(self.area_ranges), self.n_classes))
+            rec, tp, ign, rank = ops.coco_match(db, dc, ds, d_start, d_count, gb, gc, gcrowd, garea, g_start, n_gt, self._thr32,
                                                 self._lo32, self._hi32, self.max_dets[-1], self.n_classes)
-        self._rec.append(rec); self._tp.append(tp); self._ign.append(ign); self._rank.append(rank)
-        self._score.append(ds.reshape(-1).clone() if count is not None else ds)      # the caller may reuse its padded buffers
+        self._keep(count is not None, ds, rec, tp, ign, rank)
 
     def compute(self):
         """-> dict: `ap` float64 (T, A, C), NaN where n_gt = 0; `precision` float64 (T, A, C, 101); `recall` float64 (T, A, M, C), NaN
@@ -522,16 +533,9 @@ class CocoEvaluator:
         May be called repeatedly; more batches may be added afterwards."""
         import numpy as np
         from . import ops
-        if self._n_gt is None:
-            raise RuntimeError("CocoEvaluator.compute(): no batch has been added")
         T, A, C = len(self._thr32), len(self.area_ranges), self.n_classes
+        rec, score, tp, ign, rank = self._records()
         with torch.cuda.device(self._dev):
-            rec, score, rank = torch.cat(self._rec), torch.cat(self._score), torch.cat(self._rank)
-            tp, ign = torch.cat(self._tp), torch.cat(self._ign)
-            if self._padded:
-                keep = rec != -2                                              # rows past count[b] of the padded batches
-                rec, score, rank = rec[keep].contiguous(), score[keep].contiguous(), rank[keep].contiguous()
-                tp, ign = tp[keep].contiguous(), ign[keep].contiguous()
             out, tp_count, n_det = ops.coco_ap(rec, score, tp, ign, rank, self._n_gt, T, A, self.max_dets, C)
             precision = out.cpu().numpy()
             tp_count = tp_count.cpu().numpy().astype(np.int64)

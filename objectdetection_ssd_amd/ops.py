@@ -934,6 +934,32 @@ def map_eval(det_boxes, det_classes, det_scores, det_start, gt_boxes, gt_classes
 launch_counts = {"eval_match": 0, "eval_ap": 0, "coco_match": 0, "coco_ap": 0}
 
 
+def _det_layout(name, det_boxes, det_classes, det_scores, det_start, det_count, gt_boxes, gt_classes, gt_start, n_gt):
+    """The dtype checks the match entries share and the layout of their detections: concatenated (det_start) or padded (det_count)
+    -> (B, K, D), K = 0 for concatenated rows."""
+    _req(det_boxes, "det_boxes"); _req(det_scores, "det_scores"); _req(gt_boxes, "gt_boxes")
+    _req(det_classes, "det_classes", torch.int32); _req(gt_classes, "gt_classes", torch.int32)
+    _req(gt_start, "gt_start", torch.int32); _req(n_gt, "n_gt", torch.int32)
+    if (det_start is None) == (det_count is None):
+        raise ValueError(f"{name}: give det_start (concatenated rows) or det_count (padded rows), not both")
+    if det_count is not None:
+        _req(det_count, "det_count", torch.int32)
+        if det_boxes.dim() != 3 or det_boxes.shape[2] != 4 or det_boxes.shape[1] < 1:
+            raise ValueError(f"{name}: padded detections must be (B,K,4) with K >= 1")
+        B, K = int(det_boxes.shape[0]), int(det_boxes.shape[1])
+        D = B * K
+        if tuple(det_classes.shape) != (B, K) or tuple(det_scores.shape) != (B, K) or det_count.numel() != B:
+            raise ValueError(f"{name}: inconsistent padded shapes")
+    else:
+        _req(det_start, "det_start", torch.int32)
+        if det_boxes.dim() != 2 or det_boxes.shape[1] != 4:
+            raise ValueError(f"{name}: concatenated detections must be (D,4)")
+        B, K, D = int(det_start.numel()) - 1, 0, int(det_boxes.shape[0])
+        if det_classes.numel() != D or det_scores.numel() != D:
+            raise ValueError(f"{name}: inconsistent array lengths")
+    return B, K, D
+
+
 def eval_match(det_boxes, det_classes, det_scores, det_start, det_count, gt_boxes, gt_classes, gt_difficult, gt_start, n_gt,
                thresholds, n_classes):
     """One batch of the detection evaluator (include/ssd_gfx950.h ssd_eval_match).  Detections: concatenated (D,4)/(D,)/(D,) with
@@ -942,26 +968,7 @@ def eval_match(det_boxes, det_classes, det_scores, det_start, det_count, gt_boxe
     added to.  thresholds: host sequence of floats.  -> (rec_classes int32, tp int16, ignored int16), one entry per detection row
     (the 16-bit masks are bit patterns: view them as uint16).  Enqueues only; no host synchronisation."""
     import numpy as np
-    _req(det_boxes, "det_boxes"); _req(det_scores, "det_scores"); _req(gt_boxes, "gt_boxes")
-    _req(det_classes, "det_classes", torch.int32); _req(gt_classes, "gt_classes", torch.int32)
-    _req(gt_start, "gt_start", torch.int32); _req(n_gt, "n_gt", torch.int32)
-    if (det_start is None) == (det_count is None):
-        raise ValueError("eval_match: give det_start (concatenated rows) or det_count (padded rows), not both")
-    if det_count is not None:
-        _req(det_count, "det_count", torch.int32)
-        if det_boxes.dim() != 3 or det_boxes.shape[2] != 4 or det_boxes.shape[1] < 1:
-            raise ValueError("eval_match: padded detections must be (B,K,4) with K >= 1")
-        B, K = int(det_boxes.shape[0]), int(det_boxes.shape[1])
-        D = B * K
-        if tuple(det_classes.shape) != (B, K) or tuple(det_scores.shape) != (B, K) or det_count.numel() != B:
-            raise ValueError("eval_match: inconsistent padded shapes")
-    else:
-        _req(det_start, "det_start", torch.int32)
-        if det_boxes.dim() != 2 or det_boxes.shape[1] != 4:
-            raise ValueError("eval_match: concatenated detections must be (D,4)")
-        B, K, D = int(det_start.numel()) - 1, 0, int(det_boxes.shape[0])
-        if det_classes.numel() != D or det_scores.numel() != D:
-            raise ValueError("eval_match: inconsistent array lengths")
+    B, K, D = _det_layout("eval_match", det_boxes, det_classes, det_scores, det_start, det_count, gt_boxes, gt_classes, gt_start, n_gt)
     G = int(gt_boxes.shape[0])
     if B < 1 or gt_boxes.dim() != 2 or gt_boxes.shape[1] != 4 or gt_classes.numel() != G or gt_start.numel() != B + 1 \
             or n_gt.numel() != n_classes:
@@ -1015,26 +1022,7 @@ def coco_match(det_boxes, det_classes, det_scores, det_start, det_count, gt_boxe
     tp int64, ignored int64, rank int32), one entry per detection row; bit a*16 + t of the 64-bit words is area range a at
     threshold t (bit patterns: view them as four uint16).  Enqueues only; no host synchronisation."""
     import numpy as np
-    _req(det_boxes, "det_boxes"); _req(det_scores, "det_scores"); _req(gt_boxes, "gt_boxes")
-    _req(det_classes, "det_classes", torch.int32); _req(gt_classes, "gt_classes", torch.int32)
-    _req(gt_start, "gt_start", torch.int32); _req(n_gt, "n_gt", torch.int32)
-    if (det_start is None) == (det_count is None):
-        raise ValueError("coco_match: give det_start (concatenated rows) or det_count (padded rows), not both")
-    if det_count is not None:
-        _req(det_count, "det_count", torch.int32)
-        if det_boxes.dim() != 3 or det_boxes.shape[2] != 4 or det_boxes.shape[1] < 1:
-            raise ValueError("coco_match: padded detections must be (B,K,4) with K >= 1")
-        B, K = int(det_boxes.shape[0]), int(det_boxes.shape[1])
-        D = B * K
-        if tuple(det_classes.shape) != (B, K) or tuple(det_scores.shape) != (B, K) or det_count.numel() != B:
-            raise ValueError("coco_match: inconsistent padded shapes")
-    else:
-        _req(det_start, "det_start", torch.int32)
-        if det_boxes.dim() != 2 or det_boxes.shape[1] != 4:
-            raise ValueError("coco_match: concatenated detections must be (D,4)")
-        B, K, D = int(det_start.numel()) - 1, 0, int(det_boxes.shape[0])
-        if det_classes.numel() != D or det_scores.numel() != D:
-            raise ValueError("coco_match: inconsistent array lengths")
+    B, K, D = _det_layout("coco_match", det_boxes, det_classes, det_scores, det_start, det_count, gt_boxes, gt_classes, gt_start, n_gt)
     G = int(gt_boxes.shape[0])
     thr = np.ascontiguousarray(np.asarray(thresholds, np.float32))
     lo = np.ascontiguousarray(np.asarray(area_lo, np.float32))

@@ -1,4 +1,4 @@
-"""COCO evaluator on the device (Util.CocoEvaluator / evaluate_coco, csrc/map_eval.hip C1-C3) against the protocol restatement
+"""COCO evaluator on the device (Util.CocoEvaluator / evaluate_coco, csrc/map_eval.hip) against the protocol restatement
 (tests/coco_protocol_ref.py).  Every comparison is bit-exact, NaN positions included: the overlaps are reproducible float32, each
 precision is one division of two integers, and the means are the same numpy calls on both sides."""
 import numpy as np
