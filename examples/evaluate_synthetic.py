@@ -3,9 +3,11 @@
 near zero; the loop is the point.
 
     python examples/evaluate_synthetic.py [--batches 4] [--batch 32] [--sweep] [--protocol voc|coco]
+                                          [--nms hard|linear|gaussian] [--keep-score 0.001]
 
 See INTEGRATION.md section 3c for the VOC devkit protocol (difficult flags) and the coordinate systems, section 3d for COCO's
-(crowd regions, area ranges in pixels, maxDets).
+(crowd regions, area ranges in pixels, maxDets), section 3e for Soft-NMS (--nms; --keep-score: the decayed score below which a
+box is dropped, default = the candidate threshold 0.02).
 """
 import argparse
 import os
@@ -42,6 +44,8 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--sweep", action="store_true", help="IoU 0.50:0.05:0.95 instead of 0.5 alone")
     ap.add_argument("--protocol", choices=("voc", "coco"), default="voc", help="coco: the 81-column model and COCO's twelve numbers")
+    ap.add_argument("--nms", choices=("hard", "linear", "gaussian"), default="hard", help="suppression rule of the decode")
+    ap.add_argument("--keep-score", type=float, default=None, help="Soft-NMS: drop boxes whose decayed score falls below this")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.protocol == "coco":
@@ -56,7 +60,7 @@ def main():
         gt_boxes, gt_classes, gt_difficult, gt_offsets = ground_truth(a.batch, rng, dev)
         with torch.no_grad():
             loc, conf = cnn(x)
-        boxes, classes, probs, _, count = inference_batch_padded(loc, conf, sizes, min_score=0.02)
+        boxes, classes, probs, _, count = inference_batch_padded(loc, conf, sizes, min_score=0.02, nms=a.nms, keep_score=a.keep_score)
         ev.add_batch(boxes, classes, probs, count, gt_boxes, gt_classes, gt_difficult, gt_offsets=gt_offsets)
     res = ev.compute()
     for t, m in zip(res["iou_thresholds"], res["mean_ap"]):
@@ -79,7 +83,7 @@ def main_coco(a, dev):
         gt_area = (gt_boxes[:, 2] - gt_boxes[:, 0]) * (gt_boxes[:, 3] - gt_boxes[:, 1]) * 0.7
         with torch.no_grad():
             loc, conf = cnn(x)
-        boxes, classes, probs, _, count = inference_batch_padded(loc, conf, sizes, min_score=0.02)
+        boxes, classes, probs, _, count = inference_batch_padded(loc, conf, sizes, min_score=0.02, nms=a.nms, keep_score=a.keep_score)
         ev.add_batch(boxes, classes, probs, count, gt_boxes, gt_classes, gt_crowd, gt_area, gt_offsets=gt_offsets)
     res = ev.compute()
     for k, v in res["stats"].items():

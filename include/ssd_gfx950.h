@@ -465,6 +465,32 @@ int ssd_decode_nms_batch(const float* l_, const float* c_, const float* priors_c
                          int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
                          float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Soft-NMS (Bodla et al. 2017) as the suppression rule of the same decode: the arguments of ssd_decode_nms[_batch] followed by
+ * method (1 = linear, 2 = gaussian), sigma (> 0; gaussian only) and keep_score (1e-6 .. 1).  Per class, in descending order of
+ * probability (ties: lower prior index): pick the live candidate with the largest score (ties: earlier in that order), stop once
+ * it is below keep_score, otherwise emit it and multiply every other live score by
+ *   linear:   iou > iou_threshold ? 1 - iou : 1          gaussian:   expf(-(iou * iou) / sigma)          1 where iou is not finite;
+ * a candidate whose score falls below keep_score is dropped.  At most top_k picks per class; the emitted probs are the decayed
+ * scores, and the cross-class top-k runs on them.  The same workspace as the hard rule, no allocation, no host synchronisation.
+ * SSD_ERR_BAD_SHAPE -- before anything is enqueued -- for another method, sigma <= 0, keep_score or iou_threshold (0 .. 1) out of
+ * range, or P > 40704 (the live scores of a class, 4 * P bytes, stay in LDS). */
+int ssd_decode_nms_soft(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
+                        float min_score, float iou_threshold, int top_k, float img_w, float img_h,
+                        float* boxes, int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count,
+                        void* workspace, size_t workspace_bytes, void* stream, int method, float sigma, float keep_score);
+int ssd_decode_nms_batch_soft(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
+                              int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
+                              float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes, void* stream,
+                              int method, float sigma, float keep_score);
+/* The Soft-NMS kernel alone, for tests and tools: s_boxes (B,C1,P,4) xyxy and s_prob (B,C1,P) hold, per (image, class), the
+ * cand_cnt[b * (C1 + 1) + c] candidates in descending order of probability (cand_cnt is (B, C1+1)); C1 = 1..255.  Outputs, per
+ * (image, class) in pick order: kept_pos (B,C1,P) sorted positions, kept_prob (B,C1,P) decayed scores, kept_cnt (B, C1+1) number of
+ * picks (<= max_picks, 1..4096).  Scores must be finite, positive and descending; anything else gives unspecified values, never an
+ * access outside the arrays. */
+int ssd_soft_nms_sorted(const float* s_boxes, const float* s_prob, const int32_t* cand_cnt, int B, int C1, int P, int method,
+                        float iou_threshold, float sigma, float keep_score, int max_picks, int32_t* kept_pos, float* kept_prob,
+                        int32_t* kept_cnt, void* stream);
+
 /* ---- mAP evaluator (Util.py:783-885 get_map: per-class 11-point interpolated AP, IoU > 0.5, one claim per
  * ground-truth box, no 'difficult' handling) over B images given as concatenated arrays:
  * det_* (D rows; det_start[B+1] = first row of each image), gt_* (G rows; gt_start[B+1]); classes are int32 in

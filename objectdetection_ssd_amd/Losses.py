@@ -120,19 +120,24 @@ def _image_size(index, phase):
 draw_hook = None      # optional callable(image_path_or_size, boxes, labels, probs); drawing itself is out of scope
 
 
-def inference(l_, c_, index, top_k=200, phase='train', toDraw=True, min_score=0.2, iou_threshold=0.45):
+def inference(l_, c_, index, top_k=200, phase='train', toDraw=True, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5,
+              keep_score=None):
     """l_ (8732,4) predicted offsets, c_ (8732,C) class scores of ONE image (C = foreground classes + background, 2..256;
     detections carry class ids 0..C-2).  `index` is either the
     reference's dataset index (image size read from `all_images[phase][index]`) or an (img_w, img_h)
     pair.  Returns (boxes (K,4) pixel xyxy, classes (K,) int64, probs (K,)) with K <= top_k, or
     ([], [], []) when nothing reaches min_score (reference Losses.py:62-63).  Drawing (Losses.py:92-97) is
-    out of scope: with toDraw the optional module-level `draw_hook` is called, nothing otherwise."""
+    out of scope: with toDraw the optional module-level `draw_hook` is called, nothing otherwise.
+    nms: "hard" (the reference's greedy rule), or Soft-NMS "linear" / "gaussian" (INTEGRATION.md section 3e): overlapped boxes keep a
+    decayed score -- times 1 - IoU beyond iou_threshold, or times exp(-IoU^2 / sigma) -- and are dropped below keep_score (None:
+    min_score); the returned probs are the decayed scores."""
+    ops.nms_method(nms)
     if not l_.is_cuda:
         raise RuntimeError("inference() runs on the gfx950 HIP kernels only (no CPU fallback)")
     w, h = _image_size(index, phase)
     pri, _ = _priors_on(l_.device, l_.shape[0])
     boxes, classes, probs, ids, count = ops.decode_nms(l_.detach().float().contiguous(), c_.detach().float().contiguous(), pri,
-                                                      w, h, top_k, min_score, iou_threshold)
+                                                      w, h, top_k, min_score, iou_threshold, nms, sigma, keep_score)
     k = int(count.item())
     if k == 0:
         return [], [], []
@@ -147,11 +152,12 @@ def inference(l_, c_, index, top_k=200, phase='train', toDraw=True, min_score=0.
 inference.last_prior_ids = None
 
 
-def inference_batch_padded(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=0.45):
+def inference_batch_padded(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5, keep_score=None):
     """The batched decode as it leaves the device: (boxes (B,top_k,4) pixel xyxy, classes (B,top_k) int64, probs (B,top_k),
     prior_ids (B,top_k) int32, count (B,) int32), rows i >= count[b] zero.  Four kernels + one memset, NO host synchronisation:
     the primary form for a serving loop (slice on the host only when the detections are consumed there).  `sizes`: a (B,2) device
-    tensor of (img_w, img_h) is used as it is; anything else is uploaded."""
+    tensor of (img_w, img_h) is used as it is; anything else is uploaded.  nms / sigma / keep_score: as in `inference`."""
+    ops.nms_method(nms)
     if not l.is_cuda:
         raise RuntimeError("inference_batch_padded() runs on the gfx950 HIP kernels only (no CPU fallback)")
     if torch.is_tensor(sizes) and sizes.is_cuda and sizes.dtype == torch.float32 and sizes.is_contiguous():
@@ -159,14 +165,15 @@ def inference_batch_padded(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=
     else:
         wh = torch.as_tensor(sizes, dtype=torch.float32).reshape(-1, 2).to(l.device).contiguous()
     pri, _ = _priors_on(l.device, l.shape[1])
-    return ops.decode_nms_batch(l.detach().float().contiguous(), c.detach().float().contiguous(), pri, wh, top_k, min_score, iou_threshold)
+    return ops.decode_nms_batch(l.detach().float().contiguous(), c.detach().float().contiguous(), pri, wh, top_k, min_score, iou_threshold,
+                                nms, sigma, keep_score)
 
 
-def inference_batch(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=0.45):
+def inference_batch(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5, keep_score=None):
     """Batched `inference`: l (B,8732,4), c (B,8732,21), sizes = B (img_w, img_h)
     pairs or a (B,2) tensor.  `inference_batch_padded` + ONE host sync (the counts) for the whole batch.  Returns a list of
     B tuples (boxes (K_i,4), classes (K_i,), probs (K_i,)); an image without detections gives ([], [], [])."""
-    boxes, classes, probs, ids, count = inference_batch_padded(l, c, sizes, top_k, min_score, iou_threshold)
+    boxes, classes, probs, ids, count = inference_batch_padded(l, c, sizes, top_k, min_score, iou_threshold, nms, sigma, keep_score)
     out = []
     for i, k in enumerate(count.tolist()):
         out.append(([], [], []) if k == 0 else (boxes[i, :k], classes[i, :k], probs[i, :k]))

@@ -11,6 +11,8 @@
 //                      the sort is a scatter; all classes and candidates in parallel
 //   D4 nms             block per class, greedy in sorted order, 64 rows at a time: suppression words by
 //                      wave ballot, in-chunk resolve by v_readlane, removed bitset in LDS
+//   D4s soft_nms       (in place of D4 for the Soft-NMS decode) block per class, sequential arg-max picks over live scores kept in
+//                      LDS, each pick decaying the scores of the boxes it overlaps; same output layout as D4
 //   D5 topk_emit       class-major offsets and compact list of the kept boxes (first phase of the same block), then:
 //                      if more than top_k survive: radix select of the top_k-th probability, ties in
 //                      class-major order, rank of the selected entries in LDS; scale boxes by (w,h,w,h)
@@ -536,6 +538,110 @@ __global__ __launch_bounds__(NB_T) void topk_emit_kernel(TopkArgs a) {
 }
 
 __global__ void set_wh_kernel(float* wh, float w, float h) { wh[0] = w; wh[1] = h; }
+__global__ void zero_counts_kernel(int32_t* cnt, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) cnt[i] = 0;
+}
+
+// D4s  Soft-NMS (Bodla et al. 2017) of one class of one image, the second suppression rule beside nms_kernel: a pick lowers the
+// scores of the boxes it overlaps instead of deleting them, so the order of the picks is only known as they are made -- a sequential
+// arg-max loop, not the bit-mask kernel.  The rule, with sorted position j as the candidate's name:
+//   live score s[j] = probability; repeat at most min(n, max_picks) times:
+//     pick the live candidate with the largest s, ties to the lower j (max of the 64-bit key  score bits << 32 | ~j,  the idiom of
+//     decode_compact); stop if s < keep_score; emit (j, s); for every other live b:  s[b] = s[b] * w,
+//       linear    w = iou > thr ? 1 - iou : 1        gaussian    w = expf(-(iou * iou) / sigma)        w = 1 where iou is not finite,
+//     iou = iou_boxes(picked, b) (the contraction-free sequence of the hard rule, IEEE division); b dies once s[b] < keep_score.
+// max_picks = top_k picks per class are enough: decay only lowers scores, so the picked scores of a class never increase, and the
+// cross-class top-k (D5) can take from a class no more than its first top_k picks.
+// Output in nms_kernel's layout (kept_pos / kept_prob / kept_cnt), entries in pick order, kept_prob = the decayed scores.
+//
+// Block per (class, image).  The live scores stay in LDS (4 * P bytes; 0 = dead or picked: a live score is >= keep_score >= 1e-6, and
+// a candidate below keep_score can never be emitted, so it starts dead).  One fused pass per pick: every thread walks its strided
+// candidates, applies the decay of pick k and carries the best key -- and that candidate's box -- for pick k + 1; wave max by
+// shuffles, then the lane that owns the wave's best puts key and box into the wave's slot, and after ONE barrier every thread reads
+// the NT / 64 slots (LDS broadcast) and has the picked box: no second arg-max pass and no global load on the pick-to-pick path.  The
+// slots alternate between two sets by pick parity, which is what makes the one barrier enough.  The box areas are recomputed from
+// the box in registers (three operations, the same bits every time) instead of being stored beside it.
+// Bounds: n is clamped to P, j < n comes from keys built here, and at most min(n, max_picks) <= P entries are written per class.
+template <int NT, int METHOD>
+__global__ __launch_bounds__(NT) void soft_nms_kernel(const float* __restrict__ s_boxes, const float* __restrict__ s_prob,
+                                                        const int32_t* __restrict__ cand_cnt, int P, float thr, float sigma, float keep_score,
+                                                        int max_picks, int32_t* __restrict__ kept_pos, uint32_t* __restrict__ kept_prob,
+                                                        int32_t* __restrict__ kept_cnt) {
+    constexpr int NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) float live_s[];             // [P]
+    __shared__ uint64_t slot_key[2][NW];
+    __shared__ __attribute__((aligned(16))) float slot_box[2][NW][4];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const size_t img = blockIdx.z, C1 = gridDim.x;
+    s_boxes += (img * C1 + c) * P * 4; s_prob += (img * C1 + c) * P; cand_cnt += img * (C1 + 1);
+    kept_pos += (img * C1 + c) * P; kept_prob += (img * C1 + c) * P; kept_cnt += img * (C1 + 1);
+    const int n = max(0, min(cand_cnt[c], P));
+    const int n_picks = min(n, max_picks);
+    uint64_t best = 0;
+    f32x4 bbox = {0.f, 0.f, 0.f, 0.f};
+    for (int b = tid; b < n; b += NT) {
+        float s = s_prob[b];
+        if (!(s >= keep_score)) s = 0.f;
+        live_s[b] = s;
+        const uint64_t key = s > 0.f ? ((uint64_t)__float_as_uint(s) << 32) | (uint64_t)(0xffffffffu - (uint32_t)b) : 0ull;
+        if (key > best) {
+            best = key;
+            bbox = *reinterpret_cast<const f32x4*>(s_boxes + (size_t)b * 4);
+        }
+    }
+    int k = 0;
+    for (; k < n_picks; ++k) {
+        // ---- arg-max of the keys the pass before left in the threads ------------------------------------
+        const int par = k & 1;
+        uint64_t wmax = best;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned lo = __shfl_xor((unsigned)wmax, o, 64), hi = __shfl_xor((unsigned)(wmax >> 32), o, 64);
+            const uint64_t other = ((uint64_t)hi << 32) | lo;
+            wmax = other > wmax ? other : wmax;
+        }
+        if (wmax == 0ull ? lane == 0 : best == wmax) {            // keys of live candidates are unique: exactly one lane
+            slot_key[par][wave] = wmax;
+            *reinterpret_cast<f32x4*>(slot_box[par][wave]) = bbox;
+        }
+        __syncthreads();
+        uint64_t gkey = slot_key[par][0];
+        int gw = 0;
+#pragma unroll
+        for (int w = 1; w < NW; ++w) {
+            const uint64_t kw = slot_key[par][w];
+            if (kw > gkey) { gkey = kw; gw = w; }
+        }
+        if (gkey == 0ull) break;                                    // uniform: nothing live is left (every live score is >= keep_score)
+        const f32x4 a = *reinterpret_cast<const f32x4*>(slot_box[par][gw]);
+        const int j = (int)(0xffffffffu - (uint32_t)gkey);
+        if (tid == 0) {
+            kept_pos[k] = j;
+            kept_prob[k] = (uint32_t)(gkey >> 32);
+        }
+        if (k + 1 == n_picks) { ++k; break; }                       // uniform: the last pick needs no decay pass
+        // ---- decay by pick k, best key for pick k + 1 ----------------------------------------------------------
+        best = 0;
+#pragma unroll 4
+        for (int b = tid; b < n; b += NT) {
+            const float s = live_s[b];
+            const f32x4 bx = *reinterpret_cast<const f32x4*>(s_boxes + (size_t)b * 4);
+            const float iou = iou_boxes(a, bx);
+            float w;
+            if (METHOD == 1) w = iou > thr ? 1.0f - iou : 1.0f;
+            else w = expf(-(iou * iou) / sigma);
+            if (!(fabsf(iou) <= 3.4028235e38f)) w = 1.0f;          // NaN or infinite: no decay
+            float s2 = s * w;                                       // (a dead 0 stays 0: w is finite)
+            if (s2 < keep_score || b == j) s2 = 0.f;
+            live_s[b] = s2;
+            const uint64_t key = s2 > 0.f ? ((uint64_t)__float_as_uint(s2) << 32) | (uint64_t)(0xffffffffu - (uint32_t)b) : 0ull;
+            if (key > best) { best = key; bbox = bx; }
+        }
+    }
+    if (tid == 0) kept_cnt[c] = k;
+}
 
 }  // namespace
 
@@ -545,16 +651,65 @@ extern "C" size_t ssd_decode_nms_batch_workspace(int B, int P, int n_classes) {
 }
 extern "C" size_t ssd_decode_nms_workspace(int P, int n_classes) { return ssd_decode_nms_batch_workspace(1, P, n_classes); }
 
-extern "C" int ssd_decode_nms_batch(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
-                                    int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
-                                    float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes, void* stream) {
+// Soft-NMS: the live scores of a class take 4 * P bytes of LDS beside the kernel's fixed part (wave slots, under 1 KB), and a
+// workgroup may have 160 KB: P <= 40 704 (SSD300: 35 KB, SSD512: 98 KB).  Checked, with the rule's parameters, before any launch.
+constexpr size_t SOFT_NMS_LDS_MAX = 160 * 1024 - 1024;
+static bool soft_nms_args_ok(int P, int method, float iou_threshold, float sigma, float keep_score, int max_picks) {
+    if (method != 1 && method != 2) return false;
+    if (!(sigma > 0.f) || !(sigma <= 3.4028235e38f)) return false;
+    if (!(keep_score >= 1e-6f && keep_score <= 1.f) || !(iou_threshold >= 0.f && iou_threshold <= 1.f)) return false;
+    if (max_picks <= 0 || max_picks > 4096) return false;
+    return (size_t)P * 4 <= SOFT_NMS_LDS_MAX;
+}
+
+// 1024 threads where few workgroups run (a single image: latency), 512 for batches: the split of the hard rule's kernel.
+static int launch_soft_nms(const float* s_boxes, const float* s_prob, const int32_t* cand_cnt, int B, int C1, int P, int method,
+                           float iou_threshold, float sigma, float keep_score, int max_picks, int32_t* kept_pos, uint32_t* kept_prob,
+                           int32_t* kept_cnt, hipStream_t st) {
+    const size_t lds = (size_t)P * 4;
+    if (lds > 48 * 1024) {
+        static std::atomic<unsigned long long> raised{0};
+        int dev;
+        if (ssd_attr_needed(raised, dev)) {
+            const void* fns[4] = {reinterpret_cast<const void*>(soft_nms_kernel<1024, 1>), reinterpret_cast<const void*>(soft_nms_kernel<1024, 2>),
+                                  reinterpret_cast<const void*>(soft_nms_kernel<512, 1>), reinterpret_cast<const void*>(soft_nms_kernel<512, 2>)};
+            for (const void* f : fns)
+                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SOFT_NMS_LDS_MAX) != hipSuccess) return SSD_ERR_LAUNCH;
+            ssd_attr_done(raised, dev);
+        }
+    }
+    const bool wide = (size_t)C1 * B <= 128;
+    const dim3 grid(C1, 1, B);
+#define SSD_SOFT_NMS_LAUNCH(NT, M)                                                                                                     \
+    hipLaunchKernelGGL((soft_nms_kernel<NT, M>), grid, dim3(NT), lds, st, s_boxes, s_prob, cand_cnt, P, iou_threshold, sigma, keep_score, \
+                       max_picks, kept_pos, kept_prob, kept_cnt)
+    if (wide) { if (method == 1) SSD_SOFT_NMS_LAUNCH(1024, 1); else SSD_SOFT_NMS_LAUNCH(1024, 2); }
+    else      { if (method == 1) SSD_SOFT_NMS_LAUNCH(512, 1);  else SSD_SOFT_NMS_LAUNCH(512, 2); }
+#undef SSD_SOFT_NMS_LAUNCH
+    SSD_CHECK_LAUNCH();
+    return SSD_OK;
+}
+
+// D1, D3, then D4 (method 0: the greedy rule, nms_kernel) or D4s (method 1 / 2: Soft-NMS, soft_nms_kernel), then D5.
+static int decode_nms_batch_impl(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
+                                 int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
+                                 float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes, void* stream,
+                                 int method, float sigma, float keep_score) {
     if (!l_ || !c_ || !priors_cxcywh || !img_wh || !boxes || !classes || !probs || !prior_ids || !count || !workspace) return SSD_ERR_NULL;
     if (B <= 0 || B > 65535 || P <= 0 || P > 100000 || n_classes < 2 || n_classes > 256 || top_k <= 0 || top_k > 4096) return SSD_ERR_BAD_SHAPE;
+    if (method != 0 && !soft_nms_args_ok(P, method, iou_threshold, sigma, keep_score, top_k)) return SSD_ERR_BAD_SHAPE;
     if (!ssd_aligned16(l_) || !ssd_aligned16(priors_cxcywh) || !ssd_aligned16(boxes) || !ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
     if (workspace_bytes < ssd_decode_nms_batch_workspace(B, P, n_classes)) return SSD_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const NmsWs w = carve(workspace, P, n_classes, B);
     const int C1 = n_classes - 1;
+    // The candidate counters of decode_compact.  The Soft-NMS decode clears them with a kernel: it is replayed from captured graphs, and a
+    // memset node of this size was seen to complete only in part against the work in front of it on replay -- with
+    // counters left over, decode_compact and rank_scatter index past their arrays.  The hard rule's launches stay as they were.
+    if (method != 0) {
+        hipLaunchKernelGGL(zero_counts_kernel, dim3(ssd_cdiv(n_classes * B, 256)), dim3(256), 0, st, w.cand_cnt, n_classes * B);
+        SSD_CHECK_LAUNCH();
+    } else
     if (hipMemsetAsync(w.cand_cnt, 0, (size_t)n_classes * 4 * B, st) != hipSuccess) return SSD_ERR_LAUNCH;     // the candidate counters of decode_compact
     {
         // priors per block: as many as keep the staged rows within 48 KB (256 up to C = 47, C = 21 as always), 64 beyond C = 95
@@ -584,33 +739,39 @@ extern "C" int ssd_decode_nms_batch(const float* l_, const float* c_, const floa
     }
     hipLaunchKernelGGL(rank_scatter_kernel, dim3(ssd_cdiv(P, 256), C1, B), dim3(256), 0, st, w.keys, w.cand_cnt, w.boxes, P, w.s_boxes, w.s_prob, w.s_idx);
     SSD_CHECK_LAUNCH();
-    // Block size and LDS by batch: a single image is a latency problem (20 workgroups on 256 CUs: 16 waves each, 64-row chunks whatever
-    // the candidate count); a batch is a throughput problem -- 8-wave workgroups with a 37 KB chunk buffer fit four to a CU, so up to
-    // 1024 (image, class) problems are resident at once instead of two rounds of 512 (64-row chunks up to 4608 candidates per class).
-    const int nwcap = (P + 63) / 64;
-    const bool wide = (size_t)C1 * B <= 128;
-    int chunk_words = wide ? 64 * nwcap : (32 * nwcap > 4608 ? 32 * nwcap : 4608);
-    const int cap_words = 140 * 1024 / 8 - nwcap;                  // (SSD512's 24564 priors: 64-row chunks up to 4 480 candidates of a class)
-    if (chunk_words > cap_words) chunk_words = cap_words;
-    if (chunk_words < 32 * nwcap) return SSD_ERR_BAD_SHAPE;
-    const size_t lds = (size_t)(nwcap + chunk_words) * 8;
-    if (lds > 48 * 1024) {
-        static std::atomic<unsigned long long> raised{0};     // one bit per device (common.h): the attribute belongs to (kernel, device)
-        int dev;
-        if (ssd_attr_needed(raised, dev)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-                return SSD_ERR_LAUNCH;
-            ssd_attr_done(raised, dev);
+    if (method != 0) {
+        const int rc = launch_soft_nms(w.s_boxes, w.s_prob, w.cand_cnt, B, C1, P, method, iou_threshold, sigma, keep_score, top_k, w.kept_pos,
+                                       w.kept_prob, w.kept_cnt, st);
+        if (rc != SSD_OK) return rc;
+    } else {
+        // Block size and LDS by batch: a single image is a latency problem (20 workgroups on 256 CUs: 16 waves each, 64-row chunks whatever
+        // the candidate count); a batch is a throughput problem -- 8-wave workgroups with a 37 KB chunk buffer fit four to a CU, so up to
+        // 1024 (image, class) problems are resident at once instead of two rounds of 512 (64-row chunks up to 4608 candidates per class).
+        const int nwcap = (P + 63) / 64;
+        const bool wide = (size_t)C1 * B <= 128;
+        int chunk_words = wide ? 64 * nwcap : (32 * nwcap > 4608 ? 32 * nwcap : 4608);
+        const int cap_words = 140 * 1024 / 8 - nwcap;                  // (SSD512's 24564 priors: 64-row chunks up to 4 480 candidates of a class)
+        if (chunk_words > cap_words) chunk_words = cap_words;
+        if (chunk_words < 32 * nwcap) return SSD_ERR_BAD_SHAPE;
+        const size_t lds = (size_t)(nwcap + chunk_words) * 8;
+        if (lds > 48 * 1024) {
+            static std::atomic<unsigned long long> raised{0};     // one bit per device (common.h): the attribute belongs to (kernel, device)
+            int dev;
+            if (ssd_attr_needed(raised, dev)) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+                    hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
+                    return SSD_ERR_LAUNCH;
+                ssd_attr_done(raised, dev);
+            }
         }
+        if (wide)
+            hipLaunchKernelGGL(nms_kernel<1024>, dim3(C1, 1, B), dim3(1024), lds, st, w.s_boxes, w.s_prob, w.cand_cnt, P, iou_threshold, chunk_words, w.kept_pos,
+                               w.kept_prob, w.kept_cnt);
+        else
+            hipLaunchKernelGGL(nms_kernel<512>, dim3(C1, 1, B), dim3(512), lds, st, w.s_boxes, w.s_prob, w.cand_cnt, P, iou_threshold, chunk_words, w.kept_pos,
+                               w.kept_prob, w.kept_cnt);
+        SSD_CHECK_LAUNCH();
     }
-    if (wide)
-        hipLaunchKernelGGL(nms_kernel<1024>, dim3(C1, 1, B), dim3(1024), lds, st, w.s_boxes, w.s_prob, w.cand_cnt, P, iou_threshold, chunk_words, w.kept_pos,
-                           w.kept_prob, w.kept_cnt);
-    else
-        hipLaunchKernelGGL(nms_kernel<512>, dim3(C1, 1, B), dim3(512), lds, st, w.s_boxes, w.s_prob, w.cand_cnt, P, iou_threshold, chunk_words, w.kept_pos,
-                           w.kept_prob, w.kept_cnt);
-    SSD_CHECK_LAUNCH();
     const int kp_cap = 16384;                                    // 64 KB of probability bits beside the 2 * top_k selection words
     {
         static std::atomic<unsigned long long> raised{0};
@@ -627,18 +788,63 @@ extern "C" int ssd_decode_nms_batch(const float* l_, const float* c_, const floa
     return SSD_OK;
 }
 
+extern "C" int ssd_decode_nms_batch(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
+                                    int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
+                                    float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes, void* stream) {
+    return decode_nms_batch_impl(l_, c_, priors_cxcywh, img_wh, B, P, n_classes, min_score, iou_threshold, top_k, boxes, classes, probs,
+                                 prior_ids, count, workspace, workspace_bytes, stream, 0, 0.f, 0.f);
+}
+
+extern "C" int ssd_decode_nms_batch_soft(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
+                                         int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
+                                         float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes,
+                                         void* stream, int method, float sigma, float keep_score) {
+    if (method != 1 && method != 2) return SSD_ERR_BAD_SHAPE;
+    return decode_nms_batch_impl(l_, c_, priors_cxcywh, img_wh, B, P, n_classes, min_score, iou_threshold, top_k, boxes, classes, probs,
+                                 prior_ids, count, workspace, workspace_bytes, stream, method, sigma, keep_score);
+}
+
 // one image, image size passed by value (kept in the last 256 bytes of the workspace)
-extern "C" int ssd_decode_nms(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
-                              float min_score, float iou_threshold, int top_k, float img_w, float img_h, float* boxes,
-                              int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count, void* workspace,
-                              size_t workspace_bytes, void* stream) {
+static int decode_nms_impl(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
+                           float min_score, float iou_threshold, int top_k, float img_w, float img_h, float* boxes,
+                           int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count, void* workspace,
+                           size_t workspace_bytes, void* stream, int method, float sigma, float keep_score) {
     if (!workspace) return SSD_ERR_NULL;
     const size_t need = ssd_decode_nms_batch_workspace(1, P, n_classes);
     if (need == 0) return SSD_ERR_BAD_SHAPE;
+    if (method != 0 && !soft_nms_args_ok(P, method, iou_threshold, sigma, keep_score, top_k)) return SSD_ERR_BAD_SHAPE;
     if (workspace_bytes < need) return SSD_ERR_WORKSPACE;
     float* wh = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + need - 256);
     hipLaunchKernelGGL(set_wh_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, wh, img_w, img_h);
     SSD_CHECK_LAUNCH();
-    return ssd_decode_nms_batch(l_, c_, priors_cxcywh, wh, 1, P, n_classes, min_score, iou_threshold, top_k, boxes, classes, probs,
-                                prior_ids, count, workspace, workspace_bytes, stream);
+    return decode_nms_batch_impl(l_, c_, priors_cxcywh, wh, 1, P, n_classes, min_score, iou_threshold, top_k, boxes, classes, probs,
+                                 prior_ids, count, workspace, workspace_bytes, stream, method, sigma, keep_score);
+}
+
+extern "C" int ssd_decode_nms(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
+                              float min_score, float iou_threshold, int top_k, float img_w, float img_h, float* boxes,
+                              int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    return decode_nms_impl(l_, c_, priors_cxcywh, P, n_classes, min_score, iou_threshold, top_k, img_w, img_h, boxes, classes, probs,
+                           prior_ids, count, workspace, workspace_bytes, stream, 0, 0.f, 0.f);
+}
+
+extern "C" int ssd_decode_nms_soft(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
+                                   float min_score, float iou_threshold, int top_k, float img_w, float img_h, float* boxes,
+                                   int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count, void* workspace,
+                                   size_t workspace_bytes, void* stream, int method, float sigma, float keep_score) {
+    if (method != 1 && method != 2) return SSD_ERR_BAD_SHAPE;
+    return decode_nms_impl(l_, c_, priors_cxcywh, P, n_classes, min_score, iou_threshold, top_k, img_w, img_h, boxes, classes, probs,
+                           prior_ids, count, workspace, workspace_bytes, stream, method, sigma, keep_score);
+}
+
+extern "C" int ssd_soft_nms_sorted(const float* s_boxes, const float* s_prob, const int32_t* cand_cnt, int B, int C1, int P, int method,
+                                   float iou_threshold, float sigma, float keep_score, int max_picks, int32_t* kept_pos, float* kept_prob,
+                                   int32_t* kept_cnt, void* stream) {
+    if (!s_boxes || !s_prob || !cand_cnt || !kept_pos || !kept_prob || !kept_cnt) return SSD_ERR_NULL;
+    if (B <= 0 || B > 65535 || C1 <= 0 || C1 > 255 || P <= 0 || P > 100000) return SSD_ERR_BAD_SHAPE;
+    if (!soft_nms_args_ok(P, method, iou_threshold, sigma, keep_score, max_picks)) return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(s_boxes)) return SSD_ERR_ALIGN;
+    return launch_soft_nms(s_boxes, s_prob, cand_cnt, B, C1, P, method, iou_threshold, sigma, keep_score, max_picks, kept_pos,
+                           reinterpret_cast<uint32_t*>(kept_prob), kept_cnt, (hipStream_t)stream);
 }

@@ -855,8 +855,22 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
     return dict(losses=losses, obj=obj, cls=cls, dloc=dloc, dconf=dconf)
 
 
-def decode_nms(l_, c_, priors_cxcywh, img_w, img_h, top_k=200, min_score=0.2, iou_threshold=0.45):
-    """-> (boxes (top_k,4), classes (top_k,) i64, probs (top_k,), prior_ids (top_k,) i32, count (1,) i32), all device."""
+NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}
+
+
+def nms_method(nms):
+    """0 / 1 / 2 for "hard" / "linear" / "gaussian" (the `method` of the C ABI); ValueError for anything else."""
+    try:
+        return NMS_METHODS[nms]
+    except (KeyError, TypeError):
+        raise ValueError(f"nms must be 'hard', 'linear' or 'gaussian', not {nms!r}") from None
+
+
+def decode_nms(l_, c_, priors_cxcywh, img_w, img_h, top_k=200, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5,
+               keep_score=None):
+    """-> (boxes (top_k,4), classes (top_k,) i64, probs (top_k,), prior_ids (top_k,) i32, count (1,) i32), all device.
+    nms = "linear" / "gaussian": Soft-NMS (probs are the decayed scores; keep_score None = min_score)."""
+    method = nms_method(nms)
     _req(l_, "l_"); _req(c_, "c_"); _req(priors_cxcywh, "priors")
     p, ncls = c_.shape
     if tuple(l_.shape) != (p, 4) or tuple(priors_cxcywh.shape) != (p, 4):
@@ -869,15 +883,25 @@ def decode_nms(l_, c_, priors_cxcywh, img_w, img_h, top_k=200, min_score=0.2, io
     probs = torch.zeros((top_k,), device=dev, dtype=torch.float32)
     ids = torch.zeros((top_k,), device=dev, dtype=torch.int32)
     count = torch.zeros((1,), device=dev, dtype=torch.int32)
+    if method != 0:
+        check(lib.ssd_decode_nms_soft(l_.data_ptr(), c_.data_ptr(), priors_cxcywh.data_ptr(), p, ncls, float(min_score),
+                                      float(iou_threshold), int(top_k), float(img_w), float(img_h), boxes.data_ptr(),
+                                      classes.data_ptr(), probs.data_ptr(), ids.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      _stream(), method, float(sigma), float(min_score if keep_score is None else keep_score)),
+              "decode_nms_soft")
+        return boxes, classes, probs, ids, count
     check(lib.ssd_decode_nms(l_.data_ptr(), c_.data_ptr(), priors_cxcywh.data_ptr(), p, ncls, float(min_score),
                              float(iou_threshold), int(top_k), float(img_w), float(img_h), boxes.data_ptr(), classes.data_ptr(),
                              probs.data_ptr(), ids.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "decode_nms")
     return boxes, classes, probs, ids, count
 
 
-def decode_nms_batch(l, c, priors_cxcywh, img_wh, top_k=200, min_score=0.2, iou_threshold=0.45):
+def decode_nms_batch(l, c, priors_cxcywh, img_wh, top_k=200, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5,
+                     keep_score=None):
     """l (B,P,4), c (B,P,C), img_wh (B,2) device floats -> (boxes (B,top_k,4), classes (B,top_k) i64, probs (B,top_k),
-    prior_ids (B,top_k) i32, count (B,) i32), all on the device, one launch set, no host sync."""
+    prior_ids (B,top_k) i32, count (B,) i32), all on the device, one launch set, no host sync.
+    nms = "linear" / "gaussian": Soft-NMS (probs are the decayed scores; keep_score None = min_score)."""
+    method = nms_method(nms)
     _req(l, "l"); _req(c, "c"); _req(priors_cxcywh, "priors"); _req(img_wh, "img_wh")
     b, p, ncls = c.shape
     if tuple(l.shape) != (b, p, 4) or tuple(priors_cxcywh.shape) != (p, 4) or tuple(img_wh.shape) != (b, 2):
@@ -890,6 +914,13 @@ def decode_nms_batch(l, c, priors_cxcywh, img_wh, top_k=200, min_score=0.2, iou_
     probs = torch.zeros((b, top_k), device=dev, dtype=torch.float32)
     ids = torch.zeros((b, top_k), device=dev, dtype=torch.int32)
     count = torch.zeros((b,), device=dev, dtype=torch.int32)
+    if method != 0:
+        check(lib.ssd_decode_nms_batch_soft(l.data_ptr(), c.data_ptr(), priors_cxcywh.data_ptr(), img_wh.data_ptr(), b, p, ncls,
+                                            float(min_score), float(iou_threshold), int(top_k), boxes.data_ptr(), classes.data_ptr(),
+                                            probs.data_ptr(), ids.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+                                            method, float(sigma), float(min_score if keep_score is None else keep_score)),
+              "decode_nms_batch_soft")
+        return boxes, classes, probs, ids, count
     check(lib.ssd_decode_nms_batch(l.data_ptr(), c.data_ptr(), priors_cxcywh.data_ptr(), img_wh.data_ptr(), b, p, ncls,
                                    float(min_score), float(iou_threshold), int(top_k), boxes.data_ptr(), classes.data_ptr(),
                                    probs.data_ptr(), ids.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
