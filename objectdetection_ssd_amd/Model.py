@@ -13,7 +13,9 @@ L2-norm kernels) through one `torch.autograd.Function`.
 from __future__ import annotations
 
 import numbers
-from typing import Dict, List, Optional
+from collections import namedtuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -130,6 +132,63 @@ def _cat_flat(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.cat((a, b))
 
 
+@dataclass(frozen=True)
+class _Layer:
+    """A `conv` or `head` op as the engine's one convolution-layer path sees it, built once per op.  A head is a 3x3 / pad 1 convolution
+    without ReLU whose filter is two parameter tensors stacked (loc rows, then conf rows) and whose output rows are padded to 32."""
+    key: str                      # op["p"]: weight-cache key and profile label
+    weights: Tuple[str, ...]      # parameter names: one filter, or a head's (_bb, _cl) pair ...
+    biases: Tuple[str, ...]
+    rows0: int                    # ... whose first tensor has this many output rows
+    x: str
+    y: Optional[str]              # the activation a conv produces; a head's output goes to the packed head list
+    co: int
+    co_pad: int                   # leading dimension of the output and of an f32 dy (conv: co; head: pad32(co))
+    ld16: int                     # leading dimension of a bf16 dy (conv: co; head: pad64(co))
+    conv: Tuple[int, int, int, int, int]      # ci, kernel size, stride, padding, dilation
+    relu: bool
+    head: bool
+    first_dx: bool                # the last reader of its input: in the backward the first to deliver that input's gradient
+
+    def geom(self, bs: int, h: int, w: int):
+        return ops.make_geom(bs, h, w, self.conv[0], self.co, *self.conv[1:])
+
+    def filter(self, P) -> tuple:
+        return tuple(P[n] for n in self.weights)
+
+    def bias(self, P) -> torch.Tensor:
+        b = [P[n].detach() for n in self.biases]
+        return b[0] if len(b) == 1 else _cat_flat(*b)
+
+    def wanted(self, need) -> bool:
+        return any(need[n] for n in self.weights + self.biases)
+
+    def hand(self, grads, dw, db) -> None:
+        """The layer's (dw, db) to its parameters' entries of the gradient table: a head's rows split into loc and conf."""
+        if len(self.weights) == 1:
+            grads[self.weights[0]], grads[self.biases[0]] = dw, db
+        else:
+            r = self.rows0
+            grads[self.weights[0]], grads[self.weights[1]] = dw[:r], dw[r:]
+            grads[self.biases[0]], grads[self.biases[1]] = db[:r], db[r:]
+
+
+def _stacked(tensors) -> torch.Tensor:
+    """The filter of a layer as one OIHW tensor (a head's loc and conf rows stacked)."""
+    return tensors[0] if len(tensors) == 1 else torch.cat(list(tensors), 0)
+
+
+# What `_Engine._path` answers for one layer:
+#   kind        "b16" (csrc/conv_bf16.hip on bf16 tensors) | "wino" (Winograd F(4x4) / F(2x2)) | "x31" (1x1 limb GEMMs) | "direct" (igemm)
+#   cast16      b16: the input is an f32 tensor and the layer (a head) runs on a bf16 copy of it; its dx goes back as f32
+#   adj         wino, training: the backward filter is laid out for the adjoint data gradient
+#   keep        wino, training: the forward keeps its F(4x4) input planes for the Winograd weight gradient
+#   bits        wino, training: the input transform also leaves the ReLU mask of its input as bits
+#   pool        wino: the 2x2 / stride-2 pool op fused into the output transform, or None
+#   wino_wgrad  the weight gradient runs in the Winograd domain (else: the fused direct kernels, or the path's own)
+_Path = namedtuple("_Path", "kind cast16 adj keep bits pool wino_wgrad", defaults=(False, False, False, False, None, False))
+
+
 class _Elided:
     """Stands in the activation table for a tensor that a fused kernel consumed without writing it: shape only.  In the backward it
     takes the ReLU-mask slot of its pool, which then gates by the pooled output (`maxpool_bwd(..., y_gate=)`)."""
@@ -212,6 +271,19 @@ class _Engine:
                     and op["relu"] and op["co"] % 4 == 0):
                 self.pool_after[op["y"]] = readers[0]
         self._conv_of = {o["y"]: o for o in self.ops if o["op"] == "conv"}      # producer of an activation, where that is a convolution
+        self.layers: Dict[str, _Layer] = {}       # op["p"] -> description of every conv / head op
+        for op in self.ops:
+            if op["op"] not in ("conv", "head"):
+                continue
+            p, head = op["p"], op["op"] == "head"
+            co = op["a"] * (4 + n_conf) if head else op["co"]
+            self.layers[p] = _Layer(
+                key=p, x=op["x"], y=None if head else op["y"], head=head, relu=not head and op["relu"],
+                weights=(p + "_bb.weight", p + "_cl.weight") if head else (p + ".weight",),
+                biases=(p + "_bb.bias", p + "_cl.bias") if head else (p + ".bias",),
+                rows0=4 * op["a"] if head else co, co=co, co_pad=ops.pad32(co) if head else co, ld16=ops.pad64(co) if head else co,
+                conv=(op["ci"], 3, 1, 1, 1) if head else (op["ci"], op["k"], op["s"], op["pad"], op["dil"]),
+                first_dx=[o for o in self.ops if o["x"] == op["x"]][-1] is op)
         self.grad_sink = None     # callable(name, gradient): called during backward the moment a parameter's gradient is ready
         self.grad_out = None      # callable(names) -> flat f32 tensor or None: where the gradient of these consecutive parameters is to be written
         self.sink_owns_grads = False   # True (ddp.py): gradients live in the listener's buffer, autograd is handed None for them
@@ -274,17 +346,17 @@ class _Engine:
         return self.batch_weights and not self.x3 and (not self.bf16 or self.bf16_tensors)
 
     # -- weights ----------------------------------------------------------------------------
-    def _layouts(self, key: str, tensors, co_pad: int, need_bwd: bool):
+    def _layouts(self, L: _Layer, P, need_bwd: bool):
         """Cached [Co_pad][T][Ci] / [Ci][T][Co_pad] copies, refreshed when a parameter changes."""
+        tensors = L.filter(P)
         sig = tuple((t.data_ptr(), t._version) for t in tensors)
-        ent = self._wcache.get(key)
+        ent = self._wcache.get(L.key)
         if ent is None or ent[0] != sig:
-            w = tensors[0] if len(tensors) == 1 else torch.cat(list(tensors), 0)
-            ent = [sig, w.detach().contiguous(), None, None]
-            ent[2] = ops.weight_ohwi(ent[1], co_pad)
-            self._wcache[key] = ent
+            ent = [sig, _stacked(tensors).detach().contiguous(), None, None]
+            ent[2] = ops.weight_ohwi(ent[1], L.co_pad)
+            self._wcache[L.key] = ent
         if need_bwd and ent[3] is None:
-            ent[3] = ops.weight_ihwo(ent[1], co_pad)
+            ent[3] = ops.weight_ihwo(ent[1], L.co_pad)
         if self.x3 or (self.bf16 and not self.bf16_tensors):      # pre-split limb planes of the layouts in use
             if len(ent) == 4:
                 ent += [None, None]
@@ -317,14 +389,15 @@ class _Engine:
         return (self.wino and not self.bf16 and not self.x3 and ops.wino_x3(4, 256) and g.R == 1 and g.S == 1 and g.stride == 1 and g.pad == 0
                 and g.Ci % 32 == 0 and g.Ci >= 256 and g.Co % 32 == 0 and g.Co >= 128 and g.N * g.H * g.W >= self.X31_MIN_PIXELS)
 
-    def _x31_weights(self, key: str, tensors, co_pad: int):
+    def _x31_weights(self, L: _Layer, P):
         """Cached limb planes of a 1x1 filter and of its transpose, refreshed when the parameter changes."""
+        tensors = L.filter(P)
         sig = tuple((t.data_ptr(), t._version) for t in tensors)
-        ent = self._wcache.get("x31:" + key)
+        ent = self._wcache.get("x31:" + L.key)
         if ent is None or ent[0] != sig:
-            wf, wb = ops.conv1x1_weights_x3(tensors[0].detach().contiguous(), co_pad)
+            wf, wb = ops.conv1x1_weights_x3(_stacked(tensors).detach().contiguous(), L.co_pad)
             ent = (sig, wf, wb)
-            self._wcache["x31:" + key] = ent
+            self._wcache["x31:" + L.key] = ent
         return ent[1], ent[2]
 
     def _wino_wgrad_ok(self, g, head: bool) -> bool:
@@ -348,18 +421,19 @@ class _Engine:
         g = ops.make_geom(bs, x.shape[2], x.shape[3], nxt["ci"], nxt["co"], nxt["k"], nxt["s"], nxt["pad"], nxt["dil"])
         return self._wino_ok(g) and g.dil == 1 and g.Co % 4 == 0 and not ops.wino_uses_full(g, 0)
 
-    def _wino_weights(self, key: str, tensors, co_pad: int, adj: bool = False):
+    def _wino_weights(self, L: _Layer, P, adj: bool = False):
         """Cached Winograd-domain filters (U_fwd [16][Co][Ci], U_bwd [16][Ci][co_pad]), refreshed when a parameter changes.
         adj: U_bwd in the adjoint form (the forward transform laid out [Ci][co_pad]) instead of the rotated filter's transform."""
+        tensors = L.filter(P)
         sig = tuple((t.data_ptr(), t._version) for t in tensors) + (ops.wino_x3(4, 256), bool(adj))     # + the GEMM form the filters were laid out for
-        ent = self._wcache.get("wino:" + key)
+        ent = self._wcache.get("wino:" + L.key)
         if ent is None or ent[0] != sig:
-            w = tensors[0] if len(tensors) == 1 else torch.cat(list(tensors), 0)
-            uf, ub = ops.wino_weights(w.detach().contiguous(), co_pad, want_bwd=not adj, mo=self.WINO_TILE)
+            w = _stacked(tensors)
+            uf, ub = ops.wino_weights(w.detach().contiguous(), L.co_pad, want_bwd=not adj, mo=self.WINO_TILE)
             if adj:
-                ub = ops.wino_adj_weights(w.detach().contiguous(), co_pad)
+                ub = ops.wino_adj_weights(w.detach().contiguous(), L.co_pad)
             ent = (sig, uf, ub)
-            self._wcache["wino:" + key] = ent
+            self._wcache["wino:" + L.key] = ent
         return ent[1], ent[2]
 
     def _planes(self, key: str, bwd: bool):
@@ -369,32 +443,76 @@ class _Engine:
         ent = self._wcache.get(key)
         return None if ent is None or len(ent) < 6 else ent[5 if bwd else 4]
 
-    def _t16(self, g, xin) -> bool:
-        """bf16-tensor mode: this convolution runs csrc/conv_bf16.hip (3x3 / stride 1 / pad 1 on a bf16 input, Ci a multiple of 64)."""
-        return (self.bf16 and self.bf16_tensors and g.R == 3 and g.S == 3 and g.stride == 1 and g.dil == 1 and g.pad == 1 and g.Ci % 64 == 0
-                and (xin is None or xin.dtype == torch.bfloat16))
+    def _t16(self, g) -> bool:
+        """bf16-tensor mode: this convolution, given a bf16 input, runs csrc/conv_bf16.hip (3x3 / stride 1 / pad 1, Ci a multiple of 64)."""
+        return self.bf16 and self.bf16_tensors and g.R == 3 and g.S == 3 and g.stride == 1 and g.dil == 1 and g.pad == 1 and g.Ci % 64 == 0
 
-    def _head16(self, op, g) -> bool:
+    def _head16(self, L: _Layer, g) -> bool:
         """bf16-tensor mode: this head, although its input is an f32 tensor, runs csrc/conv_bf16.hip on a bf16 copy of it -- where the map is
         large enough to pay (19x19) and the head is the FIRST to deliver its input's gradient (so that gradient needs neither += nor a
         ReLU mask from the kernel, which writes it as f32)."""
-        if not (self._t16(g, None) and g.H >= 16):
-            return False
-        readers = [o for o in self.ops if o["x"] == op["x"]]
-        return readers[-1] is op
+        return L.head and L.first_dx and self._t16(g) and g.H >= 16
 
-    def _bf16_weights(self, key: str, tensors):
+    def _path(self, L: _Layer, g, x_is_b16: bool, save: bool = True) -> _Path:
+        """THE dispatch decision of a conv / head layer: which kernel family it runs on, given its geometry and whether its input is held
+        in bf16, and the sub-decisions that go with the family (the fields of `_Path`).  The forward records the answer in `aux`, the
+        backward reads it back, the weight table (`_plan`) lays out the filters it names: nothing else looks at the predicates."""
+        if self._t16(g) and (x_is_b16 or self._head16(L, g)):
+            return _Path("b16", cast16=not x_is_b16)
+        if self._wino_ok(g):
+            t4 = self.WINO_TILE == 4
+            wino_wgrad = self._wino_wgrad_ok(g, L.head)
+            # training: the transformed input stays for the weight gradient, which multiplies the same planes
+            keep = save and self.keep_planes and t4 and wino_wgrad
+            if L.head:                                  # no ReLU in front of a head's dx, no pool behind it, no adjoint form
+                return _Path("wino", keep=keep, wino_wgrad=wino_wgrad)
+            # the mask is only ever applied to a post-ReLU input (deliver() in the backward): pool outputs and the image are not gated here
+            bits = keep and self.relu_bits and self.dual_dy and L.x in self.relu_out and g.Co % 32 == 0
+            pool = self.pool_after.get(L.y) if (self.fuse_pool and t4) else None
+            return _Path("wino", adj=save and self._adj_ok(g), keep=keep, bits=bits, pool=pool, wino_wgrad=wino_wgrad)
+        if self._x31_ok(g):
+            return _Path("x31")
+        return _Path("direct")
+
+    def _plan(self, bs: int, h: int, w: int, save: bool = True):
+        """(op, layer, geometry, path) of every conv / head op for a batch of bs images of h x w, without running anything: the map sizes
+        follow from the ops in front, and a tensor is held in bf16 where the path of its producer says so."""
+        hw, b16 = {"x": (h, w)}, {"x": False}
+        for op in self.ops:
+            kind = op["op"]
+            if kind in ("conv", "head"):
+                L = self.layers[op["p"]]
+                g = L.geom(bs, *hw[op["x"]])
+                path = self._path(L, g, b16[op["x"]], save)
+                if kind == "conv":
+                    hw[op["y"]], b16[op["y"]] = (g.Ho, g.Wo), path.kind == "b16"
+                yield op, L, g, path
+            elif kind == "pool":
+                hw[op["y"]] = tuple(ops.pool_out(n, op["k"], op["s"], op["pad"], op["ceil"]) for n in hw[op["x"]])
+                b16[op["y"]] = b16[op["x"]]
+            else:                                       # conv_first (bf16 out in the bf16-tensor mode), l2norm
+                hw[op["y"]] = hw[op["x"]]
+                b16[op["y"]] = (self.bf16 and self.bf16_tensors) if kind == "conv_first" else b16[op["x"]]
+
+    def _table_kind(self, path: _Path) -> Optional[str]:
+        """What the batched weight table lays out for a layer on this path; None: nothing (F(2x2), a tuning aid, is transformed per layer)."""
+        if path.kind == "wino":
+            return None if self.WINO_TILE != 4 else "wino_adj" if path.adj else "wino"
+        return {"b16": "b16", "x31": "x31", "direct": "layout"}[path.kind]
+
+    def _bf16_weights(self, L: _Layer, P):
         """bf16 OHWI (co, 9, ci) and IHWO (ci, 9, pad64(co)) copies of a 3x3 filter (+ the bias padded to a multiple of 4), cached."""
+        tensors = L.filter(P)
         sig = tuple((t.data_ptr(), t._version) for t in tensors)
-        ent = self._wcache.get("b16:" + key)
+        ent = self._wcache.get("b16:" + L.key)
         if ent is None or ent[0] != sig:
-            w = (tensors[0] if len(tensors) == 1 else torch.cat(list(tensors), 0)).detach()
+            w = _stacked(tensors).detach()
             co, ci = int(w.shape[0]), int(w.shape[1])
             wf = w.permute(0, 2, 3, 1).reshape(co, 9, ci).contiguous().to(torch.bfloat16)
             wb = torch.zeros((ci, 9, ops.pad64(co)), device=w.device, dtype=torch.bfloat16)
             wb[:, :, :co] = w.permute(1, 2, 3, 0).reshape(ci, 9, co)
             ent = (sig, wf, wb)
-            self._wcache["b16:" + key] = ent
+            self._wcache["b16:" + L.key] = ent
         return ent[1], ent[2]
 
     def _prepare_weights_batched(self, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> None:
@@ -404,79 +522,49 @@ class _Engine:
         sig = (x.shape[2], x.shape[3]) + self.schedule_key() + tuple(P[n].data_ptr() for n in self.names)
         if self._wtable is None or self._wtable[0] != sig:
             jobs, entries = [], []
-            bs, hw, dev = x.shape[0], {"x": (x.shape[2], x.shape[3])}, x.device
-            b16 = {"x": False}                     # which tensors the forward will hold in bf16 (mirrors the dtype flow of `forward`)
-            for op in self.ops:
-                kind = op["op"]
-                if kind in ("pool", "l2norm"):
-                    b16[op["y"]] = b16[op["x"]]
-                if kind == "conv_first":
-                    b16[op["y"]] = self.bf16 and self.bf16_tensors
-                    hw[op["y"]] = hw[op["x"]]
-                    w = P[op["p"] + ".weight"]
-                    rows = torch.empty((64, 1, 32), device=dev, dtype=torch.float32)
-                    jobs.append(dict(kind=2, w0=w.detach(), co0=64, co=64, ci=3, taps=9, co_pad=64, out_fwd=rows))
-                    entries.append((op["p"], "first", (w,), (rows,)))
-                elif kind == "pool":
-                    h, w_ = hw[op["x"]]
-                    hw[op["y"]] = (ops.pool_out(h, op["k"], op["s"], op["pad"], op["ceil"]), ops.pool_out(w_, op["k"], op["s"], op["pad"], op["ceil"]))
-                elif kind == "l2norm":
-                    hw[op["y"]] = hw[op["x"]]
-                elif kind in ("conv", "head"):
-                    h, w_ = hw[op["x"]]
-                    if kind == "conv":
-                        g = ops.make_geom(bs, h, w_, op["ci"], op["co"], op["k"], op["s"], op["pad"], op["dil"])
-                        hw[op["y"]] = (g.Ho, g.Wo)
-                        tensors, co_pad = (P[op["p"] + ".weight"],), op["co"]
-                    else:
-                        co = op["a"] * (4 + self.n_conf)
-                        g = ops.make_geom(bs, h, w_, op["ci"], co, 3, 1, 1, 1)
-                        tensors, co_pad = (P[op["p"] + "_bb.weight"], P[op["p"] + "_cl.weight"]), ops.pad32(co)
-                    t16 = self._t16(g, None) and (b16[op["x"]] or (kind == "head" and self._head16(op, g)))
-                    if kind == "conv":
-                        b16[op["y"]] = t16
-                    co_all = sum(t.shape[0] for t in tensors)
-                    job = dict(w0=tensors[0].detach(), w1=tensors[1].detach() if len(tensors) > 1 else None, co0=tensors[0].shape[0], co=co_all,
-                               ci=g.Ci, taps=g.R * g.S, co_pad=co_pad)
-                    # bf16-tensor mode: which layers see a bf16 input is decided by the trunk's structure (everything up to pool5, the c_4 head)
-                    if t16:
-                        wf = torch.empty((co_all, 9, g.Ci), device=dev, dtype=torch.bfloat16)
-                        wb = torch.empty((g.Ci, 9, ops.pad64(co_all)), device=dev, dtype=torch.bfloat16)
-                        jobs.append(dict(job, kind=3, co_pad=co_all, pad1=ops.pad64(co_all), out_fwd=wf, out_bwd=wb))
-                        entries.append((op["p"], "b16", tensors, (wf, wb)))
-                    elif kind == "conv" and self._x31_ok(g):
-                        wf = ops.x3_filter_alloc(co_all, g.Ci, dev)
-                        wb = ops.x3_filter_alloc(g.Ci, co_pad, dev)
-                        jobs.append(dict(job, kind=4, out_fwd=wf, out_bwd=wb))
-                        entries.append((op["p"], "x31", tensors, (wf, wb)))
-                    elif self._wino_ok(g) and self.WINO_TILE == 4:
-                        uf = ops.wino_filter_alloc(4, co_all, g.Ci, dev)
-                        ub = ops.wino_filter_alloc(4, g.Ci, co_pad, dev)
-                        adj = kind == "conv" and self._adj_ok(g)
-                        jobs.append(dict(job, kind=0, out_fwd=uf, out_bwd=ub, adj=adj))
-                        entries.append((op["p"], "wino_adj" if adj else "wino", tensors, (uf, ub)))
-                    elif self._wino_ok(g):
-                        continue                               # F(2x2) (a tuning aid): transformed per layer as before
-                    else:
-                        wf = torch.empty((co_pad, g.R * g.S, g.Ci), device=dev, dtype=torch.float32)
-                        wb = torch.empty((g.Ci, g.R * g.S, co_pad), device=dev, dtype=torch.float32)
-                        jobs.append(dict(job, kind=1, out_fwd=wf, out_bwd=wb))
-                        entries.append((op["p"], "layout", tensors, (wf, wb)))
+            bs, dev = x.shape[0], x.device
+            first = self.ops[0]                    # conv_first: its [64][32] rows
+            w = P[first["p"] + ".weight"]
+            rows = torch.empty((64, 1, 32), device=dev, dtype=torch.float32)
+            jobs.append(dict(kind=2, w0=w.detach(), co0=64, co=64, ci=3, taps=9, co_pad=64, out_fwd=rows))
+            entries.append((first["p"], "first", (w,), (rows,)))
+            for _, L, g, path in self._plan(bs, x.shape[2], x.shape[3]):
+                what = self._table_kind(path)
+                if what is None:
+                    continue
+                tensors, co_pad, taps = L.filter(P), L.co_pad, g.R * g.S
+                co_all = sum(t.shape[0] for t in tensors)
+                job = dict(w0=tensors[0].detach(), w1=tensors[1].detach() if len(tensors) > 1 else None, co0=tensors[0].shape[0], co=co_all,
+                           ci=g.Ci, taps=taps, co_pad=co_pad)
+                if what == "b16":
+                    bufs = (torch.empty((co_all, 9, g.Ci), device=dev, dtype=torch.bfloat16),
+                            torch.empty((g.Ci, 9, ops.pad64(co_all)), device=dev, dtype=torch.bfloat16))
+                    job.update(kind=3, co_pad=co_all, pad1=ops.pad64(co_all))
+                elif what == "x31":
+                    bufs = (ops.x3_filter_alloc(co_all, g.Ci, dev), ops.x3_filter_alloc(g.Ci, co_pad, dev))
+                    job.update(kind=4)
+                elif what == "layout":
+                    bufs = (torch.empty((co_pad, taps, g.Ci), device=dev, dtype=torch.float32),
+                            torch.empty((g.Ci, taps, co_pad), device=dev, dtype=torch.float32))
+                    job.update(kind=1)
+                else:
+                    bufs = (ops.wino_filter_alloc(4, co_all, g.Ci, dev), ops.wino_filter_alloc(4, g.Ci, co_pad, dev))
+                    job.update(kind=0, adj=path.adj)
+                jobs.append(dict(job, out_fwd=bufs[0], out_bwd=bufs[1]))
+                entries.append((L.key, what, tensors, bufs))
             self._wtable = (sig, ops.WeightTable(jobs, dev), entries)
         _, table, entries = self._wtable
         table.run()
         for key, what, tensors, bufs in entries:
             lsig = tuple((t.data_ptr(), t._version) for t in tensors)
-            if what == "b16":
-                self._wcache["b16:" + key] = (lsig, bufs[0], bufs[1])
-            elif what in ("wino", "wino_adj"):
-                self._wcache["wino:" + key] = (lsig + (ops.wino_x3(4, 256), what == "wino_adj"), bufs[0], bufs[1])
-            elif what == "x31":
-                self._wcache["x31:" + key] = (lsig, bufs[0], bufs[1])
+            if what == "first":
+                self._wcache[key] = [lsig[0], None, bufs[0], None]
             elif what == "layout":
                 self._wcache[key] = [lsig, None, bufs[0], bufs[1]]
+            elif what in ("b16", "x31"):
+                self._wcache[what + ":" + key] = (lsig, bufs[0], bufs[1])
             else:
-                self._wcache[key] = [lsig[0], None, bufs[0], None]
+                self._wcache["wino:" + key] = (lsig + (ops.wino_x3(4, 256), what == "wino_adj"), bufs[0], bufs[1])
 
     # -- forward ----------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], save: bool):
@@ -573,74 +661,16 @@ class _Engine:
                                              lambda: ops.conv2d_fwd(col, ent[2], bias, g, True, bf16=self.bf16))
                 T["x_col"] = col
                 aux[op["y"]] = g
-            elif kind == "conv":
+            elif kind in ("conv", "head"):
+                L = self.layers[op["p"]]
                 xin = T[op["x"]]
-                g = ops.make_geom(bs, xin.shape[1], xin.shape[2], op["ci"], op["co"], op["k"], op["s"], op["pad"], op["dil"])
-                bias = P[op["p"] + ".bias"].detach()
-                if self._t16(g, xin):
-                    wf16, _ = self._bf16_weights(op["p"], (P[op["p"] + ".weight"],))
-                    T[op["y"]] = self._timed("fwd " + op["p"], "conv3x3_bf16_kernel", ops.conv_flops(g),
-                                             lambda: ops.conv3x3_bf16(xin, wf16, bias, op["co"], op["relu"]))
-                    aux[op["y"]] = g
-                    continue
-                if xin.dtype == torch.bfloat16:                   # boundary of the bf16 trunk (pool5 -> fc6): the kernels below take f32 tensors
-                    xin = T[op["x"] + ":f32"] = ops.cast_f32(xin)
-                if self._wino_ok(g):
-                    uf, _ = self._wino_weights(op["p"], (P[op["p"] + ".weight"],), op["co"], adj=save and self._adj_ok(g))
-                    pl = self.pool_after.get(op["y"]) if (self.fuse_pool and self.WINO_TILE == 4) else None
-                    # training: the transformed input stays for the weight gradient, which multiplies the same planes
-                    keep = save and self.keep_planes and self.WINO_TILE == 4 and self._wino_wgrad_ok(g, False)
-                    # the mask is only ever applied to a post-ReLU input (deliver() below): pool outputs and the image are not gated here
-                    wb = keep and self.relu_bits and self.dual_dy and op["x"] in self.relu_out and g.Co % 32 == 0
-                    pre = aux.pop("preplanes:" + op["x"], None)
-                    if pre is not None:
-                        # the producer of this layer's input left the input planes (and the ReLU bits): GEMMs + output transform only
-                        planes, pbits = pre
-                        if pl is not None:
-                            yp, am = self._timed("fwd " + op["p"], "winograd_3x3", ops.wino_flops(g),
-                                                 lambda: ops.conv2d_fwd_wino_from_planes(planes, uf, bias, g, True, pool_ceil=pl["ceil"], want_argmax=save))
-                            T[op["y"]] = _Elided((bs, g.H, g.W, op["co"]))
-                            T[pl["y"]], aux[pl["y"]] = yp, am
-                        else:
-                            T[op["y"]] = self._timed("fwd " + op["p"], "winograd_3x3", ops.wino_flops(g),
-                                                     lambda: ops.conv2d_fwd_wino_from_planes(planes, uf, bias, g, op["relu"]))
-                        aux[op["y"]] = g
-                        if keep:
-                            aux["planes:" + op["p"]] = planes
-                        if wb and pbits is not None:
-                            aux["bits:" + op["p"]] = pbits
-                        continue
-                    if pl is not None:
-                        res = self._timed("fwd " + op["p"], "winograd_3x3", ops.wino_flops(g),
-                                          lambda: ops.conv2d_fwd_wino_pool(xin, uf, bias, g, pl["ceil"], want_argmax=save, keep_planes=keep,
-                                                                           want_bits=wb))
-                        T[op["y"]] = _Elided((bs, g.H, g.W, op["co"]))      # never materialised: its only reader is the pool
-                        T[pl["y"]], aux[pl["y"]], aux[op["y"]] = res[0], res[1], g
-                        if keep:
-                            aux["planes:" + op["p"]] = res[2]
-                        if wb:
-                            aux["bits:" + op["p"]] = res[3]
-                        continue
-                    res = self._timed("fwd " + op["p"], "winograd_3x3", ops.wino_flops(g),
-                                      lambda: ops.conv2d_fwd_wino(xin, uf, bias, g, op["relu"], keep_planes=keep, want_bits=wb))
-                    T[op["y"]] = res[0] if keep else res
-                    if keep:
-                        aux["planes:" + op["p"]] = res[1]
-                    if wb:
-                        aux["bits:" + op["p"]] = res[2]
-                    aux[op["y"]] = g
-                    continue
-                if self._x31_ok(g):
-                    w3f, _ = self._x31_weights(op["p"], (P[op["p"] + ".weight"],), op["co"])
-                    T[op["y"]] = self._timed("fwd " + op["p"], "gemm_planes_x3_kernel (1x1)", ops.conv_flops(g),
-                                             lambda: ops.conv1x1_fwd_x3(xin, w3f, bias, g, op["relu"]))
-                    aux[op["y"]] = g
-                    continue
-                wf, _ = self._layouts(op["p"], (P[op["p"] + ".weight"],), op["co"], False)
-                T[op["y"]] = self._timed("fwd " + op["p"], ops.igemm_tile(g, 0, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
-                                         lambda: ops.conv2d_fwd_x3(xin, wf, bias, g, op["relu"]) if self.x3 else
-                                         ops.conv2d_fwd(xin, wf, bias, g, op["relu"], bf16=self.bf16, w3=self._planes(op["p"], False)))
-                aux[op["y"]] = g
+                g = L.geom(bs, xin.shape[1], xin.shape[2])
+                path = aux["path:" + L.key] = self._path(L, g, xin.dtype == torch.bfloat16, save)
+                y = self._conv_forward(L, g, path, xin, P, save, T, aux)
+                if L.head:
+                    heads.append((op, y, g))
+                else:
+                    T[op["y"]], aux[op["y"]] = y, g
             elif kind == "pool":
                 if op["y"] in T:                                  # produced by the convolution before it
                     continue
@@ -649,40 +679,67 @@ class _Engine:
                 aux[op["y"]] = am
             elif kind == "l2norm":
                 T[op["y"]] = ops.l2norm_fwd(T[op["x"]], P[op["p"]].detach().reshape(-1))
-            elif kind == "head":
-                xin = T[op["x"]]
-                a = op["a"]
-                co = a * (4 + self.n_conf)
-                g = ops.make_geom(bs, xin.shape[1], xin.shape[2], op["ci"], co, 3, 1, 1, 1)
-                pre = op["p"]
-                bias = _cat_flat(P[pre + "_bb.bias"].detach(), P[pre + "_cl.bias"].detach())
-                if self._head16(op, g) and xin.dtype == torch.float32:
-                    # a head on an f32 tensor outside the bf16 trunk (c_7 on fc7's output): one cast, then the LDS-DMA kernel
-                    xin = T[op["x"] + ":b16"] = ops.cast_bf16(xin)
-                if self._t16(g, xin):
-                    wf16, _ = self._bf16_weights(pre, (P[pre + "_bb.weight"], P[pre + "_cl.weight"]))
-                    ld, co4 = ops.pad32(co), (co + 3) // 4 * 4
-                    out = torch.empty((bs, g.H, g.W, ld), device=xin.device, dtype=torch.float32)      # pad columns are never read
-                    packed = self._timed("fwd " + pre, "conv3x3_bf16_kernel", ops.conv_flops(g),
-                                         lambda: ops.conv3x3_bf16(xin, wf16, bias, co4, False, out=out, out_f32=True, ldo=ld))
-                    heads.append((op, packed, g))
-                    continue
-                if xin.dtype == torch.bfloat16:
-                    xin = T[op["x"] + ":f32"] = T.get(op["x"] + ":f32") if T.get(op["x"] + ":f32") is not None else ops.cast_f32(xin)
-                if self._wino_ok(g):
-                    uf, _ = self._wino_weights(pre, (P[pre + "_bb.weight"], P[pre + "_cl.weight"]), ops.pad32(co))
-                    keep = save and self.keep_planes and self.WINO_TILE == 4 and self._wino_wgrad_ok(g, True)
-                    res = self._timed("fwd " + pre, "winograd_3x3", ops.wino_flops(g),
-                                      lambda: ops.conv2d_fwd_wino(xin, uf, bias, g, False, ld=ops.pad32(co), keep_planes=keep))
-                    if keep:
-                        aux["planes:" + pre] = res[1]
-                    heads.append((op, res[0] if keep else res, g))
-                    continue
-                wf, _ = self._layouts(pre, (P[pre + "_bb.weight"], P[pre + "_cl.weight"]), ops.pad32(co), False)
-                packed = self._timed("fwd " + pre, ops.igemm_tile(g, 0, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
-                                     lambda: ops.conv2d_fwd_x3(xin, wf, bias, g, False, ld=ops.pad32(co)) if self.x3 else
-                                     ops.conv2d_fwd(xin, wf, bias, g, False, ld=ops.pad32(co), bf16=self.bf16, w3=self._planes(pre, False)))
-                heads.append((op, packed, g))
+
+    def _conv_forward(self, L: _Layer, g, path: _Path, xin, P, save, T, aux):
+        """Forward of one convolution layer, trunk or head, on the path `_path` chose -> its output (N, Ho, Wo, L.co_pad), or the `_Elided`
+        stand-in where the pool behind it was fused (the pooled map and its argmax are then stored under the pool's name)."""
+        bias, label = L.bias(P), "fwd " + L.key
+        if path.kind == "b16":
+            if path.cast16:
+                # a head on an f32 tensor outside the bf16 trunk (c_7 on fc7's output): one cast, then the LDS-DMA kernel
+                xin = T[L.x + ":b16"] = ops.cast_bf16(xin)
+            wf16, _ = self._bf16_weights(L, P)
+            if not L.head:
+                return self._timed(label, "conv3x3_bf16_kernel", ops.conv_flops(g), lambda: ops.conv3x3_bf16(xin, wf16, bias, L.co, L.relu))
+            # a head's rows go to the scatter as f32 with its leading dimension
+            out = torch.empty((g.N, g.H, g.W, L.co_pad), device=xin.device, dtype=torch.float32)      # pad columns are never read
+            return self._timed(label, "conv3x3_bf16_kernel", ops.conv_flops(g),
+                               lambda: ops.conv3x3_bf16(xin, wf16, bias, (L.co + 3) // 4 * 4, False, out=out, out_f32=True, ldo=L.co_pad))
+        if xin.dtype == torch.bfloat16:
+            # boundary of the bf16 trunk (pool5 -> fc6): the kernels below take f32 tensors; a copy another reader made is reused
+            xin = T[L.x + ":f32"] = T.get(L.x + ":f32") if T.get(L.x + ":f32") is not None else ops.cast_f32(xin)
+        if path.kind == "wino":
+            uf, _ = self._wino_weights(L, P, adj=path.adj)
+            pl, keep, wb = path.pool, path.keep, path.bits
+            pre = aux.pop("preplanes:" + L.x, None)
+            if pre is not None:
+                # the producer of this layer's input left the input planes (and the ReLU bits): GEMMs + output transform only
+                planes, pbits = pre
+                if pl is not None:
+                    yp, am = self._timed(label, "winograd_3x3", ops.wino_flops(g),
+                                         lambda: ops.conv2d_fwd_wino_from_planes(planes, uf, bias, g, True, pool_ceil=pl["ceil"], want_argmax=save))
+                    y = _Elided((g.N, g.H, g.W, L.co))
+                    T[pl["y"]], aux[pl["y"]] = yp, am
+                else:
+                    y = self._timed(label, "winograd_3x3", ops.wino_flops(g), lambda: ops.conv2d_fwd_wino_from_planes(planes, uf, bias, g, L.relu))
+                if keep:
+                    aux["planes:" + L.key] = planes
+                if wb and pbits is not None:
+                    aux["bits:" + L.key] = pbits
+                return y
+            if pl is not None:
+                res = self._timed(label, "winograd_3x3", ops.wino_flops(g),
+                                  lambda: ops.conv2d_fwd_wino_pool(xin, uf, bias, g, pl["ceil"], want_argmax=save, keep_planes=keep, want_bits=wb))
+                T[pl["y"]], aux[pl["y"]] = res[0], res[1]
+                if keep:
+                    aux["planes:" + L.key] = res[2]
+                if wb:
+                    aux["bits:" + L.key] = res[3]
+                return _Elided((g.N, g.H, g.W, L.co))      # never materialised: its only reader is the pool
+            res = self._timed(label, "winograd_3x3", ops.wino_flops(g),
+                              lambda: ops.conv2d_fwd_wino(xin, uf, bias, g, L.relu, ld=L.co_pad, keep_planes=keep, want_bits=wb))
+            if keep:
+                aux["planes:" + L.key] = res[1]
+            if wb:
+                aux["bits:" + L.key] = res[2]
+            return res[0] if keep else res
+        if path.kind == "x31":
+            w3f, _ = self._x31_weights(L, P)
+            return self._timed(label, "gemm_planes_x3_kernel (1x1)", ops.conv_flops(g), lambda: ops.conv1x1_fwd_x3(xin, w3f, bias, g, L.relu))
+        wf, _ = self._layouts(L, P, False)
+        return self._timed(label, ops.igemm_tile(g, 0, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
+                           lambda: ops.conv2d_fwd_x3(xin, wf, bias, g, L.relu, ld=L.co_pad) if self.x3 else
+                           ops.conv2d_fwd(xin, wf, bias, g, L.relu, ld=L.co_pad, bf16=self.bf16, w3=self._planes(L.key, False)))
 
     def _wgrad_gemm_async(self, main, Y, kept, part, g, ldy, assign):
         """Second half of a Winograd weight gradient on the weight-gradient stream: waits for what `main` has enqueued so far (the dy
@@ -753,6 +810,160 @@ class _Engine:
         # they are enqueued AFTER the group's data-gradient chain, behind the join event.
         deferred = []
         defer = self.defer_tail_wgrad and self.prof is None
+
+        def conv_backward(L, g, path, dy):
+            """Weight and data gradient of one convolution layer, trunk or head, on the path its forward recorded.  dy: a tensor with rows
+            of L.co_pad (b16: L.ld16) columns, or (trunk only) a `PooledGrad` / `AdjPlanesGrad` that stands for one."""
+            nonlocal wgrad_used
+            name, xin, need_w = L.key, T[L.x], L.wanted(need)
+
+            def gout():
+                """where the gradient listener, if any, wants this layer's dw and db written"""
+                return dict(dw_out=self._gout(*L.weights), db_out=self._gout(*L.biases))
+            if path.kind == "b16":
+                # bf16 trunk: nine-tap bf16 weight gradient, LDS-DMA data gradient
+                f32_dx = path.cast16                      # the head ran on a bf16 copy of an f32 tensor: its dx goes back as f32
+                if f32_dx:
+                    xin = T[L.x + ":b16"]
+                if need_w:
+                    L.hand(grads, *self._timed("wgrad " + name, "wgrad3x3_bf16_kernel", ops.conv_flops(g),
+                                               lambda: ops.conv3x3_wgrad_bf16t(xin, dy, g, L.ld16, True, **gout())))
+                _, wb16 = self._bf16_weights(L, P)
+
+                def dgrad16(dx, acc, mask):
+                    if f32_dx and (acc or mask is not None or dx is not None):
+                        raise RuntimeError("a head on a bf16 copy must be the first to deliver its input's gradient")
+                    return self._timed("dgrad " + name, "conv3x3_bf16_kernel", ops.conv_flops(g),
+                                       lambda: ops.conv3x3_bf16(dy, wb16, None, g.Ci, False, flip=True, out=dx, out_f32=f32_dx, relu_mask=mask,
+                                                                accumulate=acc))
+                deliver(L.x, dgrad16)
+                return
+            to_bf16 = xin.dtype == torch.bfloat16         # boundary of the bf16 trunk: this layer ran on the f32 copy, its dx goes back as bf16
+            if to_bf16:
+                xin = T[L.x + ":f32"]
+            full = path.kind == "wino" and ops.wino_uses_full(g, 1)      # the library runs this data gradient as one kernel that reads dy itself
+            kept_planes = aux.get("planes:" + name) is not None
+            # dy rows the plane GEMMs of both gradients can share.  One condition for both kinds: a trunk layer's co_pad is its Co, so
+            # this reads Co % 32 == 0 and Co <= 1024; a head's co_pad = pad32(co) is a multiple of 32 by construction, so for it only
+            # co_pad <= 1024 decides (SSD300 / SSD512, conf widths 2 .. 256: 32 .. 1568).
+            wide = L.co_pad % 32 == 0 and L.co_pad <= 1024
+            if isinstance(dy, ops.PooledGrad):
+                # dy exists only behind its pool; the Winograd dy pass of this layer can form it on the fly when that pass feeds
+                # both the weight gradient and the data gradient -- otherwise it is scattered to memory after all
+                if not (need_w and path.wino_wgrad and self.WINO_TILE == 4 and self.dual_dy and kept_planes and wide and not full):
+                    dy = dy.materialize()
+            # (an adjoint layout implies the Winograd path, hence f32 mode: never the bf16 trunk's boundary)
+            adj = path.adj and kept_planes and not (async_wgrad and side_ctx[0] is None) and not full
+            if isinstance(dy, ops.AdjPlanesGrad) and not adj:
+                dy = dy.materialize()
+            if adj:
+                # Adjoint Winograd form: ONE set of dy planes (A dy A^T) feeds the weight gradient's TN GEMMs and the data gradient's
+                # plane GEMMs; where dy itself is the adjoint data gradient of the layer above (same map, this layer its only reader)
+                # the planes come straight from that layer's product planes and dy is never a tensor.
+                kept = aux.pop("planes:" + name)
+
+                def dy_planes():
+                    if isinstance(dy, ops.AdjPlanesGrad):
+                        return ops.wino_adj_output_to_planes(dy.md, dy.g, g, dy.relu_mask, dy.bits, want_bias=need_w)
+                    Yp, _, part = ops.wino_dy_transform(dy, g, g.Co, False, need_w)
+                    return Yp, part
+                if need_w:
+                    def wg_adj():
+                        Yp, part = dy_planes()
+                        dw_, db_ = ops.wino_wgrad_gemm(Yp, kept, part, g, g.Co, **gout())
+                        return Yp, dw_, db_
+                    Y, dw, db = self._timed("wgrad " + name, "winograd_3x3", ops.wino_flops(g), wg_adj)
+                    L.hand(grads, dw, db)
+                else:
+                    Y, _ = dy_planes()
+                del kept
+                _, uadj = self._wino_weights(L, P, adj=True)
+                bits = aux.pop("bits:" + name, None)
+                below = self._conv_of.get(L.x) if self.adjoint_chain else None
+                gb = aux.get(L.x) if below is not None else None
+                chain = (below is not None and gb is not None and self.consumers[L.x] == 1 and L.x in self.relu_out
+                         and aux["path:" + below["p"]].adj and aux.get("planes:" + below["p"]) is not None and gb.Co == g.Ci
+                         and (gb.N, gb.H, gb.W) == (g.N, g.H, g.W) and T[L.x].dtype == torch.float32)
+
+                def dgrad_adj(dx, acc, mask):
+                    md = ops.wino_dgrad_adj_gemm(Y, uadj, g, g.Co)
+                    use_bits = bits if mask is not None else None
+                    fmask = None if use_bits is not None else mask
+                    if chain and dx is None and not acc and mask is not None:
+                        return ops.AdjPlanesGrad(md, g, fmask, use_bits)         # the layer below reads the planes, not a tensor
+                    return ops.wino_adj_output(md, g, dx, relu_mask=fmask, bits=use_bits, accumulate=acc)
+                deliver(L.x, lambda dx, acc, mask: self._timed("dgrad " + name, "winograd_3x3", ops.wino_flops(g),
+                                                               lambda: dgrad_adj(dx, acc, mask)))
+                return
+            dyp = None
+            if need_w:
+                if path.wino_wgrad and async_wgrad and side_ctx[0] is None and kept_planes and wide:
+                    kept = aux.pop("planes:" + name)
+                    # the one-kernel data gradient reads dy itself: no B^T dy B planes to write (a head's data gradient always takes them)
+                    Y, dyp, part = ops.wino_dy_transform(dy, g, L.co_pad, L.head or not full, True)
+                    self._wgrad_gemm_async(main, Y, kept, part, g, L.co_pad, lambda dw, db: L.hand(grads, dw, db))
+                    wgrad_used = True
+                elif path.wino_wgrad:
+                    kept = aux.pop("planes:" + name, None)
+                    # one pass over dy feeds the weight and the data gradient (trunk: where the data gradient runs on planes at all)
+                    dual = kept is not None and self.dual_dy and (L.head or (g.Co % 32 == 0 and not full))
+                    res = self._timed("wgrad " + name, "winograd_3x3", ops.wino_flops(g),
+                                      lambda: ops.conv2d_wgrad_wino(xin, dy, g, L.co_pad, True, mo=self.WINO_TILE, planes=kept,
+                                                                    dgrad_planes=dual, **gout()))
+                    L.hand(grads, res[0], res[1])
+                    dyp = res[2] if dual else None
+                else:
+                    def wg():
+                        if path.kind == "x31":
+                            L.hand(grads, *self._timed("wgrad " + name, "gemm_tn_x3_kernel (1x1)", ops.conv_flops(g),
+                                                       lambda: ops.conv1x1_wgrad_x3(xin, dy, g, L.co_pad, True, **gout())))
+                            return
+                        L.hand(grads, *self._timed("wgrad " + name, ops.wgrad_tile(g, self.bf16) if self.prof is not None else "", ops.conv_flops(g),
+                                                   lambda: ops.conv2d_wgrad(xin, dy, g, L.co_pad, True, bf16=self.bf16, **gout())))
+                    if side_ctx[0] is not None and defer:
+                        deferred.append(wg)
+                    else:
+                        wg()
+            if path.kind == "wino":
+                if path.adj:
+                    raise RuntimeError(f"{name}: its filter planes are laid out for the adjoint data gradient, which needs the forward's kept planes "
+                                       "(the engine's keep_planes / dual_dy / adjoint_dgrad switches must not change between a forward and its backward)")
+                _, ub = self._wino_weights(L, P)
+                bits = aux.pop("bits:" + name, None) if (dyp is not None or full or isinstance(T[L.x], _Elided)) else None
+
+                def dgrad_rot(dx, acc, mask):
+                    if isinstance(mask, _Elided):            # the gated activation was never stored (conv1_1 -> planes): only its bits exist
+                        if bits is None:
+                            raise RuntimeError(f"{name}: its input was not stored and no ReLU bits were kept for its data gradient")
+                        mask_t = None
+                    else:
+                        mask_t = mask
+                    return ops.conv2d_dgrad_wino(None if isinstance(dy, ops.PooledGrad) else dy, ub, g, dx, mask_t, acc, planes=dyp,
+                                                 bits=bits if mask is not None else None)
+                deliver(L.x, lambda dx, acc, mask: self._timed("dgrad " + name, "winograd_3x3", ops.wino_flops(g),
+                                                               lambda: dgrad_rot(dx, acc, mask)))
+                return
+            if path.kind == "x31" and not to_bf16:
+                _, w3b = self._x31_weights(L, P)
+                deliver(L.x, lambda dx, acc, mask: self._timed(
+                    "dgrad " + name, "gemm_planes_x3_kernel (1x1)", ops.conv_flops(g),
+                    lambda: ops.conv1x1_dgrad_x3(dy, w3b, g, dx, mask, acc)))
+                return
+            _, wb = self._layouts(L, P, True)
+            if to_bf16:
+                def boundary(dx, acc, mask):
+                    if acc or mask is not None or dx is not None:
+                        raise RuntimeError("the bf16 trunk's boundary tensor must have one consumer and no ReLU of its own")
+                    d32 = self._timed("dgrad " + name, ops.igemm_tile(g, 1, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
+                                      lambda: ops.conv2d_dgrad(dy, wb, g, None, None, False, bf16=self.bf16, w3=self._planes(name, True)))
+                    return ops.cast_bf16(d32)
+                deliver(L.x, boundary)
+                return
+            deliver(L.x, lambda dx, acc, mask: self._timed(
+                "dgrad " + name, ops.igemm_tile(g, 1, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
+                lambda: ops.conv2d_dgrad_x3(dy, wb, g, dx, mask, acc) if self.x3 else
+                ops.conv2d_dgrad(dy, wb, g, dx, mask, acc, bf16=self.bf16, w3=self._planes(name, True))))
+
         for op in reversed(self.ops):
             kind = op["op"]
             if side_ctx[0] is not None and id(op) not in self._side_ids:   # the side group is enqueued: back to the caller's stream
@@ -779,233 +990,18 @@ class _Engine:
                 main.wait_event(join_event)
                 joined = True
             if kind == "head":
-                pre = op["p"]
-                off, g = offs[pre]
-                co_pad = ops.pad32(g.Co)
-                xin = T[op["x"]]
-                a4 = 4 * op["a"]
-                x16 = T.get(op["x"] + ":b16")
-                if x16 is not None or self._t16(g, xin):
-                    # bf16 trunk: packed bf16 dy (K of the data gradient padded to 64), nine-tap bf16 weight gradient, LDS-DMA data gradient
-                    f32_dx = x16 is not None                  # the head ran on a bf16 copy of an f32 tensor: its dx goes back as f32
-                    if f32_dx:
-                        xin = x16
-                    ld = ops.pad64(g.Co)
-                    dy = ops.heads_gather_bf16(dloc, dconf, ld, bs, g.Ho * g.Wo, op["a"], off).view(bs, g.Ho, g.Wo, ld)
-                    if any(need[pre + s] for s in ("_bb.weight", "_bb.bias", "_cl.weight", "_cl.bias")):
-                        dw, db = self._timed("wgrad " + pre, "wgrad3x3_bf16_kernel", ops.conv_flops(g),
-                                             lambda: ops.conv3x3_wgrad_bf16t(xin, dy, g, ld, True, dw_out=self._gout(pre + "_bb.weight", pre + "_cl.weight"),
-                                                                             db_out=self._gout(pre + "_bb.bias", pre + "_cl.bias")))
-                        grads[pre + "_bb.weight"], grads[pre + "_cl.weight"] = dw[:a4], dw[a4:]
-                        grads[pre + "_bb.bias"], grads[pre + "_cl.bias"] = db[:a4], db[a4:]
-                    _, wb16 = self._bf16_weights(pre, (P[pre + "_bb.weight"], P[pre + "_cl.weight"]))
-                    def dgrad16(dx, acc, mask, dy=dy, wb16=wb16, g=g, pre=pre, f32_dx=f32_dx):
-                        if f32_dx and (acc or mask is not None or dx is not None):
-                            raise RuntimeError("a head on a bf16 copy must be the first to deliver its input's gradient")
-                        return self._timed("dgrad " + pre, "conv3x3_bf16_kernel", ops.conv_flops(g),
-                                           lambda: ops.conv3x3_bf16(dy, wb16, None, g.Ci, False, flip=True, out=dx, out_f32=f32_dx, relu_mask=mask,
-                                                                    accumulate=acc))
-                    deliver(op["x"], dgrad16)
-                    continue
-                if xin.dtype == torch.bfloat16:
-                    xin = T[op["x"] + ":f32"]
-                dy = ops.heads_gather(dloc, dconf, co_pad, bs, g.Ho * g.Wo, op["a"], off)
-                dyp = None
-                dw = db = None
-                if any(need[pre + s] for s in ("_bb.weight", "_bb.bias", "_cl.weight", "_cl.bias")):
-                    if self._wino_wgrad_ok(g, True) and async_wgrad and side_ctx[0] is None and aux.get("planes:" + pre) is not None \
-                            and co_pad <= 1024:
-                        kept = aux.pop("planes:" + pre)
-                        Y, dyp, part = ops.wino_dy_transform(dy, g, co_pad, True, True)
-
-                        def put(dw, db, pre=pre, a4=a4):
-                            grads[pre + "_bb.weight"], grads[pre + "_cl.weight"] = dw[:a4], dw[a4:]
-                            grads[pre + "_bb.bias"], grads[pre + "_cl.bias"] = db[:a4], db[a4:]
-                        self._wgrad_gemm_async(main, Y, kept, part, g, co_pad, put)
-                        wgrad_used = True
-                    elif self._wino_wgrad_ok(g, True):
-                        kept = aux.pop("planes:" + pre, None)
-                        dual = kept is not None and self.dual_dy        # one pass over dy feeds the weight and the data gradient
-                        res = self._timed("wgrad " + pre, "winograd_3x3", ops.wino_flops(g),
-                                          lambda: ops.conv2d_wgrad_wino(xin, dy, g, co_pad, True, mo=self.WINO_TILE, planes=kept,
-                                                                        dgrad_planes=dual, dw_out=self._gout(pre + "_bb.weight", pre + "_cl.weight"),
-                                                                        db_out=self._gout(pre + "_bb.bias", pre + "_cl.bias")))
-                        dw, db = res[0], res[1]
-                        dyp = res[2] if dual else None
-                    else:
-                        def wg(pre=pre, a4=a4, xin=xin, dy=dy, g=g, co_pad=co_pad):
-                            dw_, db_ = self._timed("wgrad " + pre, ops.wgrad_tile(g, self.bf16) if self.prof is not None else "", ops.conv_flops(g),
-                                                   lambda: ops.conv2d_wgrad(xin, dy, g, co_pad, True, bf16=self.bf16,
-                                                                            dw_out=self._gout(pre + "_bb.weight", pre + "_cl.weight"),
-                                                                            db_out=self._gout(pre + "_bb.bias", pre + "_cl.bias")))
-                            grads[pre + "_bb.weight"], grads[pre + "_cl.weight"] = dw_[:a4], dw_[a4:]
-                            grads[pre + "_bb.bias"], grads[pre + "_cl.bias"] = db_[:a4], db_[a4:]
-                        if side_ctx[0] is not None and defer:
-                            deferred.append(wg)
-                        else:
-                            wg()
-                    if dw is not None:
-                        grads[pre + "_bb.weight"], grads[pre + "_cl.weight"] = dw[:a4], dw[a4:]
-                        grads[pre + "_bb.bias"], grads[pre + "_cl.bias"] = db[:a4], db[a4:]
-                if self._wino_ok(g):
-                    _, ub = self._wino_weights(pre, (P[pre + "_bb.weight"], P[pre + "_cl.weight"]), co_pad)
-                    deliver(op["x"], lambda dx, acc, mask: self._timed("dgrad " + pre, "winograd_3x3", ops.wino_flops(g),
-                                                                       lambda: ops.conv2d_dgrad_wino(dy, ub, g, dx, mask, acc, planes=dyp)))
-                    continue
-                _, wb = self._layouts(pre, (P[pre + "_bb.weight"], P[pre + "_cl.weight"]), co_pad, True)
-                deliver(op["x"], lambda dx, acc, mask: self._timed(
-                    "dgrad " + pre, ops.igemm_tile(g, 1, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
-                    lambda: ops.conv2d_dgrad_x3(dy, wb, g, dx, mask, acc) if self.x3 else
-                    ops.conv2d_dgrad(dy, wb, g, dx, mask, acc, bf16=self.bf16, w3=self._planes(pre, True))))
+                L = self.layers[op["p"]]
+                off, g = offs[L.key]
+                path = aux["path:" + L.key]
+                # its dy is gathered from the loss gradients: packed bf16 rows (K of the data gradient padded to 64) on the bf16 path
+                if path.kind == "b16":
+                    dy = ops.heads_gather_bf16(dloc, dconf, L.ld16, bs, g.Ho * g.Wo, op["a"], off).view(bs, g.Ho, g.Wo, L.ld16)
+                else:
+                    dy = ops.heads_gather(dloc, dconf, L.co_pad, bs, g.Ho * g.Wo, op["a"], off)
+                conv_backward(L, g, path, dy)
             elif kind == "conv":
-                dy = G.pop(op["y"])
-                g = aux[op["y"]]
-                xin = T[op["x"]]
-                dyp = None
-                if self._t16(g, xin) and dy.dtype == torch.bfloat16:
-                    name = op["p"]
-                    if need[name + ".weight"] or need[name + ".bias"]:
-                        grads[name + ".weight"], grads[name + ".bias"] = self._timed(
-                            "wgrad " + name, "wgrad3x3_bf16_kernel", ops.conv_flops(g),
-                            lambda: ops.conv3x3_wgrad_bf16t(xin, dy, g, g.Co, True, dw_out=self._gout(name + ".weight"), db_out=self._gout(name + ".bias")))
-                    _, wb16 = self._bf16_weights(name, (P[name + ".weight"],))
-                    deliver(op["x"], lambda dx, acc, mask: self._timed(
-                        "dgrad " + name, "conv3x3_bf16_kernel", ops.conv_flops(g),
-                        lambda: ops.conv3x3_bf16(dy, wb16, None, g.Ci, False, flip=True, out=dx, relu_mask=mask, accumulate=acc)))
-                    continue
-                to_bf16 = xin.dtype == torch.bfloat16         # boundary of the bf16 trunk: this layer ran on the f32 copy, its dx goes back as bf16
-                if to_bf16:
-                    xin = T[op["x"] + ":f32"]
-                if isinstance(dy, ops.PooledGrad):
-                    # dy exists only behind its pool; the Winograd dy pass of this layer can form it on the fly when that pass feeds
-                    # both the weight gradient and the data gradient -- otherwise it is scattered to memory after all
-                    if not ((need[op["p"] + ".weight"] or need[op["p"] + ".bias"]) and self._wino_wgrad_ok(g, False) and self.WINO_TILE == 4
-                            and self.dual_dy and aux.get("planes:" + op["p"]) is not None and g.Co % 32 == 0 and g.Co <= 1024
-                            and not ops.wino_uses_full(g, 1) and self._wino_ok(g)):
-                        dy = dy.materialize()
-                adj = (self._adj_ok(g) and not to_bf16 and aux.get("planes:" + op["p"]) is not None and not (async_wgrad and side_ctx[0] is None)
-                       and not ops.wino_uses_full(g, 1))
-                if isinstance(dy, ops.AdjPlanesGrad) and not adj:
-                    dy = dy.materialize()
-                if adj:
-                    # Adjoint Winograd form: ONE set of dy planes (A dy A^T) feeds the weight gradient's TN GEMMs and the data gradient's
-                    # plane GEMMs; where dy itself is the adjoint data gradient of the layer above (same map, this layer its only reader)
-                    # the planes come straight from that layer's product planes and dy is never a tensor.
-                    name = op["p"]
-                    kept = aux.pop("planes:" + name)
-                    need_w = need[name + ".weight"] or need[name + ".bias"]
-
-                    def dy_planes(dy=dy, g=g, need_w=need_w):
-                        if isinstance(dy, ops.AdjPlanesGrad):
-                            return ops.wino_adj_output_to_planes(dy.md, dy.g, g, dy.relu_mask, dy.bits, want_bias=need_w)
-                        Yp, _, part = ops.wino_dy_transform(dy, g, g.Co, False, need_w)
-                        return Yp, part
-                    if need_w:
-                        def wg_adj(name=name, g=g, kept=kept):
-                            Yp, part = dy_planes()
-                            dw_, db_ = ops.wino_wgrad_gemm(Yp, kept, part, g, g.Co, dw_out=self._gout(name + ".weight"), db_out=self._gout(name + ".bias"))
-                            return Yp, dw_, db_
-                        Y, dw, db = self._timed("wgrad " + name, "winograd_3x3", ops.wino_flops(g), wg_adj)
-                        grads[name + ".weight"], grads[name + ".bias"] = dw, db
-                    else:
-                        Y, _ = dy_planes()
-                    del kept
-                    _, uadj = self._wino_weights(name, (P[name + ".weight"],), op["co"], adj=True)
-                    bits = aux.pop("bits:" + name, None)
-                    below = self._conv_of.get(op["x"]) if self.adjoint_chain else None
-                    gb = aux.get(op["x"]) if below is not None else None
-                    chain = (below is not None and gb is not None and self.consumers[op["x"]] == 1 and op["x"] in self.relu_out
-                             and self._adj_ok(gb) and aux.get("planes:" + below["p"]) is not None and gb.Co == g.Ci
-                             and (gb.N, gb.H, gb.W) == (g.N, g.H, g.W) and T[op["x"]].dtype == torch.float32)
-
-                    def dgrad_adj(dx, acc, mask, Y=Y, uadj=uadj, g=g, bits=bits, chain=chain):
-                        md = ops.wino_dgrad_adj_gemm(Y, uadj, g, g.Co)
-                        use_bits = bits if mask is not None else None
-                        fmask = None if use_bits is not None else mask
-                        if chain and dx is None and not acc and mask is not None:
-                            return ops.AdjPlanesGrad(md, g, fmask, use_bits)         # the layer below reads the planes, not a tensor
-                        return ops.wino_adj_output(md, g, dx, relu_mask=fmask, bits=use_bits, accumulate=acc)
-                    deliver(op["x"], lambda dx, acc, mask: self._timed("dgrad " + name, "winograd_3x3", ops.wino_flops(g),
-                                                                       lambda: dgrad_adj(dx, acc, mask)))
-                    continue
-                if need[op["p"] + ".weight"] or need[op["p"] + ".bias"]:
-                    if self._wino_wgrad_ok(g, False) and async_wgrad and side_ctx[0] is None and aux.get("planes:" + op["p"]) is not None \
-                            and g.Co % 32 == 0 and g.Co <= 1024:
-                        kept = aux.pop("planes:" + op["p"])
-                        # the one-kernel data gradient reads dy itself: no B^T dy B planes to write
-                        Y, dyp, part = ops.wino_dy_transform(dy, g, g.Co, not ops.wino_uses_full(g, 1), True)
-
-                        def put(dw, db, name=op["p"]):
-                            grads[name + ".weight"], grads[name + ".bias"] = dw, db
-                        self._wgrad_gemm_async(main, Y, kept, part, g, g.Co, put)
-                        wgrad_used = True
-                        dw = None
-                    elif self._wino_wgrad_ok(g, False):
-                        kept = aux.pop("planes:" + op["p"], None)
-                        dual = kept is not None and self.dual_dy and g.Co % 32 == 0 and not ops.wino_uses_full(g, 1)
-                        res = self._timed("wgrad " + op["p"], "winograd_3x3", ops.wino_flops(g),
-                                          lambda: ops.conv2d_wgrad_wino(xin, dy, g, g.Co, True, mo=self.WINO_TILE, planes=kept,
-                                                                        dgrad_planes=dual, dw_out=self._gout(op["p"] + ".weight"),
-                                                                        db_out=self._gout(op["p"] + ".bias")))
-                        dw, db = res[0], res[1]
-                        dyp = res[2] if dual else None
-                    else:
-                        def wg(name=op["p"], xin=xin, dy=dy, g=g):
-                            if self._x31_ok(g):
-                                grads[name + ".weight"], grads[name + ".bias"] = self._timed(
-                                    "wgrad " + name, "gemm_tn_x3_kernel (1x1)", ops.conv_flops(g),
-                                    lambda: ops.conv1x1_wgrad_x3(xin, dy, g, g.Co, True, dw_out=self._gout(name + ".weight"),
-                                                                 db_out=self._gout(name + ".bias")))
-                                return
-                            grads[name + ".weight"], grads[name + ".bias"] = self._timed(
-                                "wgrad " + name, ops.wgrad_tile(g, self.bf16) if self.prof is not None else "", ops.conv_flops(g),
-                                lambda: ops.conv2d_wgrad(xin, dy, g, g.Co, True, bf16=self.bf16, dw_out=self._gout(name + ".weight"),
-                                                         db_out=self._gout(name + ".bias")))
-                        if side_ctx[0] is not None and defer:
-                            deferred.append(wg)
-                        else:
-                            wg()
-                        dw = None
-                    if dw is not None:
-                        grads[op["p"] + ".weight"], grads[op["p"] + ".bias"] = dw, db
-                if self._wino_ok(g):
-                    _, ub = self._wino_weights(op["p"], (P[op["p"] + ".weight"],), op["co"], adj=self._adj_ok(g))
-                    if self._adj_ok(g):
-                        raise RuntimeError(f"{op['p']}: its filter planes are laid out for the adjoint data gradient, which needs the forward's kept planes "
-                                           "(the engine's keep_planes / dual_dy / adjoint_dgrad switches must not change between a forward and its backward)")
-                    bits = aux.pop("bits:" + op["p"], None) if (dyp is not None or ops.wino_uses_full(g, 1) or isinstance(T[op["x"]], _Elided)) else None
-                    def dgrad_rot(dx, acc, mask, dy=dy, ub=ub, g=g, dyp=dyp, bits=bits, name=op["p"]):
-                        if isinstance(mask, _Elided):            # the gated activation was never stored (conv1_1 -> planes): only its bits exist
-                            if bits is None:
-                                raise RuntimeError(f"{name}: its input was not stored and no ReLU bits were kept for its data gradient")
-                            mask_t = None
-                        else:
-                            mask_t = mask
-                        return ops.conv2d_dgrad_wino(None if isinstance(dy, ops.PooledGrad) else dy, ub, g, dx, mask_t, acc, planes=dyp,
-                                                     bits=bits if mask is not None else None)
-                    deliver(op["x"], lambda dx, acc, mask: self._timed("dgrad " + op["p"], "winograd_3x3", ops.wino_flops(g),
-                                                                       lambda: dgrad_rot(dx, acc, mask)))
-                    continue
-                if self._x31_ok(g) and not to_bf16:
-                    _, w3b = self._x31_weights(op["p"], (P[op["p"] + ".weight"],), op["co"])
-                    deliver(op["x"], lambda dx, acc, mask: self._timed(
-                        "dgrad " + op["p"], "gemm_planes_x3_kernel (1x1)", ops.conv_flops(g),
-                        lambda: ops.conv1x1_dgrad_x3(dy, w3b, g, dx, mask, acc)))
-                    continue
-                _, wb = self._layouts(op["p"], (P[op["p"] + ".weight"],), op["co"], True)
-                if to_bf16:
-                    def boundary(dx, acc, mask, dy=dy, wb=wb, g=g, name=op["p"]):
-                        if acc or mask is not None or dx is not None:
-                            raise RuntimeError("the bf16 trunk's boundary tensor must have one consumer and no ReLU of its own")
-                        d32 = self._timed("dgrad " + name, ops.igemm_tile(g, 1, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
-                                          lambda: ops.conv2d_dgrad(dy, wb, g, None, None, False, bf16=self.bf16, w3=self._planes(name, True)))
-                        return ops.cast_bf16(d32)
-                    deliver(op["x"], boundary)
-                    continue
-                deliver(op["x"], lambda dx, acc, mask: self._timed(
-                    "dgrad " + op["p"], ops.igemm_tile(g, 1, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
-                    lambda: ops.conv2d_dgrad_x3(dy, wb, g, dx, mask, acc) if self.x3 else
-                    ops.conv2d_dgrad(dy, wb, g, dx, mask, acc, bf16=self.bf16, w3=self._planes(op["p"], True))))
+                L = self.layers[op["p"]]
+                conv_backward(L, aux[op["y"]], aux["path:" + L.key], G.pop(op["y"]))
             elif kind == "pool":
                 dy = G.pop(op["y"])
                 xin = T[op["x"]]

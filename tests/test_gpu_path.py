@@ -1184,6 +1184,28 @@ def test_weight_cache_is_refreshed_in_training_and_invalidated_on_request():
         assert float((e3 - e2).abs().max()) > 1e-3
 
 
+@pytest.mark.parametrize("conv_dtype", ["f32", "bf16"])
+def test_forward_records_the_path_the_weight_table_planned(golden_net, conv_dtype):
+    """One decision, three readers: what a training forward records per layer for its backward (`aux["path:..."]`) is what the walk
+    over the op list (`_plan`) answers for the same batch, and the weight table holds the filters that path names."""
+    import grad_measure as M
+    net, _, _ = golden_net
+    eng = net._engine
+    M.set_engine(net, "wino", conv_dtype)
+    try:
+        with torch.no_grad():
+            _, _, saved = eng.forward(torch.zeros(2, 3, 300, 300, device=DEV), net._forward_params(), save=True)
+        plan = list(eng._plan(2, 300, 300))
+        kinds = M.weight_kinds(net)
+    finally:
+        M.set_engine(net, "wino", "f32")
+    assert len(plan) == len(eng.layers)
+    for _, L, g, path in plan:
+        assert saved["aux"]["path:" + L.key] == path, L.key
+        assert kinds[L.key] == eng._table_kind(path), L.key
+    assert {path.kind for _, _, _, path in plan} == ({"wino", "direct"} if conv_dtype == "f32" else {"b16", "direct"})
+
+
 def test_ops_refuse_tensors_of_another_device_than_the_current_one():
     from objectdetection_ssd_amd import ops
     if torch.cuda.device_count() < 2:
