@@ -61,7 +61,8 @@ def multibox_loss(loc, conf, boxes, classes, pri_cxcywh=None, neg_pos_ratio=3):
     logp64 = torch.log_softmax(torch.from_numpy(conf.reshape(-1, C)).double(), dim=-1).numpy().reshape(bs, P, C)
     cce64 = -np.take_along_axis(logp64, cls[..., None], axis=2)[..., 0]
     loc_loss = np.abs(diff.astype(np.float64)).sum() / (n_pos * 4)
-    conf_loss = (cce64[hn].sum() + cce64[pos].sum()) / n_pos
+    # a quota past the negatives spills onto positives, which count as 0 there (Losses.py:190: cce1[pos_ancs] = 0. before the sort)
+    conf_loss = (cce64[hn & ~pos].sum() + cce64[pos].sum()) / n_pos
     dloc = np.zeros(loc.shape, np.float64)
     dloc[pos] = np.sign(diff) / (n_pos * 4)
     onehot = np.zeros((bs, P, C), np.float64)
