@@ -1,6 +1,6 @@
 """Drop-in usage on synthetic data: the reference's training loop shape (train_function.py:59-95) on the gfx950 path.
 
-    python examples/train_synthetic.py [--steps 20] [--batch 20]
+    python examples/train_synthetic.py [--steps 20] [--batch 20] [--fused-sgd] [--grad-clip 10.0]
 
 With the reference checked out next to this repo, the same three lines (`install_dropin()`, then
 `from train_function import train_model`) run its own `train_model` unchanged -- see INTEGRATION.md.
@@ -41,7 +41,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=20)        # train.py:29
     ap.add_argument("--fused-sgd", action="store_true", help="objectdetection_ssd_amd.optim.SGD in place of torch.optim.SGD (same results)")
+    ap.add_argument("--grad-clip", type=float, default=None, metavar="FLOAT",
+                    help="clip the global gradient 2-norm to FLOAT inside the fused optimizer step and skip non-finite steps (implies "
+                         "--fused-sgd; what torch.nn.utils.clip_grad_norm_ before optimizer.step() does, without leaving the device)")
     a = ap.parse_args()
+    clip = {}
+    if a.grad_clip is not None:
+        a.fused_sgd = True
+        clip = dict(max_grad_norm=a.grad_clip, skip_nonfinite=True)
     device = torch.device("cuda")
     cnn = SSD_300().to(device)
     biases = [p for n, p in cnn.named_parameters() if p.requires_grad and n.endswith(".bias")]
@@ -52,7 +59,7 @@ def main():
     else:
         SGD = torch.optim.SGD
     optimizer = SGD(params=[{"params": biases, "lr": 2 * lr}, {"params": not_biases}], lr=lr, momentum=0.9,
-                    weight_decay=5e-4)                      # train.py:53-55
+                    weight_decay=5e-4, **clip)              # train.py:53-55
     cnn.train()
     t0 = time.time()
     for count, (inputs, classes, bboxes) in enumerate(batches(a.steps, a.batch, device)):
@@ -66,7 +73,11 @@ def main():
         loss.backward()
         optimizer.step()
         if count % 5 == 0:
-            print(f"it {count:3d}  l1 {loss1.item():.4f}  l2 {loss2.item():.4f}  {time.time() - t0:.1f}s")
+            norm = ""
+            if clip:                                        # device values of the step just taken; reading them is this loop's sync
+                norm = (f"  |g| {optimizer.grad_norm.item():.3f}  clip {optimizer.clip_coef.item():.3f}"
+                        f"  skipped {optimizer.skipped_steps.item()}")
+            print(f"it {count:3d}  l1 {loss1.item():.4f}  l2 {loss2.item():.4f}{norm}  {time.time() - t0:.1f}s")
     torch.cuda.synchronize()
     print(f"{a.steps * a.batch / (time.time() - t0):.1f} images/s incl. host-side data generation")
 

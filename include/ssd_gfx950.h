@@ -609,6 +609,35 @@ int ssd_graph_node_counts(void* graph, int* kernel_nodes, int* total_nodes);
 int ssd_sgd_momentum(float* param, const float* grad, float* momentum_buf, size_t n, float lr, float momentum,
                      float weight_decay, const float* grad_scale_dev, int first_step, void* stream);
 
+/* ---- gradient-norm clipping and the non-finite step guard of the fused SGD step (torch.nn.utils.clip_grad_norm_, which a user of
+ * the reference loop puts between train_function.py:94 `loss.backward()` and :95 `optimizer.step()`), without leaving the device.
+ *
+ * ssd_grad_norm_partials: one pass over grad[0..n) (f32, 16-byte aligned, n % 4 == 0, pads zero) that writes
+ * ssd_grad_norm_slots(n) per-workgroup partials into partials[slot0 ...] (f64; slot_capacity = slots the buffer holds):
+ *   norm_kind 0: sums of squares accumulated in f64 (the square of an f32 is exact there);
+ *   norm_kind 1: max |g| widened to f64, NaN if the range holds a NaN.
+ * The grid depends on n alone and every reduction runs in a fixed order without atomics: results are bitwise reproducible.
+ *
+ * ssd_grad_clip_finalize: one workgroup folds partials[0..n_slots) -- all ranges of the step -- in a fixed order and writes
+ * state[0..5) (4-byte words of a block the caller zeroes once):
+ *   state[0] total_norm = (float)(sqrt(S) * (double)pre_scale)  (kind 0)  or  (float)max * pre_scale  (kind 1); pre_scale_dev may
+ *            be NULL (= 1; ddp.py passes 1 / n_pos_global, which the flat gradient buffer still lacks);
+ *   state[1] clip_coef  = min(1, (1 / (total_norm + 1e-6f)) * max_norm), f32, each of the three operations rounded once (correctly
+ *            rounded reciprocal), a NaN kept: the sequence clip_grad_norm_ executes for `max_norm / (total_norm + 1e-6)` -- torch
+ *            divides a number by a tensor as reciprocal-times-number -- so equal norms give bit-equal coefficients;
+ *            max_norm < 0: no clipping, clip_coef = 1;
+ *   state[2] grad_scale = pre_scale * clip_coef (clip_coef itself without pre_scale): what ssd_sgd_momentum* take as grad_scale_dev;
+ *   state[3] skip (int32) = guard != 0 and total_norm is Inf or NaN;   state[4] skipped_steps (int32) += skip.
+ *
+ * ssd_sgd_momentum_guarded: ssd_sgd_momentum, same arithmetic and rounding, that writes nothing at all -- neither parameters nor
+ * momentum -- when *skip_dev != 0. */
+int ssd_grad_norm_slots(size_t n);
+int ssd_grad_norm_partials(const float* grad, size_t n, int norm_kind, double* partials, int slot0, int slot_capacity, void* stream);
+int ssd_grad_clip_finalize(const double* partials, int n_slots, int norm_kind, float max_norm, const float* pre_scale_dev, int guard,
+                           float* state, void* stream);
+int ssd_sgd_momentum_guarded(float* param, const float* grad, float* momentum_buf, size_t n, float lr, float momentum,
+                             float weight_decay, const float* grad_scale_dev, int first_step, const int* skip_dev, void* stream);
+
 /* ---- BatchNorm2d in training mode, Dropout / Dropout2d (SSD_resnet34 train mode: Model.py:24,56-70,72-126 and
  * torchvision's BasicBlock).  Tensors are [M][ld] f32 rows whose first C columns are the channels (M = N*H*W), C % 4 == 0,
  * ld % 4 == 0, rows 16-byte aligned.  Reductions use fixed-order slab partials (no atomics): results are bitwise reproducible.

@@ -384,10 +384,14 @@ __global__ void heads_gather_kernel(const float* __restrict__ dloc, const float*
 // The rounding sequence is the one torch's foreach path performs with its separate launches -- add(grad, p, alpha=wd) and
 // add_(p, buf, alpha=-lr) are single fused multiply-adds, mul_(buf, mom) and add_(buf, g) round separately -- so a run through
 // this kernel and a run through torch.optim.SGD stay bit-identical.
+// GUARD: `skip` points at the step guard's flag (grad_clip.hip writes it); when it is set the whole grid returns before its first
+// load, so neither parameters nor momentum are touched.
 // ---------------------------------------------------------------------------------------
+template <bool GUARD>
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, size_t n, float lr,
-                           float mom, float wd, const float* __restrict__ scale, int first) {
+                           float mom, float wd, const float* __restrict__ scale, int first, const int* __restrict__ skip) {
 #pragma clang fp contract(off)
+    if (GUARD && *skip != 0) return;
     const float sc = scale ? *scale : 1.f;
     const float neg_lr = -lr;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -590,7 +594,17 @@ extern "C" int ssd_sgd_momentum(float* param, const float* grad, float* buf, siz
                                 float weight_decay, const float* grad_scale_dev, int first_step, void* stream) {
     if (!param || !grad || !buf) return SSD_ERR_NULL;
     if (n == 0) return SSD_OK;
-    hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, param, grad, buf, n, lr, momentum, weight_decay, grad_scale_dev, first_step);
+    hipLaunchKernelGGL((sgd_kernel<false>), dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, param, grad, buf, n, lr, momentum, weight_decay, grad_scale_dev, first_step, (const int*)nullptr);
+    SSD_CHECK_LAUNCH();
+    return SSD_OK;
+}
+
+extern "C" int ssd_sgd_momentum_guarded(float* param, const float* grad, float* buf, size_t n, float lr, float momentum,
+                                        float weight_decay, const float* grad_scale_dev, int first_step, const int* skip_dev,
+                                        void* stream) {
+    if (!param || !grad || !buf || !skip_dev) return SSD_ERR_NULL;
+    if (n == 0) return SSD_OK;
+    hipLaunchKernelGGL((sgd_kernel<true>), dim3(grid_for(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, param, grad, buf, n, lr, momentum, weight_decay, grad_scale_dev, first_step, skip_dev);
     SSD_CHECK_LAUNCH();
     return SSD_OK;
 }

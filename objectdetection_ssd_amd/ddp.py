@@ -22,9 +22,10 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .optim import GradClipMixin
 
 
-class FlatSGDDataParallel(torch.optim.Optimizer):
+class FlatSGDDataParallel(GradClipMixin, torch.optim.Optimizer):
     """The data-parallel optimizer of the step.  It IS a `torch.optim.Optimizer` with the two parameter groups of reference
     train.py:53-55 in the same order (`param_groups[0]` = biases at 2x lr, `param_groups[1]` = the rest), so the caller's
     `StepLR(optimizer, ...)` (train.py:57), `for g in optimizer.param_groups: g['lr'] = lr` (train_function.py:29-30),
@@ -34,7 +35,8 @@ class FlatSGDDataParallel(torch.optim.Optimizer):
 
     def __init__(self, model, lr: float = 1e-4, momentum: float = 0.9, weight_decay: float = 5e-4,
                  bias_lr_mult: float = 2.0, process_group=None, overlap: Optional[bool] = None, bucket_bytes: int = 16 << 20,
-                 grad_dtype: torch.dtype = torch.float32, time_exchange: bool = False):
+                 grad_dtype: torch.dtype = torch.float32, time_exchange: bool = False,
+                 max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False):
         """overlap: start the all-reduce of a slice of the flat gradient buffer as soon as the backward has produced all of it
         (asynchronous collectives on the process group's stream, `bucket_bytes` per slice), instead of one all-reduce after the
         backward.  Same sums, same result (bitwise: tests/test_ddp_gloo.py at world 2 / 4 / 8).  None (default) = overlapped whenever
@@ -48,7 +50,14 @@ class FlatSGDDataParallel(torch.optim.Optimizer):
         to the single all-reduce.
 
         time_exchange: record HIP events around the points where the COMPUTE stream waits for the collectives, so that
-        `exposed_exchange_ms()` reports how long a step's gradient exchange was not hidden behind the backward."""
+        `exposed_exchange_ms()` reports how long a step's gradient exchange was not hidden behind the backward.
+
+        max_grad_norm / norm_type (2 or inf) / skip_nonfinite: clip the norm of the GLOBAL-batch gradient -- the reduced buffer times
+        1 / n_pos_global, so every rank computes the same norm from the same bytes and no further collective is needed -- and skip a
+        step whose norm is Inf or NaN (parameters and momentum untouched, `skipped_steps` counts it).  One streaming read of the
+        gradient buffer and one finalise launch in front of the two SGD launches, all on the device; `grad_norm`, `clip_coef` and
+        `skipped_steps` are 0-dim device tensors, overwritten by the next step.  Plain attributes: they may be changed between steps."""
+        self._init_clip(max_grad_norm, norm_type, skip_nonfinite)
         self.model = model
         self.group = process_group
         if grad_dtype not in (torch.float32, torch.bfloat16):
@@ -119,6 +128,7 @@ class FlatSGDDataParallel(torch.optim.Optimizer):
             eng_ref = (lambda e=eng: e)
         self._finalizer = weakref.finalize(self, FlatSGDDataParallel._detach, eng_ref, self._token)
         self.flat_grad16 = (torch.zeros(self.n_w, device=dev, dtype=torch.bfloat16) if grad_dtype == torch.bfloat16 else None)
+        self._clip_prepare()
         # -- overlapped exchange: contiguous slices of the weight segment, filled from the back of the network first ------------
         self.overlap = bool(overlap)
         self._handles: list = []
@@ -368,18 +378,36 @@ class FlatSGDDataParallel(torch.optim.Optimizer):
             self._closed = True
             self._finalizer()
 
+    def _clip_prepare(self) -> bool:
+        """Clipping or the guard switched on: make sure the small device buffers exist (outside any graph capture) -> True."""
+        if not self._clip_on():
+            return False
+        self._clip_buffers(self.flat_grad.device, ops.grad_norm_slots(self.n))
+        return True
+
     def apply_sgd(self) -> None:
         first = not self._has_momentum
         gb, gw = self.param_groups
         for g in (gb, gw):
             if g.get("dampening", 0) != 0 or g.get("nesterov", False):
                 raise ValueError("FlatSGDDataParallel: dampening / nesterov are not part of the reference's step (train.py:53-55)")
-        ops.sgd_momentum_(self.flat_param[:self.n_w], self.flat_grad[:self.n_w], self.flat_mom[:self.n_w],
-                          float(gw["lr"]), float(gw["momentum"]), float(gw["weight_decay"]), self.inv_npos,
-                          first or gw["momentum"] == 0)
-        ops.sgd_momentum_(self.flat_param[self.n_w:], self.flat_grad[self.n_w:self.n], self.flat_mom[self.n_w:],
-                          float(gb["lr"]), float(gb["momentum"]), float(gb["weight_decay"]), self.inv_npos,
-                          first or gb["momentum"] == 0)
+        if self._clip_prepare():
+            # the norm of flat_grad[:n] * inv_npos (count slot and pad excluded), read behind the all-reduce: the same on every rank.
+            # (A skipped first step leaves the momentum at zero; momentum * 0 + g is the first-step form in value.)
+            scale, skip = self._clip_run([self.flat_grad[:self.n]], self.inv_npos)
+            ops.sgd_momentum_guarded_(self.flat_param[:self.n_w], self.flat_grad[:self.n_w], self.flat_mom[:self.n_w],
+                                      float(gw["lr"]), float(gw["momentum"]), float(gw["weight_decay"]), scale,
+                                      first or gw["momentum"] == 0, skip)
+            ops.sgd_momentum_guarded_(self.flat_param[self.n_w:], self.flat_grad[self.n_w:self.n], self.flat_mom[self.n_w:],
+                                      float(gb["lr"]), float(gb["momentum"]), float(gb["weight_decay"]), scale,
+                                      first or gb["momentum"] == 0, skip)
+        else:
+            ops.sgd_momentum_(self.flat_param[:self.n_w], self.flat_grad[:self.n_w], self.flat_mom[:self.n_w],
+                              float(gw["lr"]), float(gw["momentum"]), float(gw["weight_decay"]), self.inv_npos,
+                              first or gw["momentum"] == 0)
+            ops.sgd_momentum_(self.flat_param[self.n_w:], self.flat_grad[self.n_w:self.n], self.flat_mom[self.n_w:],
+                              float(gb["lr"]), float(gb["momentum"]), float(gb["weight_decay"]), self.inv_npos,
+                              first or gb["momentum"] == 0)
         if first and (gw["momentum"] != 0 or gb["momentum"] != 0):
             for p, mv in zip(self.params, self.mom_views):
                 self.state[p]["momentum_buffer"] = mv          # torch.optim.SGD's state layout: checkpoints carry the momentum
@@ -429,7 +457,11 @@ class GraphedTrainStep:
     `FlatSGDDataParallel(overlap=...)` is switched off for the life of this object, and a trainer built with `grad_dtype=torch.bfloat16`
     is refused at more than one rank (`ValueError`) rather than sending f32.
 
-    What forces a re-capture: a change of lr / momentum / weight decay of either group (StepLR), of the world size, of the engine's
+    Gradient clipping and the non-finite step guard of the trainer (`max_grad_norm`, `norm_type`, `skip_nonfinite`) are launches of
+    `apply_sgd` and so part of the captured step at one rank: a skipped replayed step leaves parameters and momentum untouched and
+    bumps `trainer.skipped_steps` with no host involvement.  With more ranks they run eagerly behind the all-reduce, as the SGD does.
+
+    What forces a re-capture: a change of lr / momentum / weight decay of either group (StepLR), of the trainer's clip settings, of the world size, of the engine's
     stream placement (`overlap_tail`, `defer_tail_wgrad`), or of any engine setting in `_Engine.schedule_key()` (dtype mode, Winograd
     and its thresholds, the fused and adjoint forms).  What a replay holds: the graph has baked in raw device pointers, so this object keeps,
     for as long as the graph lives, every workspace the capture was handed (`ops.capture_workspaces`) and, where the step lays out its
@@ -529,7 +561,7 @@ class GraphedTrainStep:
         tr = self.trainer
         eng = self.net._engine
         return tuple((g["lr"], g["momentum"], g["weight_decay"]) for g in tr.param_groups) + (
-            tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + eng.schedule_key()
+            tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + tr._clip_settings() + eng.schedule_key()
 
     def _eager(self, x, classes, boxes):
         from . import Losses
@@ -581,6 +613,7 @@ class GraphedTrainStep:
             return self._eager(x, classes, boxes)
         if self._static is None:
             self._make_static(x)
+        tr._clip_prepare()                # (the clip's small buffers come into being here, never inside a capture)
         self._load_batch(x, classes, boxes)
         if self.graph is None or self._sig != self._signature():
             self._capture()

@@ -938,6 +938,59 @@ def sgd_momentum_(param, grad, buf, lr, momentum, weight_decay, grad_scale=None,
                                        float(weight_decay), _ptr(grad_scale), int(first_step), _stream()), "sgd_momentum")
 
 
+GRAD_CLIP_STATE_WORDS = 8      # total_norm, clip_coef, grad_scale (f32) | skip, skipped_steps (int32) | 3 spare: include/ssd_gfx950.h
+
+
+def _norm_kind(norm_type) -> int:
+    if norm_type == 2:
+        return 0
+    if norm_type == float("inf"):
+        return 1
+    raise ValueError(f"norm_type must be 2 or inf, got {norm_type!r}")
+
+
+def grad_norm_slots(n: int) -> int:
+    """Partial slots `grad_norm_partials_` writes for a range of n floats (host-side query, no GPU)."""
+    return int(_lib.load().ssd_grad_norm_slots(int(n)))
+
+
+def grad_norm_partials_(grad, partials, slot0, norm_type=2.0) -> int:
+    """Per-workgroup partials of sum(g^2) (f64) or max|g| over the contiguous f32 range `grad` (16-byte aligned, a multiple of 4
+    floats) into partials[slot0:]; returns the first free slot after them."""
+    _req(grad, "grad"); _req(partials, "partials", torch.float64)
+    if grad.numel() % 4 or grad.data_ptr() % 16:
+        raise ValueError("grad_norm_partials_: the range must be 16-byte aligned and a multiple of 4 floats long (zero pads)")
+    slot0 = int(slot0)
+    check(_lib.load().ssd_grad_norm_partials(grad.data_ptr(), grad.numel(), _norm_kind(norm_type), partials.data_ptr(), slot0,
+                                             partials.numel(), _stream()), "grad_norm_partials")
+    return slot0 + grad_norm_slots(grad.numel())
+
+
+def grad_clip_finalize_(partials, n_slots, norm_type, max_norm, pre_scale, guard, state):
+    """partials[:n_slots] -> state (f32[GRAD_CLIP_STATE_WORDS]): total_norm, clip_coef, grad_scale, skip, skipped_steps += skip.
+    max_norm None: no clipping (clip_coef = 1); pre_scale: optional 1-element device tensor the norm and the scale are multiplied by."""
+    _req(partials, "partials", torch.float64); _req(state, "state")
+    n_slots = int(n_slots)
+    if not 0 <= n_slots <= partials.numel() or state.numel() < GRAD_CLIP_STATE_WORDS:
+        raise ValueError("grad_clip_finalize_: slot count / state size")
+    if pre_scale is not None:
+        _req(pre_scale, "pre_scale")
+    check(_lib.load().ssd_grad_clip_finalize(partials.data_ptr(), n_slots, _norm_kind(norm_type), -1.0 if max_norm is None else float(max_norm),
+                                             _ptr(pre_scale), int(bool(guard)), state.data_ptr(), _stream()), "grad_clip_finalize")
+
+
+def sgd_momentum_guarded_(param, grad, buf, lr, momentum, weight_decay, grad_scale, first_step, skip):
+    """`sgd_momentum_` that leaves parameters and momentum untouched when the device flag `skip` (int32) is set."""
+    _req(param, "param"); _req(grad, "grad"); _req(buf, "buf"); _req(skip, "skip", torch.int32)
+    if grad.numel() != param.numel() or buf.numel() != param.numel():
+        raise ValueError("sgd sizes")
+    if grad_scale is not None:
+        _req(grad_scale, "grad_scale")
+    check(_lib.load().ssd_sgd_momentum_guarded(param.data_ptr(), grad.data_ptr(), buf.data_ptr(), param.numel(), float(lr), float(momentum),
+                                               float(weight_decay), _ptr(grad_scale), int(first_step), skip.data_ptr(), _stream()),
+          "sgd_momentum_guarded")
+
+
 def map_eval(det_boxes, det_classes, det_scores, det_start, gt_boxes, gt_classes, gt_start, recall_levels, n_classes=20):
     """Concatenated detections / ground truth (see include/ssd_gfx950.h ssd_map_eval) -> (table (n_classes, n_levels)
     float64, tp (D,) uint8, counts (2, n_classes) int32).  recall_levels: host sequence of floats."""

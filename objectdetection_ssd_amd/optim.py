@@ -13,14 +13,80 @@ The kernel reproduces torch's rounding sequence, so the parameters after k steps
 
 Only what the reference uses is implemented: `dampening`, `nesterov`, `maximize` must stay at their defaults.  GPU only,
 like the rest of the package.
+
+Gradient clipping and the non-finite step guard (`max_grad_norm`, `norm_type`, `skip_nonfinite`) are what a user of that loop
+adds with `torch.nn.utils.clip_grad_norm_` between `backward()` and `step()`: here they are one norm pass per launch range, one
+finalise launch and the guarded form of the same SGD kernel, and nothing comes back to the host (`GradClipMixin`).
 """
 from __future__ import annotations
 
+import math
 from typing import List
 
 import torch
 
 from . import ops
+
+
+def check_clip_settings(max_grad_norm, norm_type, skip_nonfinite) -> None:
+    if max_grad_norm is not None:
+        if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm must be None or a positive number, got {max_grad_norm!r}")
+    if isinstance(norm_type, bool) or not isinstance(norm_type, (int, float)) or not (norm_type == 2 or norm_type == math.inf):
+        raise ValueError(f"norm_type must be 2 or float('inf'), got {norm_type!r}")
+    if not isinstance(skip_nonfinite, bool):
+        raise ValueError(f"skip_nonfinite must be a bool, got {skip_nonfinite!r}")
+
+
+class GradClipMixin:
+    """Settings, device state and launches of gradient-norm clipping and the non-finite step guard, shared by `optim.SGD` and
+    `ddp.FlatSGDDataParallel`.  The settings are plain attributes (`max_grad_norm`, `norm_type`, `skip_nonfinite`), read at every
+    step; the state block (include/ssd_gfx950.h, ssd_grad_clip_finalize) lives on the device and `grad_norm` / `clip_coef` /
+    `skipped_steps` are views of it: reading them is the caller's synchronisation, the step itself never synchronises."""
+
+    def _init_clip(self, max_grad_norm, norm_type, skip_nonfinite) -> None:
+        check_clip_settings(max_grad_norm, norm_type, skip_nonfinite)
+        self.max_grad_norm, self.norm_type, self.skip_nonfinite = max_grad_norm, norm_type, skip_nonfinite
+        self._clip_state = None
+        self._clip_partials = None
+
+    def _clip_on(self) -> bool:
+        check_clip_settings(self.max_grad_norm, self.norm_type, self.skip_nonfinite)
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _clip_settings(self):
+        return (self.max_grad_norm, float(self.norm_type), self.skip_nonfinite)
+
+    def _clip_buffers(self, dev, slots: int) -> None:
+        if self._clip_state is None or self._clip_state.device != dev:
+            self._clip_state = torch.zeros(ops.GRAD_CLIP_STATE_WORDS, device=dev, dtype=torch.float32)
+        if self._clip_partials is None or self._clip_partials.device != dev or self._clip_partials.numel() < slots:
+            self._clip_partials = torch.zeros(max(slots, 1), device=dev, dtype=torch.float64)
+
+    def _clip_run(self, ranges, pre_scale):
+        """Norm of the flat f32 ranges (one partials launch each), one finalise -> (grad_scale, skip): the device words the guarded
+        SGD launches read."""
+        s = 0
+        for r in ranges:
+            s = ops.grad_norm_partials_(r, self._clip_partials, s, self.norm_type)
+        ops.grad_clip_finalize_(self._clip_partials, s, self.norm_type, self.max_grad_norm, pre_scale, self.skip_nonfinite,
+                                self._clip_state)
+        return self._clip_state[2:3], self._clip_state.view(torch.int32)[3:4]
+
+    @property
+    def grad_norm(self):
+        """0-dim f32 device tensor: the global gradient norm of the last clipped / guarded step (None before the first)."""
+        return None if self._clip_state is None else self._clip_state[0]
+
+    @property
+    def clip_coef(self):
+        """0-dim f32 device tensor: min(1, max_grad_norm / (grad_norm + 1e-6)) of the last step."""
+        return None if self._clip_state is None else self._clip_state[1]
+
+    @property
+    def skipped_steps(self):
+        """0-dim int32 device tensor: steps the guard has skipped so far."""
+        return None if self._clip_state is None else self._clip_state.view(torch.int32)[4]
 
 
 class _GroupBuffers:
@@ -57,9 +123,14 @@ class _GroupBuffers:
         return len(params) == len(self.ptrs) and all(p.data_ptr() == q for p, q in zip(params, self.ptrs))
 
 
-class SGD(torch.optim.Optimizer):
+class SGD(GradClipMixin, torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
-                 nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None):
+                 nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None,
+                 max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False):
+        """max_grad_norm: clip the GLOBAL norm (`norm_type` 2 or inf) of every gradient of every group to it, as
+        `torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm, norm_type)` before `step()` does.  skip_nonfinite: a step whose
+        gradient norm is Inf or NaN changes neither parameters nor momentum and counts into `skipped_steps`."""
+        self._init_clip(max_grad_norm, norm_type, skip_nonfinite)
         if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
             raise ValueError("SGD: lr, momentum and weight_decay must be non-negative")
         if dampening != 0.0 or nesterov or maximize or differentiable:
@@ -88,12 +159,31 @@ class SGD(torch.optim.Optimizer):
             buf = self._buffers[gi] = _GroupBuffers(params, self.state)
         return buf
 
+    def _launch_runs(self, buf, params, runs, lr, mom, wd, grad_scale, skip) -> None:
+        for lo, hi, fresh in runs:
+            a = buf.offsets[lo]
+            b = buf.offsets[hi - 1] + (buf.sizes[hi - 1] + 3) // 4 * 4
+            # momentum 0: torch keeps no buffer and steps with the gradient itself = the "first step" form of the kernel
+            if skip is None:
+                ops.sgd_momentum_(buf.param[a:b], buf.grad[a:b], buf.mom[a:b], lr, mom, wd, None, fresh or mom == 0.0)
+            else:
+                ops.sgd_momentum_guarded_(buf.param[a:b], buf.grad[a:b], buf.mom[a:b], lr, mom, wd, grad_scale, fresh or mom == 0.0, skip)
+            for i in range(lo, hi):
+                p = params[i]
+                if mom != 0.0 and fresh:
+                    # (a skipped first step leaves the buffer at zero: momentum * 0 + g is the first-step form in value)
+                    o, sz = buf.offsets[i], buf.sizes[i]
+                    self.state[p]["momentum_buffer"] = buf.mom[o:o + sz].view_as(p)
+                torch.autograd.graph.increment_version(p)     # written outside autograd: invalidate re-laid weight caches
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        clip = self._clip_on()
+        pending = []                                              # clipping: every group's runs wait for the one global norm
         for gi, group in enumerate(self.param_groups):
             if group["dampening"] != 0 or group["nesterov"] or group.get("maximize", False):
                 raise ValueError("SGD: dampening / nesterov / maximize are not implemented")
@@ -121,15 +211,18 @@ class SGD(torch.optim.Optimizer):
             if not have:
                 continue
             torch._foreach_copy_([buf.grad_views[i] for i in have], [params[i].grad for i in have])
-            for lo, hi, fresh in runs:
-                a = buf.offsets[lo]
-                b = buf.offsets[hi - 1] + (buf.sizes[hi - 1] + 3) // 4 * 4
-                # momentum 0: torch keeps no buffer and steps with the gradient itself = the "first step" form of the kernel
-                ops.sgd_momentum_(buf.param[a:b], buf.grad[a:b], buf.mom[a:b], lr, mom, wd, None, fresh or mom == 0.0)
-                for i in range(lo, hi):
-                    p = params[i]
-                    if mom != 0.0 and fresh:
-                        o, sz = buf.offsets[i], buf.sizes[i]
-                        self.state[p]["momentum_buffer"] = buf.mom[o:o + sz].view_as(p)
-                    torch.autograd.graph.increment_version(p)     # written outside autograd: invalidate re-laid weight caches
+            if clip:
+                pending.append((buf, params, runs, lr, mom, wd))
+            else:
+                self._launch_runs(buf, params, runs, lr, mom, wd, None, None)
+        if pending:
+            # ONE norm over the runs the SGD launches cover: slots of parameters without a gradient hold stale data and are in no run
+            ranges = []
+            for buf, _, runs, *_ in pending:
+                for lo, hi, _ in runs:
+                    ranges.append(buf.grad[buf.offsets[lo]:buf.offsets[hi - 1] + (buf.sizes[hi - 1] + 3) // 4 * 4])
+            self._clip_buffers(ranges[0].device, sum(ops.grad_norm_slots(r.numel()) for r in ranges))
+            grad_scale, skip = self._clip_run(ranges, None)
+            for work in pending:
+                self._launch_runs(*work, grad_scale, skip)
         return loss
