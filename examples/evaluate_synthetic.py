@@ -3,11 +3,12 @@
 near zero; the loop is the point.
 
     python examples/evaluate_synthetic.py [--batches 4] [--batch 32] [--sweep] [--protocol voc|coco]
-                                          [--nms hard|linear|gaussian] [--keep-score 0.001]
+                                          [--nms hard|linear|gaussian] [--keep-score 0.001] [--ema]
 
 See INTEGRATION.md section 3c for the VOC devkit protocol (difficult flags) and the coordinate systems, section 3d for COCO's
 (crowd regions, area ranges in pixels, maxDets), section 3e for Soft-NMS (--nms; --keep-score: the decayed score below which a
-box is dropped, default = the candidate threshold 0.02).
+box is dropped, default = the candidate threshold 0.02).  --ema: take a few training steps with `optim.SGD(ema_decay=...)` first and
+score under `optimizer.ema_weights()`, the averaged weights swapped in place.
 """
 import argparse
 import os
@@ -46,11 +47,40 @@ def main():
     ap.add_argument("--protocol", choices=("voc", "coco"), default="voc", help="coco: the 81-column model and COCO's twelve numbers")
     ap.add_argument("--nms", choices=("hard", "linear", "gaussian"), default="hard", help="suppression rule of the decode")
     ap.add_argument("--keep-score", type=float, default=None, help="Soft-NMS: drop boxes whose decayed score falls below this")
+    ap.add_argument("--ema", action="store_true", help="voc protocol: three training steps with a weight EMA, then score with the averaged weights")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.protocol == "coco":
         return main_coco(a, dev)
     cnn = SSD_300().to(dev).eval()
+    if a.ema:
+        with averaged_weights(cnn, dev):
+            return score_voc(a, cnn, dev)
+    return score_voc(a, cnn, dev)
+
+
+def averaged_weights(cnn, dev, steps=3, bs=4):
+    """A few steps of the reference's optimizer set-up (train.py:44-55) with `ema_decay` -> the optimizer's `ema_weights()` context."""
+    from Losses import ssd
+    from objectdetection_ssd_amd.optim import SGD
+    biases = [p for n, p in cnn.named_parameters() if p.requires_grad and n.endswith(".bias")]
+    rest = [p for n, p in cnn.named_parameters() if p.requires_grad and not n.endswith(".bias")]
+    opt = SGD([{"params": biases, "lr": 2e-4}, {"params": rest}], lr=1e-4, momentum=0.9, weight_decay=5e-4, ema_decay=0.99)
+    rng, g = np.random.default_rng(1), torch.Generator().manual_seed(1)
+    cnn.train()
+    for _ in range(steps):
+        boxes, classes, _, offsets = ground_truth(bs, rng, dev)
+        off = offsets.tolist()
+        opt.zero_grad()
+        l1, l2 = ssd(cnn(torch.randn(bs, 3, 300, 300, generator=g).to(dev)), [classes[a:b].float() for a, b in zip(off, off[1:])],
+                     [boxes[a:b] for a, b in zip(off, off[1:])])
+        (l1 + l2).backward()
+        opt.step()
+    cnn.eval()
+    return opt.ema_weights()
+
+
+def score_voc(a, cnn, dev):
     ev = DetectionEvaluator(n_classes=20, iou_thresholds=COCO_IOU_THRESHOLDS if a.sweep else (0.5,), interpolation="all")
     rng = np.random.default_rng(0)
     g = torch.Generator().manual_seed(0)

@@ -1,6 +1,7 @@
 """Drop-in usage on synthetic data: the reference's training loop shape (train_function.py:59-95) on the gfx950 path.
 
     python examples/train_synthetic.py [--steps 20] [--batch 20] [--fused-sgd] [--grad-clip 10.0]
+                                       [--schedule none|multistep|cosine] [--warmup-steps 5] [--ema-decay 0.999]
 
 With the reference checked out next to this repo, the same three lines (`install_dropin()`, then
 `from train_function import train_model`) run its own `train_model` unchanged -- see INTEGRATION.md.
@@ -44,11 +45,28 @@ def main():
     ap.add_argument("--grad-clip", type=float, default=None, metavar="FLOAT",
                     help="clip the global gradient 2-norm to FLOAT inside the fused optimizer step and skip non-finite steps (implies "
                          "--fused-sgd; what torch.nn.utils.clip_grad_norm_ before optimizer.step() does, without leaving the device)")
+    ap.add_argument("--schedule", choices=("none", "multistep", "cosine"), default="none",
+                    help="a per-iteration learning-rate schedule over --steps, kept on the device (implies --fused-sgd): multistep drops "
+                         "the rate tenfold at 2/3 and 8/9 of the run, cosine anneals it to zero")
+    ap.add_argument("--warmup-steps", type=int, default=0, help="linear warm-up from a tenth of the rate over this many steps (with --schedule)")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
+                    help="keep an exponential moving average of the weights inside the optimizer step (implies --fused-sgd)")
     a = ap.parse_args()
-    clip = {}
+    opt_kw = {}
+    if a.schedule != "none" or a.warmup_steps or a.ema_decay is not None:
+        from objectdetection_ssd_amd.optim import LRSchedule
+        a.fused_sgd = True
+        if a.schedule == "multistep":
+            opt_kw["schedule"] = LRSchedule.multistep([a.steps * 2 // 3, a.steps * 8 // 9], total_steps=a.steps, warmup_steps=a.warmup_steps)
+        elif a.schedule == "cosine":
+            opt_kw["schedule"] = LRSchedule.cosine(max(a.steps, 1), warmup_steps=a.warmup_steps)
+        elif a.warmup_steps:
+            opt_kw["schedule"] = LRSchedule.constant(warmup_steps=a.warmup_steps)
+        if a.ema_decay is not None:
+            opt_kw["ema_decay"] = a.ema_decay
     if a.grad_clip is not None:
         a.fused_sgd = True
-        clip = dict(max_grad_norm=a.grad_clip, skip_nonfinite=True)
+        opt_kw.update(max_grad_norm=a.grad_clip, skip_nonfinite=True)
     device = torch.device("cuda")
     cnn = SSD_300().to(device)
     biases = [p for n, p in cnn.named_parameters() if p.requires_grad and n.endswith(".bias")]
@@ -59,7 +77,7 @@ def main():
     else:
         SGD = torch.optim.SGD
     optimizer = SGD(params=[{"params": biases, "lr": 2 * lr}, {"params": not_biases}], lr=lr, momentum=0.9,
-                    weight_decay=5e-4, **clip)              # train.py:53-55
+                    weight_decay=5e-4, **opt_kw)              # train.py:53-55
     cnn.train()
     t0 = time.time()
     for count, (inputs, classes, bboxes) in enumerate(batches(a.steps, a.batch, device)):
@@ -74,10 +92,18 @@ def main():
         optimizer.step()
         if count % 5 == 0:
             norm = ""
-            if clip:                                        # device values of the step just taken; reading them is this loop's sync
+            if "max_grad_norm" in opt_kw:                     # device values of the step just taken; reading them is this loop's sync
                 norm = (f"  |g| {optimizer.grad_norm.item():.3f}  clip {optimizer.clip_coef.item():.3f}"
                         f"  skipped {optimizer.skipped_steps.item()}")
+            if "schedule" in opt_kw or "ema_decay" in opt_kw:
+                norm += f"  lr {optimizer.current_lr[1].item():.3g}  ema_w {optimizer.ema_weight.item():.3g}"
             print(f"it {count:3d}  l1 {loss1.item():.4f}  l2 {loss2.item():.4f}{norm}  {time.time() - t0:.1f}s")
+    if "ema_decay" in opt_kw:                                 # evaluate with the averaged weights: swapped in place, and back
+        cnn.eval()
+        with torch.no_grad(), optimizer.ema_weights():
+            loc, _ = cnn(torch.randn(a.batch, 3, 300, 300, device=device))
+        cnn.train()
+        print(f"forward with the averaged weights: mean |loc| {loc.abs().mean().item():.4f}")
     torch.cuda.synchronize()
     print(f"{a.steps * a.batch / (time.time() - t0):.1f} images/s incl. host-side data generation")
 

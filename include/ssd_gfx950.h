@@ -638,6 +638,41 @@ int ssd_grad_clip_finalize(const double* partials, int n_slots, int norm_kind, f
 int ssd_sgd_momentum_guarded(float* param, const float* grad, float* momentum_buf, size_t n, float lr, float momentum,
                              float weight_decay, const float* grad_scale_dev, int first_step, const int* skip_dev, void* stream);
 
+/* ---- device-resident learning-rate schedule and weight EMA of the fused SGD step: what a per-iteration scheduler (warm-up, multistep,
+ * cosine) and an averaged copy of the weights add to the loop of train_function.py:80-95, with no host value that changes from step
+ * to step -- so a captured step replays under any schedule.  Every kernel is compiled without floating-point contraction.
+ *
+ * Schedule state: a block of 2 + G 4-byte words the caller zeroes once:
+ *   state[0] step (int32): optimizer steps actually taken;   state[1] ema_w (f32): the EMA weight of the current step;
+ *   state[2 .. 2+G) lr[g] (f32): the learning rate of parameter group g for the current step.
+ *
+ * ssd_sgd_schedule_advance: one workgroup.  *skip_dev != 0 (skip_dev may be NULL): writes nothing.  Otherwise, with t = state.step:
+ *   lr[g] = lr_table[g * T + min(t, T-1)]  (lr_table: G x T f32, row g = group g's rate at step 0 .. T-1; past the end the last holds);
+ *   ema_w = (float)(1 - d_t) computed in f64 from IEEE add / subtract / divide only, d_t = ema_warmup ? min(ema_decay, (1+t)/(10+t))
+ *           : ema_decay;  ema_decay < 0: no EMA, ema_w = 0;
+ *   step  = t + 1.
+ * No transcendental runs on the device: every schedule is a table the host built.  G <= 0, T <= 0 or ema_decay >= 1 / NaN:
+ * SSD_ERR_BAD_SHAPE.
+ *
+ * ssd_sgd_momentum_sched: ssd_sgd_momentum with lr = *lr_dev -- the same arithmetic and rounding sequence for param and
+ * momentum_buf -- that writes nothing when skip_dev != NULL and *skip_dev != 0.  ema != NULL: after the new p is formed (and not
+ * re-read), in f32, three separately rounded operations, no fma:  d = p - e;  m = *ema_w_dev * d;  e = e + m.  ema == NULL: no EMA
+ * (ema_w_dev may then be NULL).  Ranges that are all 16-byte aligned with n % 4 == 0 move as 16-byte accesses, anything else
+ * takes a scalar loop with the same results.  The grid is min(ceil(units / 256), 2048) workgroups of 256 threads, units = n / 4 (vector)
+ * or n (scalar).
+ *
+ * ssd_swap_f32: a[i] <-> b[i] for two DISJOINT ranges (overlap: SSD_ERR_BAD_SHAPE); the same vector / scalar choice.
+ *
+ * All three only enqueue on `stream` (graph-capturable); n == 0 is SSD_OK.  Errors: SSD_ERR_NULL for a missing state, lr_table, param,
+ * grad, momentum_buf, lr_dev, a or b, and for ema given without ema_w_dev; SSD_ERR_ALIGN for any pointer (skip_dev included) that is
+ * not 4-byte aligned -- 16-byte alignment is never required, it only selects the vector form. */
+int ssd_sgd_schedule_advance(void* state, const float* lr_table, int G, int T, double ema_decay, int ema_warmup, const int* skip_dev,
+                             void* stream);
+int ssd_sgd_momentum_sched(float* param, const float* grad, float* momentum_buf, float* ema, size_t n, const float* lr_dev,
+                           const float* ema_w_dev, float momentum, float weight_decay, const float* grad_scale_dev, int first_step,
+                           const int* skip_dev, void* stream);
+int ssd_swap_f32(float* a, float* b, size_t n, void* stream);
+
 /* ---- BatchNorm2d in training mode, Dropout / Dropout2d (SSD_resnet34 train mode: Model.py:24,56-70,72-126 and
  * torchvision's BasicBlock).  Tensors are [M][ld] f32 rows whose first C columns are the channels (M = N*H*W), C % 4 == 0,
  * ld % 4 == 0, rows 16-byte aligned.  Reductions use fixed-order slab partials (no atomics): results are bitwise reproducible.

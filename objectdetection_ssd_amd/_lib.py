@@ -201,6 +201,9 @@ SIGNATURES = {
     "ssd_grad_norm_partials": (_I, [_P, _Z, _I, _P, _I, _I, _P]),
     "ssd_grad_clip_finalize": (_I, [_P, _I, _I, _F, _P, _I, _P, _P]),
     "ssd_sgd_momentum_guarded": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P, _I, _P, _P]),
+    "ssd_sgd_schedule_advance": (_I, [_P, _P, _I, _I, C.c_double, _I, _P, _P]),
+    "ssd_sgd_momentum_sched": (_I, [_P, _P, _P, _P, _Z, _P, _P, _F, _F, _P, _I, _P, _P]),
+    "ssd_swap_f32": (_I, [_P, _P, _Z, _P]),
     "ssd_bn_workspace": (_Z, [_Z, _I]),
     "ssd_bn_train_stats": (_I, [_P, _I, _Z, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_bn_apply": (_I, [_P, _I, _Z, _I, _P, _P, _P, _I, _P, _P, _I, _I, _F, _U64, _I, _I, _P, _I, _P]),

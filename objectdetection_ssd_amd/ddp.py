@@ -15,6 +15,7 @@ decay applies to both groups, as torch.optim.SGD does there).
 """
 from __future__ import annotations
 
+import contextlib
 import weakref
 from typing import List, Optional
 
@@ -22,10 +23,10 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .optim import GradClipMixin
+from .optim import GradClipMixin, SchedEmaMixin
 
 
-class FlatSGDDataParallel(GradClipMixin, torch.optim.Optimizer):
+class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
     """The data-parallel optimizer of the step.  It IS a `torch.optim.Optimizer` with the two parameter groups of reference
     train.py:53-55 in the same order (`param_groups[0]` = biases at 2x lr, `param_groups[1]` = the rest), so the caller's
     `StepLR(optimizer, ...)` (train.py:57), `for g in optimizer.param_groups: g['lr'] = lr` (train_function.py:29-30),
@@ -36,7 +37,8 @@ class FlatSGDDataParallel(GradClipMixin, torch.optim.Optimizer):
     def __init__(self, model, lr: float = 1e-4, momentum: float = 0.9, weight_decay: float = 5e-4,
                  bias_lr_mult: float = 2.0, process_group=None, overlap: Optional[bool] = None, bucket_bytes: int = 16 << 20,
                  grad_dtype: torch.dtype = torch.float32, time_exchange: bool = False,
-                 max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False):
+                 max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False, schedule=None, ema_decay=None,
+                 ema_warmup: bool = True):
         """overlap: start the all-reduce of a slice of the flat gradient buffer as soon as the backward has produced all of it
         (asynchronous collectives on the process group's stream, `bucket_bytes` per slice), instead of one all-reduce after the
         backward.  Same sums, same result (bitwise: tests/test_ddp_gloo.py at world 2 / 4 / 8).  None (default) = overlapped whenever
@@ -56,8 +58,18 @@ class FlatSGDDataParallel(GradClipMixin, torch.optim.Optimizer):
         1 / n_pos_global, so every rank computes the same norm from the same bytes and no further collective is needed -- and skip a
         step whose norm is Inf or NaN (parameters and momentum untouched, `skipped_steps` counts it).  One streaming read of the
         gradient buffer and one finalise launch in front of the two SGD launches, all on the device; `grad_norm`, `clip_coef` and
-        `skipped_steps` are 0-dim device tensors, overwritten by the next step.  Plain attributes: they may be changed between steps."""
+        `skipped_steps` are 0-dim device tensors, overwritten by the next step.  Plain attributes: they may be changed between steps.
+
+        schedule (an `optim.LRSchedule`) / ema_decay / ema_warmup: a per-step learning rate read from a device table by a device step
+        counter, and an exponential moving average of the weights (`flat_ema`, the layout of `flat_param`) updated inside the two SGD
+        launches; one more single-workgroup launch per step (`optim.SchedEmaMixin`).  The groups' 'lr' stay the base rates.  Every rank
+        holds the same schedule state: the skip word that gates it is computed behind the all-reduce.  `current_lr`, `step_count` and
+        `ema_weight` are device views; `ema_parameters()` / `ema_weights()` reach the average."""
         self._init_clip(max_grad_norm, norm_type, skip_nonfinite)
+        self._init_sched(schedule, ema_decay, ema_warmup)
+        self.flat_ema = None
+        self.ema_views = None
+        self._ema_live = False           # a step has updated the EMA, or a checkpoint brought it
         self.model = model
         self.group = process_group
         if grad_dtype not in (torch.float32, torch.bfloat16):
@@ -129,6 +141,8 @@ class FlatSGDDataParallel(GradClipMixin, torch.optim.Optimizer):
         self._finalizer = weakref.finalize(self, FlatSGDDataParallel._detach, eng_ref, self._token)
         self.flat_grad16 = (torch.zeros(self.n_w, device=dev, dtype=torch.bfloat16) if grad_dtype == torch.bfloat16 else None)
         self._clip_prepare()
+        if self._sched_on():
+            self._sched_buffers(dev)     # (the EMA waits for the first step: the parameters may still be broadcast or loaded)
         # -- overlapped exchange: contiguous slices of the weight segment, filled from the back of the network first ------------
         self.overlap = bool(overlap)
         self._handles: list = []
@@ -228,11 +242,60 @@ class FlatSGDDataParallel(GradClipMixin, torch.optim.Optimizer):
             else:
                 self.flat_mom.zero_()
         self.steps = int(state_dict.get("flat_steps", self.steps)) if isinstance(state_dict, dict) else self.steps
+        self._sched_unstamp()
+        emas = [self.state.get(p, {}).get("ema") for p in self.params]
+        if any(e is not None for e in emas):
+            if not all(e is not None for e in emas):
+                raise ValueError("FlatSGDDataParallel.load_state_dict: weight averages for only some of the parameters")
+            self._make_ema(restored=emas)
+        elif self.flat_ema is not None:
+            self._make_ema()                                         # (the restored state has no averages: the views are attached again)
 
     def state_dict(self):
+        """torch's layout plus `flat_steps`; with the schedule or the EMA on, every group also carries `sched_step`, the device step
+        counter (reading it is the one synchronisation), and `state[p]['ema']` travels with the momentum buffers."""
         sd = super().state_dict()
         sd["flat_steps"] = self.steps
-        return sd
+        return self._sched_stamp(sd)
+
+    def _make_ema(self, restored=None) -> None:
+        """`flat_ema`: a copy of the parameters (or the averages of a restored checkpoint); `state[p]['ema']` are its views."""
+        with torch.no_grad():
+            if self.flat_ema is None:
+                self.flat_ema = self.flat_param.clone()
+                self.ema_views, off = [], 0
+                for p, sz, slot in zip(self.params, self._sizes, self._slots):
+                    self.ema_views.append(self.flat_ema[off:off + sz].view_as(p))
+                    off += slot
+            for i, (p, ev) in enumerate(zip(self.params, self.ema_views)):
+                if restored is not None:
+                    ev.copy_(restored[i].to(ev.device, torch.float32).reshape(ev.shape))
+                self.state[p]["ema"] = ev
+            if restored is not None:
+                self._ema_live = True
+
+    def ema_parameters(self):
+        """The averaged weights, one tensor per entry of `params` (weights, then biases): views of `flat_ema` (a copy of the
+        parameters until the first step with `ema_decay` set)."""
+        if self.flat_ema is None:
+            self._make_ema()
+        return iter(self.ema_views)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate with the averaged weights: `flat_param` and `flat_ema` change places, in place, on entry and again on exit; the
+        engine's weight cache is invalidated both times, as after a step."""
+        if self.flat_ema is None:
+            self._make_ema()
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+
+    def _swap_ema(self) -> None:
+        ops.swap_f32_(self.flat_param, self.flat_ema)
+        self.model._engine._wcache.clear()
 
     def step(self, closure=None):
         """`optimizer.step()` of the caller's loop = `apply_sgd()`; the gradient exchange (`reduce_gradients`) comes first."""
@@ -385,16 +448,46 @@ class FlatSGDDataParallel(GradClipMixin, torch.optim.Optimizer):
         self._clip_buffers(self.flat_grad.device, ops.grad_norm_slots(self.n))
         return True
 
+    def _sched_prepare(self) -> bool:
+        """Called by a step (and by the pre-capture hook of a graphed one, outside the capture).  Schedule or EMA switched on: make
+        sure the state block and the table of rates exist and follow the groups' base rates, and start the EMA -> True.  The
+        average starts as a copy of the parameters AT THE FIRST STEP: not in the constructor, which `broadcast_parameters()` or a
+        loaded checkpoint of the model may follow, and a buffer that `ema_parameters()` / `ema_weights()` made earlier is copied again."""
+        if not self._sched_on():
+            return False
+        self._sched_buffers(self.flat_param.device)
+        if self.ema_decay is not None and not self._ema_live:
+            if self.flat_ema is None:
+                self._make_ema()
+            else:
+                self.flat_ema.copy_(self.flat_param)
+            self._ema_live = True
+        return True
+
     def apply_sgd(self) -> None:
         first = not self._has_momentum
         gb, gw = self.param_groups
         for g in (gb, gw):
             if g.get("dampening", 0) != 0 or g.get("nesterov", False):
                 raise ValueError("FlatSGDDataParallel: dampening / nesterov are not part of the reference's step (train.py:53-55)")
-        if self._clip_prepare():
+        clip, sched = self._clip_prepare(), self._sched_prepare()
+        scale, skip = self.inv_npos, None
+        if clip:
             # the norm of flat_grad[:n] * inv_npos (count slot and pad excluded), read behind the all-reduce: the same on every rank.
             # (A skipped first step leaves the momentum at zero; momentum * 0 + g is the first-step form in value.)
             scale, skip = self._clip_run([self.flat_grad[:self.n]], self.inv_npos)
+        if sched:
+            # one advance (held still by the guard's skip word), then the two launches read their rate and the EMA weight from the block
+            self._sched_advance(skip if self.skip_nonfinite else None)
+            lr_words, ema_w = self._sched_words()
+            ema = self.flat_ema if self.ema_decay is not None else None
+            ops.sgd_momentum_sched_(self.flat_param[:self.n_w], self.flat_grad[:self.n_w], self.flat_mom[:self.n_w],
+                                    None if ema is None else ema[:self.n_w], lr_words[1:2], ema_w, float(gw["momentum"]),
+                                    float(gw["weight_decay"]), scale, first or gw["momentum"] == 0, skip)
+            ops.sgd_momentum_sched_(self.flat_param[self.n_w:], self.flat_grad[self.n_w:self.n], self.flat_mom[self.n_w:],
+                                    None if ema is None else ema[self.n_w:], lr_words[0:1], ema_w, float(gb["momentum"]),
+                                    float(gb["weight_decay"]), scale, first or gb["momentum"] == 0, skip)
+        elif clip:
             ops.sgd_momentum_guarded_(self.flat_param[:self.n_w], self.flat_grad[:self.n_w], self.flat_mom[:self.n_w],
                                       float(gw["lr"]), float(gw["momentum"]), float(gw["weight_decay"]), scale,
                                       first or gw["momentum"] == 0, skip)
@@ -461,9 +554,12 @@ class GraphedTrainStep:
     `apply_sgd` and so part of the captured step at one rank: a skipped replayed step leaves parameters and momentum untouched and
     bumps `trainer.skipped_steps` with no host involvement.  With more ranks they run eagerly behind the all-reduce, as the SGD does.
 
-    What forces a re-capture: a change of lr / momentum / weight decay of either group (StepLR), of the trainer's clip settings, of the world size, of the engine's
+    What forces a re-capture: a change of lr / momentum / weight decay of either group (StepLR), of the trainer's clip settings, of its
+    schedule object or EMA settings, of the world size, of the engine's
     stream placement (`overlap_tail`, `defer_tail_wgrad`), or of any engine setting in `_Engine.schedule_key()` (dtype mode, Winograd
-    and its thresholds, the fused and adjoint forms).  What a replay holds: the graph has baked in raw device pointers, so this object keeps,
+    and its thresholds, the fused and adjoint forms).  Under an `optim.LRSchedule` the groups' lr are the BASE rates, which no longer
+    change from step to step: the rate of a step is a device word that the captured advance launch takes from the trainer's table by
+    its device step counter, so a run under any per-iteration schedule, with or without the weight EMA, is captured once.  What a replay holds: the graph has baked in raw device pointers, so this object keeps,
     for as long as the graph lives, every workspace the capture was handed (`ops.capture_workspaces`) and, where the step lays out its
     filters through the batched weight table (`_Engine.uses_weight_table()`: the default), that table -- one more weight table and
     set of scratch buffers than the eager step holds.  Eager calls on the
@@ -561,7 +657,7 @@ class GraphedTrainStep:
         tr = self.trainer
         eng = self.net._engine
         return tuple((g["lr"], g["momentum"], g["weight_decay"]) for g in tr.param_groups) + (
-            tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + tr._clip_settings() + eng.schedule_key()
+            tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + tr._clip_settings() + tr._sched_settings() + eng.schedule_key()
 
     def _eager(self, x, classes, boxes):
         from . import Losses
@@ -614,6 +710,7 @@ class GraphedTrainStep:
         if self._static is None:
             self._make_static(x)
         tr._clip_prepare()                # (the clip's small buffers come into being here, never inside a capture)
+        tr._sched_prepare()               # (and the schedule block, the table of rates and the EMA buffer)
         self._load_batch(x, classes, boxes)
         if self.graph is None or self._sig != self._signature():
             self._capture()

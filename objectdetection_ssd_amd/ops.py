@@ -991,6 +991,49 @@ def sgd_momentum_guarded_(param, grad, buf, lr, momentum, weight_decay, grad_sca
           "sgd_momentum_guarded")
 
 
+SCHED_STATE_HEAD = 2           # step (int32), ema_w (f32), then one f32 lr word per parameter group: include/ssd_gfx950.h
+
+
+def sgd_schedule_advance_(state, lr_table, ema_decay=None, ema_warmup=True, skip=None):
+    """One step of the device schedule: state (int32[2 + G]) <- lr words from column min(step, T-1) of lr_table (f32 (G, T)), the EMA
+    weight of this step (ema_decay None: 0), step + 1.  skip: optional int32 device flag; when it is set nothing is written."""
+    _req(state, "state", torch.int32); _req(lr_table, "lr_table")
+    if lr_table.dim() != 2 or lr_table.shape[0] < 1 or lr_table.shape[1] < 1 or state.numel() < SCHED_STATE_HEAD + lr_table.shape[0]:
+        raise ValueError("sgd_schedule_advance_: lr_table must be (groups, steps) and state hold 2 + groups words")
+    if skip is not None:
+        _req(skip, "skip", torch.int32)
+    check(_lib.load().ssd_sgd_schedule_advance(state.data_ptr(), lr_table.data_ptr(), int(lr_table.shape[0]), int(lr_table.shape[1]),
+                                               -1.0 if ema_decay is None else float(ema_decay), int(bool(ema_warmup)), _ptr(skip),
+                                               _stream()), "sgd_schedule_advance")
+
+
+def sgd_momentum_sched_(param, grad, buf, ema, lr_dev, ema_w_dev, momentum, weight_decay, grad_scale=None, first_step=False, skip=None):
+    """`sgd_momentum_` whose learning rate is the device word `lr_dev`, that writes nothing when the device flag `skip` is set, and
+    that, given `ema`, moves it towards the new parameters by the device weight `ema_w_dev` in the same pass."""
+    _req(param, "param"); _req(grad, "grad"); _req(buf, "buf"); _req(lr_dev, "lr_dev")
+    if grad.numel() != param.numel() or buf.numel() != param.numel() or lr_dev.numel() < 1:
+        raise ValueError("sgd sizes")
+    if ema is not None:
+        _req(ema, "ema"); _req(ema_w_dev, "ema_w_dev")
+        if ema.numel() != param.numel() or ema_w_dev.numel() < 1:
+            raise ValueError("sgd sizes")
+    if grad_scale is not None:
+        _req(grad_scale, "grad_scale")
+    if skip is not None:
+        _req(skip, "skip", torch.int32)
+    check(_lib.load().ssd_sgd_momentum_sched(param.data_ptr(), grad.data_ptr(), buf.data_ptr(), _ptr(ema), param.numel(), lr_dev.data_ptr(),
+                                             _ptr(ema_w_dev) if ema is not None else None, float(momentum), float(weight_decay),
+                                             _ptr(grad_scale), int(first_step), _ptr(skip), _stream()), "sgd_momentum_sched")
+
+
+def swap_f32_(a, b):
+    """Exchange the contents of two disjoint f32 ranges of equal length, in place."""
+    _req(a, "a"); _req(b, "b")
+    if a.numel() != b.numel():
+        raise ValueError("swap_f32_: sizes")
+    check(_lib.load().ssd_swap_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), "swap_f32")
+
+
 def map_eval(det_boxes, det_classes, det_scores, det_start, gt_boxes, gt_classes, gt_start, recall_levels, n_classes=20):
     """Concatenated detections / ground truth (see include/ssd_gfx950.h ssd_map_eval) -> (table (n_classes, n_levels)
     float64, tp (D,) uint8, counts (2, n_classes) int32).  recall_levels: host sequence of floats."""

@@ -17,12 +17,18 @@ like the rest of the package.
 Gradient clipping and the non-finite step guard (`max_grad_norm`, `norm_type`, `skip_nonfinite`) are what a user of that loop
 adds with `torch.nn.utils.clip_grad_norm_` between `backward()` and `step()`: here they are one norm pass per launch range, one
 finalise launch and the guarded form of the same SGD kernel, and nothing comes back to the host (`GradClipMixin`).
+
+A per-iteration learning-rate schedule (`LRSchedule`: warm-up, multistep, cosine, polynomial) and an exponential moving average of
+the weights (`ema_decay`) live on the device too (`SchedEmaMixin`): the rate is a device word the SGD launch reads, a device step
+counter indexes a table of rates built on the host, and the average is updated in the pass SGD makes anyway.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import List
 
+import numpy as np
 import torch
 
 from . import ops
@@ -89,6 +95,192 @@ class GradClipMixin:
         return None if self._clip_state is None else self._clip_state.view(torch.int32)[4]
 
 
+class LRSchedule:
+    """A per-step learning-rate schedule as a table of factors: step t runs at `group['lr'] * factors[min(t, T-1)]` -- past the end the
+    last factor holds.  The factors are f64; group g's row of the device table is `float32(float64(group['lr']) * factors[t])`, one
+    rounding.  `param_groups[g]['lr']` stays the BASE rate (writing a new base rebuilds the table at the next step).  The factors are
+    copied and read-only: an optimizer and a captured step key their table by the identity of this object, so another schedule is
+    another `LRSchedule`.
+
+    The constructors are the closed forms of torch's schedulers times a linear warm-up: factor(t) = warm(t) * decay(t),
+    warm(t) = warmup_start + (1 - warmup_start) * t / warmup_steps for t < warmup_steps, else 1 (torch's LinearLR)."""
+
+    def __init__(self, factors) -> None:
+        try:
+            f = np.array(factors, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"LRSchedule: factors must be a sequence of numbers ({e})") from None
+        if f.size == 0:
+            raise ValueError("LRSchedule: an empty table")
+        if not np.all(np.isfinite(f)) or np.any(f < 0):
+            raise ValueError("LRSchedule: factors must be finite and non-negative")
+        f.setflags(write=False)
+        self.factors = f
+
+    def __len__(self) -> int:
+        return int(self.factors.size)
+
+    def factor(self, t: int) -> float:
+        return float(self.factors[min(max(int(t), 0), self.factors.size - 1)])
+
+    def table(self, base_lrs) -> np.ndarray:
+        """(groups, T) f32: the rows the device reads."""
+        return np.stack([(np.float64(lr) * self.factors).astype(np.float32) for lr in base_lrs])
+
+    @staticmethod
+    def _warm(t: int, warmup_steps: int, warmup_start: float) -> float:
+        if t >= warmup_steps:
+            return 1.0
+        return warmup_start + (1.0 - warmup_start) * t / warmup_steps
+
+    @classmethod
+    def _build(cls, decay, steps: int, warmup_steps: int, warmup_start: float) -> "LRSchedule":
+        if isinstance(warmup_steps, bool) or not isinstance(warmup_steps, int) or warmup_steps < 0:
+            raise ValueError(f"LRSchedule: warmup_steps must be a non-negative integer, got {warmup_steps!r}")
+        if not 0.0 < float(warmup_start) <= 1.0:
+            raise ValueError(f"LRSchedule: warmup_start must be in (0, 1], got {warmup_start!r}")
+        steps = max(int(steps), warmup_steps)
+        return cls([cls._warm(t, warmup_steps, float(warmup_start)) * decay(t) for t in range(steps + 1)])
+
+    @classmethod
+    def constant(cls, warmup_steps: int = 0, warmup_start: float = 0.1) -> "LRSchedule":
+        return cls._build(lambda t: 1.0, 0, warmup_steps, warmup_start)
+
+    @classmethod
+    def multistep(cls, milestones, gamma: float = 0.1, total_steps=None, warmup_steps: int = 0, warmup_start: float = 0.1) -> "LRSchedule":
+        """torch's MultiStepLR: the factor is multiplied by `gamma` at every milestone (once per occurrence)."""
+        ms = sorted(int(m) for m in milestones)
+        if any(m < 0 for m in ms):
+            raise ValueError("LRSchedule.multistep: milestones must be non-negative")
+        acc, out = 1.0, []
+        last = max(ms + [0])
+        for t in range(last + 1):
+            for _ in range(ms.count(t)):
+                acc = acc * gamma
+            out.append(acc)
+        return cls._build(lambda t: out[min(t, last)], last if total_steps is None else total_steps, warmup_steps, warmup_start)
+
+    @classmethod
+    def cosine(cls, total_steps: int, min_factor: float = 0.0, warmup_steps: int = 0, warmup_start: float = 0.1) -> "LRSchedule":
+        """torch's CosineAnnealingLR(T_max=total_steps, eta_min=min_factor * lr) up to total_steps; then `min_factor` holds."""
+        if int(total_steps) < 1:
+            raise ValueError("LRSchedule.cosine: total_steps must be positive")
+        T = int(total_steps)
+        return cls._build(lambda t: min_factor + (1.0 - min_factor) * 0.5 * (1.0 + math.cos(math.pi * min(t, T) / T)), T, warmup_steps,
+                          warmup_start)
+
+    @classmethod
+    def poly(cls, total_steps: int, power: float = 1.0, warmup_steps: int = 0, warmup_start: float = 0.1) -> "LRSchedule":
+        """torch's PolynomialLR(total_iters=total_steps, power)."""
+        if int(total_steps) < 1:
+            raise ValueError("LRSchedule.poly: total_steps must be positive")
+        T = int(total_steps)
+        return cls._build(lambda t: (1.0 - min(t, T) / T) ** power, T, warmup_steps, warmup_start)
+
+
+def check_sched_settings(schedule, ema_decay, ema_warmup) -> None:
+    if schedule is not None and not isinstance(schedule, LRSchedule):
+        raise ValueError(f"schedule must be None or an LRSchedule, got {type(schedule).__name__}")
+    if schedule is not None and len(schedule) == 0:
+        raise ValueError("schedule: an empty table")
+    if ema_decay is not None:
+        if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 < ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be None or a number in (0, 1), got {ema_decay!r}")
+    if not isinstance(ema_warmup, bool):
+        raise ValueError(f"ema_warmup must be a bool, got {ema_warmup!r}")
+
+
+class SchedEmaMixin:
+    """Settings, device state and launches of the device-resident learning-rate schedule and the weight EMA, shared by `optim.SGD` and
+    `ddp.FlatSGDDataParallel`.  `schedule`, `ema_decay` and `ema_warmup` are plain attributes read at every step.  The state block
+    (include/ssd_gfx950.h, ssd_sgd_schedule_advance: step counter, EMA weight, one lr word per group) lives on the device;
+    `current_lr`, `step_count` and `ema_weight` are views of it and never synchronise.  Order inside a step: the clip norm and
+    finalise (if on), ONE advance (given the clip's skip word when the guard is on, so a skipped step advances neither the counter
+    nor the EMA), the SGD launches, which read their rate and the EMA weight from the block."""
+
+    def _init_sched(self, schedule, ema_decay, ema_warmup) -> None:
+        check_sched_settings(schedule, ema_decay, ema_warmup)
+        self.schedule, self.ema_decay, self.ema_warmup = schedule, ema_decay, ema_warmup
+        self._sched_state = None          # int32[2 + G]
+        self._sched_table = None          # f32 (G, T)
+        self._sched_key = None            # (schedule, base lrs) the table was built from
+        self._sched_step0 = 0             # counter a restored checkpoint starts from, until the block exists
+
+    def _sched_on(self) -> bool:
+        check_sched_settings(self.schedule, self.ema_decay, self.ema_warmup)
+        return self.schedule is not None or self.ema_decay is not None
+
+    def _sched_settings(self):
+        return (self.schedule, self.ema_decay, self.ema_warmup)
+
+    def _sched_buffers(self, dev) -> None:
+        """The state block and the table of rates, built or rebuilt outside any capture: a new base lr or another schedule object is
+        written INTO the table's storage when the shape allows, so a captured step keeps reading the right memory."""
+        G = len(self.param_groups)
+        if self._sched_state is None or self._sched_state.device != dev or self._sched_state.numel() != ops.SCHED_STATE_HEAD + G:
+            old = self._sched_state
+            self._sched_state = torch.zeros(ops.SCHED_STATE_HEAD + G, device=dev, dtype=torch.int32)
+            if old is not None:                                    # (a parameter group was added: the counter goes on)
+                self._sched_state[0:1].copy_(old[0:1])
+            elif self._sched_step0:
+                self._sched_state[0:1].fill_(self._sched_step0)
+            self._sched_key = None
+        base = tuple(float(g["lr"]) for g in self.param_groups)
+        key = (self.schedule, base)
+        if self._sched_key is None or self._sched_key[0] is not key[0] or self._sched_key[1] != key[1]:
+            sch = self.schedule if self.schedule is not None else LRSchedule([1.0])      # the EMA alone: the one-column table of base lrs
+            host = torch.from_numpy(sch.table(base))
+            if self._sched_table is not None and self._sched_table.device == dev and self._sched_table.shape == host.shape:
+                self._sched_table.copy_(host)
+            else:
+                self._sched_table = host.to(dev)
+            self._sched_key = key
+
+    def _sched_advance(self, skip) -> None:
+        ops.sgd_schedule_advance_(self._sched_state, self._sched_table, self.ema_decay, self.ema_warmup, skip)
+
+    def _sched_words(self):
+        """(lr words f32[G], EMA weight f32[1]) as the SGD launches take them."""
+        f = self._sched_state.view(torch.float32)
+        return f[ops.SCHED_STATE_HEAD:], f[1:2]
+
+    def _sched_step_host(self) -> int:
+        """The counter, read back: the one synchronisation (checkpoints)."""
+        return int(self._sched_state[0].item()) if self._sched_state is not None else int(self._sched_step0)
+
+    def _sched_stamp(self, sd):
+        """state_dict(): with the feature on every param group carries `sched_step`, the device counter."""
+        if self._sched_on():
+            step = self._sched_step_host()
+            for g in sd["param_groups"]:
+                g["sched_step"] = step
+        return sd
+
+    def _sched_unstamp(self) -> None:
+        """load_state_dict(): take `sched_step` out of the restored groups and into the device counter."""
+        steps = [g.pop("sched_step", None) for g in self.param_groups]
+        steps = [s for s in steps if s is not None]
+        if steps:
+            self._sched_step0 = int(steps[0])
+            if self._sched_state is not None:
+                self._sched_state[0:1].fill_(self._sched_step0)
+
+    @property
+    def current_lr(self):
+        """f32[G] device tensor: the rate each group's last step ran at (None before the first step with the feature on)."""
+        return None if self._sched_state is None else self._sched_state.view(torch.float32)[ops.SCHED_STATE_HEAD:]
+
+    @property
+    def step_count(self):
+        """0-dim int32 device tensor: optimizer steps actually taken (skipped steps do not count)."""
+        return None if self._sched_state is None else self._sched_state[0]
+
+    @property
+    def ema_weight(self):
+        """0-dim f32 device tensor: 1 - decay of the last step, the weight the EMA moved towards the new parameters by."""
+        return None if self._sched_state is None else self._sched_state.view(torch.float32)[1]
+
+
 class _GroupBuffers:
     """Flat storage of one parameter group."""
 
@@ -105,6 +297,8 @@ class _GroupBuffers:
         self.param = torch.zeros(off, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(off, device=dev, dtype=torch.float32)
         self.mom = torch.zeros(off, device=dev, dtype=torch.float32)
+        self.ema = None                                            # the weight EMA, with the parameters' layout (`make_ema`)
+        self.ema_live = False                                      # a step has updated it, or a checkpoint brought it
         self.grad_views = []
         with torch.no_grad():
             for p, o, sz in zip(params, self.offsets, sizes):
@@ -118,19 +312,49 @@ class _GroupBuffers:
                     mv.copy_(st["momentum_buffer"])
                     st["momentum_buffer"] = mv
         self.ptrs = [p.data_ptr() for p in params]
+        if any(state.get(p) is not None and state[p].get("ema") is not None for p in params):      # a restored checkpoint
+            self.make_ema(params, state)
+
+    def make_ema(self, params, state) -> None:
+        """The EMA buffer: a copy of the parameters, except where the state already carries an average; `state[p]['ema']` become its views."""
+        self.ema = self.param.clone()
+        with torch.no_grad():
+            for p, o, sz in zip(params, self.offsets, self.sizes):
+                ev = self.ema[o:o + sz].view_as(p)
+                have = state[p].get("ema")
+                if have is not None:
+                    ev.copy_(have)
+                    self.ema_live = True
+                state[p]["ema"] = ev
+
+    def start_ema(self, params, state) -> None:
+        """Called by the step that is about to update the EMA: the average starts as a copy of the parameters AT THE FIRST STEP, so a
+        buffer that `ema_parameters()` / `ema_weights()` made earlier is copied again -- the parameters may have been loaded since."""
+        if self.ema is None:
+            self.make_ema(params, state)
+        elif not self.ema_live:
+            self.ema.copy_(self.param)
+        self.ema_live = True
 
     def seated(self, params) -> bool:
         return len(params) == len(self.ptrs) and all(p.data_ptr() == q for p, q in zip(params, self.ptrs))
 
 
-class SGD(GradClipMixin, torch.optim.Optimizer):
+class SGD(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
                  nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None,
-                 max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False):
+                 max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False, schedule=None, ema_decay=None,
+                 ema_warmup: bool = True):
         """max_grad_norm: clip the GLOBAL norm (`norm_type` 2 or inf) of every gradient of every group to it, as
         `torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm, norm_type)` before `step()` does.  skip_nonfinite: a step whose
-        gradient norm is Inf or NaN changes neither parameters nor momentum and counts into `skipped_steps`."""
+        gradient norm is Inf or NaN changes neither parameters nor momentum and counts into `skipped_steps`.
+
+        schedule: an `LRSchedule`; step t runs group g at float32(group['lr'] * schedule.factors[t]) read from a device table, the
+        groups' 'lr' stay the base rates.  ema_decay (in (0, 1)): keep an exponential moving average of every parameter,
+        e += (1 - d_t) * (p - e) after each step, d_t = min(ema_decay, (1 + t) / (10 + t)) with `ema_warmup`, else ema_decay;
+        `state[p]['ema']`, `ema_parameters()` and `ema_weights()` reach it.  A parameter takes part in the steps it has a gradient in."""
         self._init_clip(max_grad_norm, norm_type, skip_nonfinite)
+        self._init_sched(schedule, ema_decay, ema_warmup)
         if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
             raise ValueError("SGD: lr, momentum and weight_decay must be non-negative")
         if dampening != 0.0 or nesterov or maximize or differentiable:
@@ -146,9 +370,48 @@ class SGD(GradClipMixin, torch.optim.Optimizer):
         if hasattr(self, "_buffers"):
             self._buffers.append(None)
 
+    def state_dict(self):
+        """torch's layout; with the schedule or the EMA on, every group also carries `sched_step`, the device step counter (reading it
+        is the one synchronisation), and `state[p]['ema']` travels with the momentum buffers."""
+        return self._sched_stamp(super().state_dict())
+
     def load_state_dict(self, state_dict) -> None:
         super().load_state_dict(state_dict)
-        self._buffers = [None] * len(self.param_groups)           # restored momentum buffers are re-seated at the next step
+        self._buffers = [None] * len(self.param_groups)           # restored momentum and EMA buffers are re-seated at the next step
+        self._sched_unstamp()
+
+    def _seat_all(self) -> None:
+        for gi, group in enumerate(self.param_groups):
+            if group["params"]:
+                buf = self._group_buffers(gi, group["params"])
+                if buf.ema is None:
+                    buf.make_ema(group["params"], self.state)
+
+    def ema_parameters(self):
+        """The averaged weights, one tensor per parameter in `param_groups` order: views of the flat EMA buffers (a copy of the
+        parameters until the first step with `ema_decay` set)."""
+        self._seat_all()
+        for group in self.param_groups:
+            for p in group["params"]:
+                yield self.state[p]["ema"]
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate with the averaged weights: parameters and EMA change places, in place, on entry and again on exit."""
+        self._seat_all()
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+
+    def _swap_ema(self) -> None:
+        for buf, group in zip(self._buffers, self.param_groups):
+            if buf is None:
+                continue
+            ops.swap_f32_(buf.param, buf.ema)
+            for p in group["params"]:
+                torch.autograd.graph.increment_version(p)         # as a step does: invalidate re-laid weight caches
 
     def _group_buffers(self, gi: int, params) -> _GroupBuffers:
         buf = self._buffers[gi]
@@ -159,12 +422,20 @@ class SGD(GradClipMixin, torch.optim.Optimizer):
             buf = self._buffers[gi] = _GroupBuffers(params, self.state)
         return buf
 
-    def _launch_runs(self, buf, params, runs, lr, mom, wd, grad_scale, skip) -> None:
+    def _launch_runs(self, buf, params, runs, lr, mom, wd, grad_scale, skip, gi=None) -> None:
+        """gi: the group's index when the rate comes from the device schedule block (then `lr` is not read), else None."""
+        if gi is not None:
+            lr_words, ema_w = self._sched_words()
+            if self.ema_decay is not None:
+                buf.start_ema(params, self.state)
         for lo, hi, fresh in runs:
             a = buf.offsets[lo]
             b = buf.offsets[hi - 1] + (buf.sizes[hi - 1] + 3) // 4 * 4
             # momentum 0: torch keeps no buffer and steps with the gradient itself = the "first step" form of the kernel
-            if skip is None:
+            if gi is not None:
+                ops.sgd_momentum_sched_(buf.param[a:b], buf.grad[a:b], buf.mom[a:b], buf.ema[a:b] if self.ema_decay is not None else None,
+                                        lr_words[gi:gi + 1], ema_w, mom, wd, grad_scale, fresh or mom == 0.0, skip)
+            elif skip is None:
                 ops.sgd_momentum_(buf.param[a:b], buf.grad[a:b], buf.mom[a:b], lr, mom, wd, None, fresh or mom == 0.0)
             else:
                 ops.sgd_momentum_guarded_(buf.param[a:b], buf.grad[a:b], buf.mom[a:b], lr, mom, wd, grad_scale, fresh or mom == 0.0, skip)
@@ -183,7 +454,8 @@ class SGD(GradClipMixin, torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         clip = self._clip_on()
-        pending = []                                              # clipping: every group's runs wait for the one global norm
+        sched = self._sched_on()
+        pending = []                                              # clipping / schedule: every group's runs wait for the norm and the advance
         for gi, group in enumerate(self.param_groups):
             if group["dampening"] != 0 or group["nesterov"] or group.get("maximize", False):
                 raise ValueError("SGD: dampening / nesterov / maximize are not implemented")
@@ -211,18 +483,22 @@ class SGD(GradClipMixin, torch.optim.Optimizer):
             if not have:
                 continue
             torch._foreach_copy_([buf.grad_views[i] for i in have], [params[i].grad for i in have])
-            if clip:
-                pending.append((buf, params, runs, lr, mom, wd))
+            if clip or sched:
+                pending.append((buf, params, runs, lr, mom, wd, gi if sched else None))
             else:
                 self._launch_runs(buf, params, runs, lr, mom, wd, None, None)
-        if pending:
+        grad_scale = skip = None
+        if pending and clip:
             # ONE norm over the runs the SGD launches cover: slots of parameters without a gradient hold stale data and are in no run
             ranges = []
-            for buf, _, runs, *_ in pending:
+            for buf, _, runs, *_rest in pending:
                 for lo, hi, _ in runs:
                     ranges.append(buf.grad[buf.offsets[lo]:buf.offsets[hi - 1] + (buf.sizes[hi - 1] + 3) // 4 * 4])
             self._clip_buffers(ranges[0].device, sum(ops.grad_norm_slots(r.numel()) for r in ranges))
             grad_scale, skip = self._clip_run(ranges, None)
-            for work in pending:
-                self._launch_runs(*work, grad_scale, skip)
+        if pending and sched:
+            self._sched_buffers(pending[0][0].param.device)
+            self._sched_advance(skip if self.skip_nonfinite else None)
+        for buf, params, runs, lr, mom, wd, gi in pending:
+            self._launch_runs(buf, params, runs, lr, mom, wd, grad_scale, skip, gi)
         return loss
