@@ -490,6 +490,27 @@ int ssd_decode_nms_batch_soft(const float* l_, const float* c_, const float* pri
 int ssd_soft_nms_sorted(const float* s_boxes, const float* s_prob, const int32_t* cand_cnt, int B, int C1, int P, int method,
                         float iou_threshold, float sigma, float keep_score, int max_picks, int32_t* kept_pos, float* kept_prob,
                         int32_t* kept_cnt, void* stream);
+/* The greedy rule's kernel alone, launched exactly as the decode launches it, for tests and tools: the layout of
+ * ssd_soft_nms_sorted (cand_cnt[b * (C1 + 1) + c] <= P candidates per (image, class), in descending order of probability).  A kept
+ * box suppresses every later box with IoU >= iou_threshold (f32, inter / ((area_a + area_b) - inter); NaN is not >=).  Outputs per
+ * (image, class), in sorted order: kept_pos (B,C1,P) sorted positions of the survivors, kept_prob (B,C1,P) their probabilities
+ * (the bits of s_prob), kept_cnt (B, C1+1) their number.  iou_threshold is passed through unchecked, as the decode passes it.
+ * ssd_nms_plan (host only, no device needed) returns the launch decision for (B, C1, P): the block size (1024 where C1 * B <= 128,
+ * else 512) and chunk_words; a class of n candidates is resolved 64 rows at a time while 64 * ceil(n / 64) <= chunk_words and 32 rows
+ * at a time beyond.  SSD_ERR_BAD_SHAPE where the decode would refuse (P > 34752: 32 rows of all columns exceed the LDS). */
+int ssd_nms_plan(int B, int C1, int P, int* threads, int* chunk_words);
+int ssd_nms_sorted(const float* s_boxes, const float* s_prob, const int32_t* cand_cnt, int B, int C1, int P, float iou_threshold,
+                   int32_t* kept_pos, float* kept_prob, int32_t* kept_cnt, void* stream);
+/* The cross-class top-k of the decode alone, for tests and tools, on caller-made survivors: s_boxes (B,C1,P,4), s_idx (B,C1,P) prior
+ * ids, and per (image, class) the first kept_cnt[b * (C1 + 1) + c] entries of kept_pos (positions into the class's P slots) and
+ * kept_prob (positive probabilities); img_wh (B,2) device floats.  Outputs as ssd_decode_nms_batch (capacity top_k per image; slots
+ * past count are not written).  All survivors in class-major order if at most top_k, else the top_k largest probabilities, ties in
+ * class-major order, in descending order.  C1 = 1..255, top_k = 1..4096, P <= 100000; s_boxes, boxes and workspace 16-byte
+ * aligned.  workspace: two arrays of 4 * B * C1 * P bytes, each rounded up to a multiple of 256. */
+int ssd_topk_emit_sorted(const float* s_boxes, const int32_t* s_idx, const int32_t* kept_pos, const float* kept_prob,
+                         const int32_t* kept_cnt, const float* img_wh, int B, int C1, int P, int top_k, float* boxes,
+                         int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---- mAP evaluator (Util.py:783-885 get_map: per-class 11-point interpolated AP, IoU > 0.5, one claim per
  * ground-truth box, no 'difficult' handling) over B images given as concatenated arrays:

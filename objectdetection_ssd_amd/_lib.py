@@ -196,6 +196,9 @@ SIGNATURES = {
     "ssd_decode_nms_soft": (_I, [_P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _F, _F]),
     "ssd_decode_nms_batch_soft": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _F, _F]),
     "ssd_soft_nms_sorted": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P]),
+    "ssd_nms_plan": (_I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ssd_nms_sorted": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "ssd_topk_emit_sorted": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_sgd_momentum": (_I, [_P, _P, _P, _Z, _F, _F, _F, _P, _I, _P]),
     "ssd_grad_norm_slots": (_I, [_Z]),
     "ssd_grad_norm_partials": (_I, [_P, _Z, _I, _P, _I, _I, _P]),

@@ -690,6 +690,73 @@ static int launch_soft_nms(const float* s_boxes, const float* s_prob, const int3
     return SSD_OK;
 }
 
+// The greedy rule's launch decision, one place for the decode and for ssd_nms_sorted / ssd_nms_plan.
+// Block size and LDS by batch: a single image is a latency problem (20 workgroups on 256 CUs: 16 waves each, 64-row chunks wherever
+// the class's words fit the LDS); a batch is a throughput problem -- 8-wave workgroups with a 37 KB chunk buffer fit four to a CU, so
+// up to 1024 (image, class) problems are resident at once instead of two rounds of 512.  A class of n candidates (nw = ceil(n / 64)
+// words) runs 64-row chunks while 64 * nw <= chunk_words, 32-row chunks beyond; chunk_words always holds 32 rows of all P columns.
+struct NmsPlan { int threads, chunk_words; size_t lds; };
+static int nms_plan(int B, int C1, int P, NmsPlan* pl) {
+    if (B <= 0 || B > 65535 || C1 <= 0 || C1 > 255 || P <= 0 || P > 100000) return SSD_ERR_BAD_SHAPE;
+    const int nwcap = (P + 63) / 64;
+    const bool wide = (size_t)C1 * B <= 128;
+    int chunk_words = wide ? 64 * nwcap : (32 * nwcap > 4608 ? 32 * nwcap : 4608);
+    // 140 KB of LDS in all.  SSD300 (137 words): wide 8768, every class in 64-row chunks; batch 4608, 64-row chunks up to 4608 candidates of
+    // a class.  SSD512 (384 words): wide 17536 = the cap, 64-row chunks up to 17536 candidates; batch 12288, up to 12288 candidates.
+    const int cap_words = 140 * 1024 / 8 - nwcap;
+    if (chunk_words > cap_words) chunk_words = cap_words;
+    if (chunk_words < 32 * nwcap) return SSD_ERR_BAD_SHAPE;                // P > 34752: 32 rows of all columns do not fit
+    pl->threads = wide ? 1024 : 512;
+    pl->chunk_words = chunk_words;
+    pl->lds = (size_t)(nwcap + chunk_words) * 8;
+    return SSD_OK;
+}
+
+static int launch_nms(const float* s_boxes, const float* s_prob, const int32_t* cand_cnt, int B, int C1, int P, float iou_threshold,
+                      int32_t* kept_pos, uint32_t* kept_prob, int32_t* kept_cnt, hipStream_t st) {
+    NmsPlan pl;
+    const int rc = nms_plan(B, C1, P, &pl);
+    if (rc != SSD_OK) return rc;
+    if (pl.lds > 48 * 1024) {
+        static std::atomic<unsigned long long> raised{0};     // one bit per device (common.h): the attribute belongs to (kernel, device)
+        int dev;
+        if (ssd_attr_needed(raised, dev)) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
+                hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
+                return SSD_ERR_LAUNCH;
+            ssd_attr_done(raised, dev);
+        }
+    }
+    if (pl.threads == 1024)
+        hipLaunchKernelGGL(nms_kernel<1024>, dim3(C1, 1, B), dim3(1024), pl.lds, st, s_boxes, s_prob, cand_cnt, P, iou_threshold, pl.chunk_words, kept_pos,
+                           kept_prob, kept_cnt);
+    else
+        hipLaunchKernelGGL(nms_kernel<512>, dim3(C1, 1, B), dim3(512), pl.lds, st, s_boxes, s_prob, cand_cnt, P, iou_threshold, pl.chunk_words, kept_pos,
+                           kept_prob, kept_cnt);
+    SSD_CHECK_LAUNCH();
+    return SSD_OK;
+}
+
+// D5 as the decode launches it: one block per image, 64 KB of probability bits (kp_cap survivors) beside the 2 * top_k selection words.
+static int launch_topk(const float* s_boxes, const int32_t* s_idx, const uint32_t* kept_prob, const int32_t* kept_pos, const int32_t* kept_cnt,
+                       uint32_t* k_prob, int32_t* k_src, const float* img_wh, int B, int C1, int P, int top_k, float* boxes, int64_t* classes,
+                       float* probs, int32_t* prior_ids, int32_t* count, hipStream_t st) {
+    const int kp_cap = 16384;
+    {
+        static std::atomic<unsigned long long> raised{0};
+        int dev;
+        if (ssd_attr_needed(raised, dev)) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(topk_emit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
+                return SSD_ERR_LAUNCH;
+            ssd_attr_done(raised, dev);
+        }
+    }
+    TopkArgs ta{s_boxes, s_idx, kept_prob, kept_pos, kept_cnt, k_prob, k_src, P, C1, top_k, kp_cap, img_wh, boxes, classes, probs, prior_ids, count};
+    hipLaunchKernelGGL(topk_emit_kernel, dim3(1, 1, B), dim3(NB_T), (size_t)top_k * 8 + (size_t)kp_cap * 4, st, ta);
+    SSD_CHECK_LAUNCH();
+    return SSD_OK;
+}
+
 // D1, D3, then D4 (method 0: the greedy rule, nms_kernel) or D4s (method 1 / 2: Soft-NMS, soft_nms_kernel), then D5.
 static int decode_nms_batch_impl(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
                                  int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
@@ -744,48 +811,11 @@ static int decode_nms_batch_impl(const float* l_, const float* c_, const float* 
                                        w.kept_prob, w.kept_cnt, st);
         if (rc != SSD_OK) return rc;
     } else {
-        // Block size and LDS by batch: a single image is a latency problem (20 workgroups on 256 CUs: 16 waves each, 64-row chunks whatever
-        // the candidate count); a batch is a throughput problem -- 8-wave workgroups with a 37 KB chunk buffer fit four to a CU, so up to
-        // 1024 (image, class) problems are resident at once instead of two rounds of 512 (64-row chunks up to 4608 candidates per class).
-        const int nwcap = (P + 63) / 64;
-        const bool wide = (size_t)C1 * B <= 128;
-        int chunk_words = wide ? 64 * nwcap : (32 * nwcap > 4608 ? 32 * nwcap : 4608);
-        const int cap_words = 140 * 1024 / 8 - nwcap;                  // (SSD512's 24564 priors: 64-row chunks up to 4 480 candidates of a class)
-        if (chunk_words > cap_words) chunk_words = cap_words;
-        if (chunk_words < 32 * nwcap) return SSD_ERR_BAD_SHAPE;
-        const size_t lds = (size_t)(nwcap + chunk_words) * 8;
-        if (lds > 48 * 1024) {
-            static std::atomic<unsigned long long> raised{0};     // one bit per device (common.h): the attribute belongs to (kernel, device)
-            int dev;
-            if (ssd_attr_needed(raised, dev)) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
-                    return SSD_ERR_LAUNCH;
-                ssd_attr_done(raised, dev);
-            }
-        }
-        if (wide)
-            hipLaunchKernelGGL(nms_kernel<1024>, dim3(C1, 1, B), dim3(1024), lds, st, w.s_boxes, w.s_prob, w.cand_cnt, P, iou_threshold, chunk_words, w.kept_pos,
-                               w.kept_prob, w.kept_cnt);
-        else
-            hipLaunchKernelGGL(nms_kernel<512>, dim3(C1, 1, B), dim3(512), lds, st, w.s_boxes, w.s_prob, w.cand_cnt, P, iou_threshold, chunk_words, w.kept_pos,
-                               w.kept_prob, w.kept_cnt);
-        SSD_CHECK_LAUNCH();
+        const int rc = launch_nms(w.s_boxes, w.s_prob, w.cand_cnt, B, C1, P, iou_threshold, w.kept_pos, w.kept_prob, w.kept_cnt, st);
+        if (rc != SSD_OK) return rc;
     }
-    const int kp_cap = 16384;                                    // 64 KB of probability bits beside the 2 * top_k selection words
-    {
-        static std::atomic<unsigned long long> raised{0};
-        int dev;
-        if (ssd_attr_needed(raised, dev)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(topk_emit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-                return SSD_ERR_LAUNCH;
-            ssd_attr_done(raised, dev);
-        }
-    }
-    TopkArgs ta{w.s_boxes, w.s_idx, w.kept_prob, w.kept_pos, w.kept_cnt, w.k_prob, w.k_src, P, C1, top_k, kp_cap, img_wh, boxes, classes, probs, prior_ids, count};
-    hipLaunchKernelGGL(topk_emit_kernel, dim3(1, 1, B), dim3(NB_T), (size_t)top_k * 8 + (size_t)kp_cap * 4, st, ta);
-    SSD_CHECK_LAUNCH();
-    return SSD_OK;
+    return launch_topk(w.s_boxes, w.s_idx, w.kept_prob, w.kept_pos, w.kept_cnt, w.k_prob, w.k_src, img_wh, B, C1, P, top_k, boxes, classes, probs,
+                       prior_ids, count, st);
 }
 
 extern "C" int ssd_decode_nms_batch(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
@@ -847,4 +877,40 @@ extern "C" int ssd_soft_nms_sorted(const float* s_boxes, const float* s_prob, co
     if (!ssd_aligned16(s_boxes)) return SSD_ERR_ALIGN;
     return launch_soft_nms(s_boxes, s_prob, cand_cnt, B, C1, P, method, iou_threshold, sigma, keep_score, max_picks, kept_pos,
                            reinterpret_cast<uint32_t*>(kept_prob), kept_cnt, (hipStream_t)stream);
+}
+
+extern "C" int ssd_nms_plan(int B, int C1, int P, int* threads, int* chunk_words) {
+    if (!threads || !chunk_words) return SSD_ERR_NULL;
+    NmsPlan pl;
+    const int rc = nms_plan(B, C1, P, &pl);
+    if (rc != SSD_OK) return rc;
+    *threads = pl.threads;
+    *chunk_words = pl.chunk_words;
+    return SSD_OK;
+}
+
+extern "C" int ssd_nms_sorted(const float* s_boxes, const float* s_prob, const int32_t* cand_cnt, int B, int C1, int P, float iou_threshold,
+                              int32_t* kept_pos, float* kept_prob, int32_t* kept_cnt, void* stream) {
+    if (!s_boxes || !s_prob || !cand_cnt || !kept_pos || !kept_prob || !kept_cnt) return SSD_ERR_NULL;
+    if (B <= 0 || B > 65535 || C1 <= 0 || C1 > 255 || P <= 0 || P > 100000) return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(s_boxes)) return SSD_ERR_ALIGN;
+    return launch_nms(s_boxes, s_prob, cand_cnt, B, C1, P, iou_threshold, kept_pos, reinterpret_cast<uint32_t*>(kept_prob), kept_cnt,
+                      (hipStream_t)stream);
+}
+
+static size_t topk_half(int B, int C1, int P) { return ((size_t)B * C1 * P * 4 + 255) / 256 * 256; }
+extern "C" int ssd_topk_emit_sorted(const float* s_boxes, const int32_t* s_idx, const int32_t* kept_pos, const float* kept_prob,
+                                    const int32_t* kept_cnt, const float* img_wh, int B, int C1, int P, int top_k, float* boxes,
+                                    int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    if (!s_boxes || !s_idx || !kept_pos || !kept_prob || !kept_cnt || !img_wh || !boxes || !classes || !probs || !prior_ids || !count || !workspace)
+        return SSD_ERR_NULL;
+    if (B <= 0 || B > 65535 || C1 <= 0 || C1 > 255 || P <= 0 || P > 100000 || top_k <= 0 || top_k > 4096) return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(s_boxes) || !ssd_aligned16(boxes) || !ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
+    const size_t half = topk_half(B, C1, P);
+    if (workspace_bytes < 2 * half) return SSD_ERR_WORKSPACE;
+    char* ws = reinterpret_cast<char*>(workspace);
+    return launch_topk(s_boxes, s_idx, reinterpret_cast<const uint32_t*>(kept_prob), kept_pos, kept_cnt, reinterpret_cast<uint32_t*>(ws),
+                       reinterpret_cast<int32_t*>(ws + half), img_wh, B, C1, P, top_k, boxes, classes, probs, prior_ids, count,
+                       (hipStream_t)stream);
 }

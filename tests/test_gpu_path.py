@@ -645,8 +645,12 @@ def test_ssd512_build_defined_extension_vs_oracle():
 
 
 def test_decode_at_ssd512_prior_count():
-    """decode + NMS with 24564 priors (the NMS kernel then works in 32-row chunks: 64-row suppression words for that
-    many columns do not fit the LDS); inputs are drawn until every decision has a margin, as for the golden cases"""
+    """decode + NMS with 24564 priors: the SSD512 prior set through decode_compact, rank_scatter, the NMS kernel with 384 column
+    words (chunk_words at the LDS cap) and the top-k.  Random logits give about 660 candidates per class, which the kernel
+    resolves in 64-row chunks: the chunk mode follows the class's own candidate count, not P.  32-row chunks are covered by
+    tests/test_hard_nms_gpu.py (test_bare_greedy_32_row_chunks_single_image at this P, test_bare_greedy_32_row_chunks_in_a_batch,
+    test_decode_of_an_undertrained_net_runs_32_row_chunks).  Inputs are drawn until every decision has a margin, as for the
+    golden cases."""
     from objectdetection_ssd_amd import Losses
     pri = O.create_priors_ssd512()
     seed = 700

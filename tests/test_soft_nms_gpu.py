@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import soft_nms_ref as S
+from nms_cases import pack, random_class
 
 pytestmark = pytest.mark.gpu
 
@@ -28,32 +29,6 @@ def _t(a):
 
 
 # ---- the bare kernel ---------------------------------------------------------------------------------------------------------
-def random_class(rng, n, lo=0.05, size=(0.05, 0.3), quantum=None):
-    """n boxes (centres uniform in the unit square) and n descending scores; quantum: scores rounded to multiples of it (ties)."""
-    c = rng.uniform(0, 1, (n, 2))
-    wh = rng.uniform(size[0], size[1], (n, 2))
-    boxes = np.concatenate([c - wh / 2, c + wh / 2], 1).astype(np.float32)
-    s = rng.uniform(lo, 1.0, n)
-    if quantum:
-        s = np.maximum(np.round(s / quantum), 1) * quantum
-    return boxes, -np.sort(-s.astype(np.float32))
-
-
-def pack(classes, B, C1, P):
-    """classes[b][c] = (boxes (n,4), scores (n,)) -> s_boxes (B,C1,P,4), s_prob (B,C1,P), cand_cnt (B,C1+1); the slots past a
-    class's count are filled with values that would change the result if they were read as candidates"""
-    s_boxes = np.full((B, C1, P, 4), 0.5, np.float32)
-    s_boxes[..., 2:] = 0.9
-    s_prob = np.full((B, C1, P), 2.0, np.float32)
-    cnt = np.zeros((B, C1 + 1), np.int32)
-    for b in range(B):
-        for c in range(C1):
-            bx, sc = classes[b][c]
-            n = sc.shape[0]
-            s_boxes[b, c, :n], s_prob[b, c, :n], cnt[b, c] = bx, sc, n
-    return s_boxes, s_prob, cnt
-
-
 def run_bare(s_boxes, s_prob, cnt, method, thr, sigma, keep, max_picks):
     from objectdetection_ssd_amd import _lib
     lib = _lib.load()
