@@ -12,6 +12,11 @@ with a single collective.
 
 SGD follows train.py:44-55: momentum 0.9, weight decay 5e-4, biases at 2x lr (weight
 decay applies to both groups, as torch.optim.SGD does there).
+
+The flat buffers are one `optim.FlatStore` over weights-then-biases whose gradient buffer
+carries the count slot as a tail; the order inside a step (clip norm, finalise, schedule
+advance) and the choice of the SGD wrapper are `optim.FusedStepMixin._step_controls` and
+`optim.launch_sgd`, shared with `optim.SGD`.
 """
 from __future__ import annotations
 
@@ -23,10 +28,10 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .optim import GradClipMixin, SchedEmaMixin
+from .optim import FlatLayout, FlatStore, FusedStepMixin, launch_sgd
 
 
-class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
+class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
     """The data-parallel optimizer of the step.  It IS a `torch.optim.Optimizer` with the two parameter groups of reference
     train.py:53-55 in the same order (`param_groups[0]` = biases at 2x lr, `param_groups[1]` = the rest), so the caller's
     `StepLR(optimizer, ...)` (train.py:57), `for g in optimizer.param_groups: g['lr'] = lr` (train_function.py:29-30),
@@ -67,9 +72,6 @@ class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         `ema_weight` are device views; `ema_parameters()` / `ema_weights()` reach the average."""
         self._init_clip(max_grad_norm, norm_type, skip_nonfinite)
         self._init_sched(schedule, ema_decay, ema_warmup)
-        self.flat_ema = None
-        self.ema_views = None
-        self._ema_live = False           # a step has updated the EMA, or a checkpoint brought it
         self.model = model
         self.group = process_group
         if grad_dtype not in (torch.float32, torch.bfloat16):
@@ -90,26 +92,15 @@ class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         super().__init__([{"params": self.params[n_wn:], "lr": lr * bias_lr_mult}, {"params": self.params[:n_wn]}],
                          dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False))
         dev = self.params[0].device      # flat buffers live where the model lives (the SGD kernel itself is GPU-only)
-        sizes = [p.numel() for p in self.params]
-        slots = [(s + 3) // 4 * 4 for s in sizes]              # every parameter starts 16-byte aligned
-        self.n_w = sum(slots[:len(self.w_names)])
-        self.n = sum(slots)
-        pad = (-(self.n + 1)) % 64
-        self.flat_param = torch.zeros(self.n, device=dev, dtype=torch.float32)
-        self.flat_grad = torch.zeros(self.n + 1 + pad, device=dev, dtype=torch.float32)     # [grads | n_pos | pad]
-        self.flat_mom = torch.zeros(self.n, device=dev, dtype=torch.float32)
+        layout = FlatLayout(self.params)
+        self._sizes, self._slots, self._offs = layout.sizes, layout.slots, layout.offsets
+        self.n_w = layout.offsets[n_wn]
+        self.n = layout.total
+        # one store over weights-then-biases; the parameters now live in `flat_param`, and `flat_grad` is [grads | n_pos | pad]
+        self._store = store = FlatStore(self.params, layout, tail=1 + (-(self.n + 1)) % 64)
+        self.flat_param, self.flat_grad, self.flat_mom = store.param, store.grad, store.mom
+        self.grad_views, self.mom_views = store.grad_views, store.mom_views
         self.inv_npos = torch.ones(1, device=dev, dtype=torch.float32)
-        self.grad_views = []
-        self.mom_views = []
-        off = 0
-        with torch.no_grad():
-            for p, sz, slot in zip(self.params, sizes, slots):
-                view = self.flat_param[off:off + sz].view_as(p)
-                view.copy_(p.data)
-                p.data = view                                  # parameters now live in the flat buffer
-                self.grad_views.append(self.flat_grad[off:off + sz].view_as(p))
-                self.mom_views.append(self.flat_mom[off:off + sz].view_as(p))
-                off += slot
         self._has_momentum = False       # False: the next step starts the momentum buffer from the gradient, as torch.optim.SGD does
         self.steps = 0
         model._engine._wcache.clear()
@@ -117,10 +108,6 @@ class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         # gradient of a parameter (or of the two parameters a fused head convolution produces) goes and reports it through `_sink`;
         # the parameters' .grad are the views.  A gradient that arrives as a tensor of its own (conv1_1's permuted rows; a caller
         # that sets p.grad itself) is copied into its slot.
-        self._sizes, self._slots = sizes, slots
-        self._offs = [0]
-        for sl in slots:
-            self._offs.append(self._offs[-1] + sl)
         self._index = {n: i for i, n in enumerate(self.names)}
         self._view = dict(zip(self.names, self.grad_views))
         self._arrived: set = set()
@@ -230,26 +217,19 @@ class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         parameter name: `_from_reference_layout`)."""
         state_dict = self._from_reference_layout(state_dict)
         super().load_state_dict(state_dict)
-        have = [self.state.get(p, {}).get("momentum_buffer") for p in self.params]
-        if any(h is not None for h in have) and not all(h is not None for h in have):
+        mom = [self.state.get(p, {}).get("momentum_buffer") is not None for p in self.params]
+        if any(mom) and not all(mom):
             raise ValueError("FlatSGDDataParallel.load_state_dict: momentum buffers for only some of the parameters")
-        self._has_momentum = all(h is not None for h in have)
-        with torch.no_grad():
-            if self._has_momentum:
-                for p, h, mv in zip(self.params, have, self.mom_views):
-                    mv.copy_(h.to(mv.device, torch.float32).reshape(mv.shape))
-                    self.state[p]["momentum_buffer"] = mv
-            else:
+        ema = [self.state.get(p, {}).get("ema") is not None for p in self.params]
+        if any(ema) and not all(ema):
+            raise ValueError("FlatSGDDataParallel.load_state_dict: weight averages for only some of the parameters")
+        self._has_momentum = all(mom)
+        if not self._has_momentum:
+            with torch.no_grad():
                 self.flat_mom.zero_()
+        self._store.adopt(self.state)        # (an EMA the restored state has no averages for stays: its views are attached again)
         self.steps = int(state_dict.get("flat_steps", self.steps)) if isinstance(state_dict, dict) else self.steps
         self._sched_unstamp()
-        emas = [self.state.get(p, {}).get("ema") for p in self.params]
-        if any(e is not None for e in emas):
-            if not all(e is not None for e in emas):
-                raise ValueError("FlatSGDDataParallel.load_state_dict: weight averages for only some of the parameters")
-            self._make_ema(restored=emas)
-        elif self.flat_ema is not None:
-            self._make_ema()                                         # (the restored state has no averages: the views are attached again)
 
     def state_dict(self):
         """torch's layout plus `flat_steps`; with the schedule or the EMA on, every group also carries `sched_step`, the device step
@@ -258,27 +238,20 @@ class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         sd["flat_steps"] = self.steps
         return self._sched_stamp(sd)
 
-    def _make_ema(self, restored=None) -> None:
-        """`flat_ema`: a copy of the parameters (or the averages of a restored checkpoint); `state[p]['ema']` are its views."""
-        with torch.no_grad():
-            if self.flat_ema is None:
-                self.flat_ema = self.flat_param.clone()
-                self.ema_views, off = [], 0
-                for p, sz, slot in zip(self.params, self._sizes, self._slots):
-                    self.ema_views.append(self.flat_ema[off:off + sz].view_as(p))
-                    off += slot
-            for i, (p, ev) in enumerate(zip(self.params, self.ema_views)):
-                if restored is not None:
-                    ev.copy_(restored[i].to(ev.device, torch.float32).reshape(ev.shape))
-                self.state[p]["ema"] = ev
-            if restored is not None:
-                self._ema_live = True
+    @property
+    def flat_ema(self):
+        """The weight EMA with the layout of `flat_param` (None until a step, a checkpoint or `ema_parameters()` made it)."""
+        return self._store.ema
+
+    @property
+    def ema_views(self):
+        return self._store.ema_views
 
     def ema_parameters(self):
         """The averaged weights, one tensor per entry of `params` (weights, then biases): views of `flat_ema` (a copy of the
         parameters until the first step with `ema_decay` set)."""
         if self.flat_ema is None:
-            self._make_ema()
+            self._store.make_ema(self.state)
         return iter(self.ema_views)
 
     @contextlib.contextmanager
@@ -286,7 +259,7 @@ class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         """Evaluate with the averaged weights: `flat_param` and `flat_ema` change places, in place, on entry and again on exit; the
         engine's weight cache is invalidated both times, as after a step."""
         if self.flat_ema is None:
-            self._make_ema()
+            self._store.make_ema(self.state)
         self._swap_ema()
         try:
             yield self
@@ -456,12 +429,8 @@ class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         if not self._sched_on():
             return False
         self._sched_buffers(self.flat_param.device)
-        if self.ema_decay is not None and not self._ema_live:
-            if self.flat_ema is None:
-                self._make_ema()
-            else:
-                self.flat_ema.copy_(self.flat_param)
-            self._ema_live = True
+        if self.ema_decay is not None:
+            self._store.start_ema(self.state)
         return True
 
     def apply_sgd(self) -> None:
@@ -470,37 +439,17 @@ class FlatSGDDataParallel(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         for g in (gb, gw):
             if g.get("dampening", 0) != 0 or g.get("nesterov", False):
                 raise ValueError("FlatSGDDataParallel: dampening / nesterov are not part of the reference's step (train.py:53-55)")
-        clip, sched = self._clip_prepare(), self._sched_prepare()
-        scale, skip = self.inv_npos, None
-        if clip:
-            # the norm of flat_grad[:n] * inv_npos (count slot and pad excluded), read behind the all-reduce: the same on every rank.
-            # (A skipped first step leaves the momentum at zero; momentum * 0 + g is the first-step form in value.)
-            scale, skip = self._clip_run([self.flat_grad[:self.n]], self.inv_npos)
-        if sched:
-            # one advance (held still by the guard's skip word), then the two launches read their rate and the EMA weight from the block
-            self._sched_advance(skip if self.skip_nonfinite else None)
-            lr_words, ema_w = self._sched_words()
-            ema = self.flat_ema if self.ema_decay is not None else None
-            ops.sgd_momentum_sched_(self.flat_param[:self.n_w], self.flat_grad[:self.n_w], self.flat_mom[:self.n_w],
-                                    None if ema is None else ema[:self.n_w], lr_words[1:2], ema_w, float(gw["momentum"]),
-                                    float(gw["weight_decay"]), scale, first or gw["momentum"] == 0, skip)
-            ops.sgd_momentum_sched_(self.flat_param[self.n_w:], self.flat_grad[self.n_w:self.n], self.flat_mom[self.n_w:],
-                                    None if ema is None else ema[self.n_w:], lr_words[0:1], ema_w, float(gb["momentum"]),
-                                    float(gb["weight_decay"]), scale, first or gb["momentum"] == 0, skip)
-        elif clip:
-            ops.sgd_momentum_guarded_(self.flat_param[:self.n_w], self.flat_grad[:self.n_w], self.flat_mom[:self.n_w],
-                                      float(gw["lr"]), float(gw["momentum"]), float(gw["weight_decay"]), scale,
-                                      first or gw["momentum"] == 0, skip)
-            ops.sgd_momentum_guarded_(self.flat_param[self.n_w:], self.flat_grad[self.n_w:self.n], self.flat_mom[self.n_w:],
-                                      float(gb["lr"]), float(gb["momentum"]), float(gb["weight_decay"]), scale,
-                                      first or gb["momentum"] == 0, skip)
-        else:
-            ops.sgd_momentum_(self.flat_param[:self.n_w], self.flat_grad[:self.n_w], self.flat_mom[:self.n_w],
-                              float(gw["lr"]), float(gw["momentum"]), float(gw["weight_decay"]), self.inv_npos,
-                              first or gw["momentum"] == 0)
-            ops.sgd_momentum_(self.flat_param[self.n_w:], self.flat_grad[self.n_w:self.n], self.flat_mom[self.n_w:],
-                              float(gb["lr"]), float(gb["momentum"]), float(gb["weight_decay"]), self.inv_npos,
-                              first or gb["momentum"] == 0)
+        self._clip_prepare()
+        sched = self._sched_prepare()
+        # the norm of flat_grad[:n] * inv_npos (count slot and pad excluded), read behind the all-reduce: the same on every rank.
+        # (A skipped first step leaves the momentum at zero; momentum * 0 + g is the first-step form in value.)
+        scale, skip, lr_words, ema_w = self._step_controls([self.flat_grad[:self.n]], self.inv_npos)
+        ema = self.flat_ema if self.ema_decay is not None else None
+        for gi, g, seg in ((1, gw, slice(0, self.n_w)), (0, gb, slice(self.n_w, self.n))):       # weights, then biases
+            launch_sgd(self.flat_param[seg], self.flat_grad[seg], self.flat_mom[seg], lr=float(g["lr"]),
+                       lr_dev=lr_words[gi:gi + 1] if sched else None, ema=None if ema is None else ema[seg], ema_w=ema_w,
+                       momentum=float(g["momentum"]), weight_decay=float(g["weight_decay"]), grad_scale=scale,
+                       first=first or g["momentum"] == 0, skip=skip)
         if first and (gw["momentum"] != 0 or gb["momentum"] != 0):
             for p, mv in zip(self.params, self.mom_views):
                 self.state[p]["momentum_buffer"] = mv          # torch.optim.SGD's state layout: checkpoints carry the momentum

@@ -11,6 +11,13 @@ param-group keys, same `state[p]['momentum_buffer']` entries, so checkpoints mov
 are re-seated as views of one buffer the first time `step()` sees them, gradients are gathered with one foreach copy.
 The kernel reproduces torch's rounding sequence, so the parameters after k steps are bit-identical to torch.optim.SGD's.
 
+This module is also where the pieces that `SGD` shares with `ddp.FlatSGDDataParallel` exist once: `FlatLayout` (the slot rule of a
+flat buffer), `FlatStore` (the flat parameter / gradient / momentum / EMA buffers of one layout, their views and the EMA's life
+cycle; `SGD` keeps one per parameter group, the trainer one over all its parameters), `FusedStepMixin._step_controls` (the order
+inside a step: clip norm and finalise, ONE schedule advance, and the device words the SGD launches then read) and `launch_sgd`
+(the choice between the plain, guarded and scheduled SGD wrappers).  What differs stays with each optimizer: how gradients reach the
+flat buffer, which ranges are launched, and the momentum bookkeeping.
+
 Only what the reference uses is implemented: `dampening`, `nesterov`, `maximize` must stay at their defaults.  GPU only,
 like the rest of the package.
 
@@ -68,16 +75,6 @@ class GradClipMixin:
             self._clip_state = torch.zeros(ops.GRAD_CLIP_STATE_WORDS, device=dev, dtype=torch.float32)
         if self._clip_partials is None or self._clip_partials.device != dev or self._clip_partials.numel() < slots:
             self._clip_partials = torch.zeros(max(slots, 1), device=dev, dtype=torch.float64)
-
-    def _clip_run(self, ranges, pre_scale):
-        """Norm of the flat f32 ranges (one partials launch each), one finalise -> (grad_scale, skip): the device words the guarded
-        SGD launches read."""
-        s = 0
-        for r in ranges:
-            s = ops.grad_norm_partials_(r, self._clip_partials, s, self.norm_type)
-        ops.grad_clip_finalize_(self._clip_partials, s, self.norm_type, self.max_grad_norm, pre_scale, self.skip_nonfinite,
-                                self._clip_state)
-        return self._clip_state[2:3], self._clip_state.view(torch.int32)[3:4]
 
     @property
     def grad_norm(self):
@@ -194,9 +191,7 @@ class SchedEmaMixin:
     """Settings, device state and launches of the device-resident learning-rate schedule and the weight EMA, shared by `optim.SGD` and
     `ddp.FlatSGDDataParallel`.  `schedule`, `ema_decay` and `ema_warmup` are plain attributes read at every step.  The state block
     (include/ssd_gfx950.h, ssd_sgd_schedule_advance: step counter, EMA weight, one lr word per group) lives on the device;
-    `current_lr`, `step_count` and `ema_weight` are views of it and never synchronise.  Order inside a step: the clip norm and
-    finalise (if on), ONE advance (given the clip's skip word when the guard is on, so a skipped step advances neither the counter
-    nor the EMA), the SGD launches, which read their rate and the EMA weight from the block."""
+    `current_lr`, `step_count` and `ema_weight` are views of it and never synchronise."""
 
     def _init_sched(self, schedule, ema_decay, ema_warmup) -> None:
         check_sched_settings(schedule, ema_decay, ema_warmup)
@@ -236,14 +231,6 @@ class SchedEmaMixin:
                 self._sched_table = host.to(dev)
             self._sched_key = key
 
-    def _sched_advance(self, skip) -> None:
-        ops.sgd_schedule_advance_(self._sched_state, self._sched_table, self.ema_decay, self.ema_warmup, skip)
-
-    def _sched_words(self):
-        """(lr words f32[G], EMA weight f32[1]) as the SGD launches take them."""
-        f = self._sched_state.view(torch.float32)
-        return f[ops.SCHED_STATE_HEAD:], f[1:2]
-
     def _sched_step_host(self) -> int:
         """The counter, read back: the one synchronisation (checkpoints)."""
         return int(self._sched_state[0].item()) if self._sched_state is not None else int(self._sched_step0)
@@ -281,66 +268,124 @@ class SchedEmaMixin:
         return None if self._sched_state is None else self._sched_state.view(torch.float32)[1]
 
 
-class _GroupBuffers:
-    """Flat storage of one parameter group."""
+class FusedStepMixin(GradClipMixin, SchedEmaMixin):
+    """What both optimizers run between the gradients and the SGD launches."""
 
-    def __init__(self, params: List[torch.nn.Parameter], state) -> None:
+    def _step_controls(self, ranges, pre_scale=None):
+        """The device words this step's SGD launches read -> (grad_scale, skip, lr_words, ema_w); each is None when its feature is off
+        (grad_scale is then `pre_scale`).  Order: with clipping or the guard on, the norm of the flat f32 gradient `ranges` (one
+        partials launch each) times `pre_scale` and one finalise; with the schedule or the EMA on, ONE advance, given the skip word
+        only when the guard is on, so a skipped step advances neither the counter nor the EMA.  The buffers exist already
+        (`_clip_buffers`, `_sched_buffers`: never inside a capture)."""
+        grad_scale, skip, lr_words, ema_w = pre_scale, None, None, None
+        if self._clip_on():
+            s = 0
+            for r in ranges:
+                s = ops.grad_norm_partials_(r, self._clip_partials, s, self.norm_type)
+            ops.grad_clip_finalize_(self._clip_partials, s, self.norm_type, self.max_grad_norm, pre_scale, self.skip_nonfinite,
+                                    self._clip_state)
+            grad_scale, skip = self._clip_state[2:3], self._clip_state.view(torch.int32)[3:4]
+        if self._sched_on():
+            ops.sgd_schedule_advance_(self._sched_state, self._sched_table, self.ema_decay, self.ema_warmup,
+                                      skip if self.skip_nonfinite else None)
+            f = self._sched_state.view(torch.float32)
+            lr_words, ema_w = f[ops.SCHED_STATE_HEAD:], f[1:2]          # f32[G], f32[1]
+        return grad_scale, skip, lr_words, ema_w
+
+
+def launch_sgd(param, grad, buf, *, lr, lr_dev, ema, ema_w, momentum, weight_decay, grad_scale, first, skip) -> None:
+    """One fused SGD launch over equally long flat slices: the only caller of the three wrappers.  With the device rate `lr_dev` the
+    scheduled form (which also updates `ema`, if given, by the device weight `ema_w`); else, with the device flag `skip`, the guarded
+    form at the host rate `lr`; else the plain one."""
+    if lr_dev is not None:
+        ops.sgd_momentum_sched_(param, grad, buf, ema, lr_dev, ema_w, momentum, weight_decay, grad_scale, first, skip)
+    elif skip is not None:
+        ops.sgd_momentum_guarded_(param, grad, buf, lr, momentum, weight_decay, grad_scale, first, skip)
+    else:
+        ops.sgd_momentum_(param, grad, buf, lr, momentum, weight_decay, grad_scale, first)
+
+
+class FlatLayout:
+    """Where each parameter sits in a flat f32 buffer.  Every parameter starts 16-byte aligned: its slot is its size rounded up to a
+    multiple of 4 floats, and `offsets` (one more entry than there are parameters) are the running sums of the slots."""
+
+    def __init__(self, params) -> None:
+        self.shapes = [p.shape for p in params]
+        self.sizes = [p.numel() for p in params]
+        self.slots = [(s + 3) // 4 * 4 for s in self.sizes]
+        self.offsets = [0]
+        for s in self.slots:
+            self.offsets.append(self.offsets[-1] + s)
+        self.total = self.offsets[-1]
+
+    def views(self, flat) -> list:
+        """One view of `flat` per parameter, in its shape."""
+        return [flat[o:o + sz].view(shape) for o, sz, shape in zip(self.offsets, self.sizes, self.shapes)]
+
+    def span(self, lo: int, hi: int) -> slice:
+        """The floats of parameters lo .. hi-1, the last one's pad included."""
+        return slice(self.offsets[lo], self.offsets[hi])
+
+
+class FlatStore:
+    """The flat `param`, `grad`, `mom` and (once asked for) `ema` buffers of one `FlatLayout`, and their per-parameter views.  The
+    parameters are seated in `param` (`p.data` become its views); `grad` has `tail` more words behind the last slot."""
+
+    def __init__(self, params, layout: FlatLayout, tail: int = 0) -> None:
         dev = params[0].device
-        sizes = [p.numel() for p in params]
-        slots = [(s + 3) // 4 * 4 for s in sizes]                  # every parameter starts 16-byte aligned
-        self.offsets, off = [], 0
-        for s in slots:
-            self.offsets.append(off)
-            off += s
-        self.total = off
-        self.sizes = sizes
-        self.param = torch.zeros(off, device=dev, dtype=torch.float32)
-        self.grad = torch.zeros(off, device=dev, dtype=torch.float32)
-        self.mom = torch.zeros(off, device=dev, dtype=torch.float32)
-        self.ema = None                                            # the weight EMA, with the parameters' layout (`make_ema`)
+        self.params, self.layout = list(params), layout
+        self.param = torch.zeros(layout.total, device=dev, dtype=torch.float32)
+        self.grad = torch.zeros(layout.total + tail, device=dev, dtype=torch.float32)
+        self.mom = torch.zeros(layout.total, device=dev, dtype=torch.float32)
+        self.grad_views, self.mom_views = layout.views(self.grad), layout.views(self.mom)
+        self.ema = self.ema_views = None                           # the weight EMA, with the parameters' layout (`make_ema`)
         self.ema_live = False                                      # a step has updated it, or a checkpoint brought it
-        self.grad_views = []
         with torch.no_grad():
-            for p, o, sz in zip(params, self.offsets, sizes):
-                view = self.param[o:o + sz].view_as(p)
+            for p, view in zip(self.params, layout.views(self.param)):
                 view.copy_(p.data)
                 p.data = view
-                self.grad_views.append(self.grad[o:o + sz].view_as(p))
-                st = state.get(p)
-                if st is not None and st.get("momentum_buffer") is not None:
-                    mv = self.mom[o:o + sz].view_as(p)
-                    mv.copy_(st["momentum_buffer"])
-                    st["momentum_buffer"] = mv
-        self.ptrs = [p.data_ptr() for p in params]
-        if any(state.get(p) is not None and state[p].get("ema") is not None for p in params):      # a restored checkpoint
-            self.make_ema(params, state)
-
-    def make_ema(self, params, state) -> None:
-        """The EMA buffer: a copy of the parameters, except where the state already carries an average; `state[p]['ema']` become its views."""
-        self.ema = self.param.clone()
-        with torch.no_grad():
-            for p, o, sz in zip(params, self.offsets, self.sizes):
-                ev = self.ema[o:o + sz].view_as(p)
-                have = state[p].get("ema")
-                if have is not None:
-                    ev.copy_(have)
-                    self.ema_live = True
-                state[p]["ema"] = ev
-
-    def start_ema(self, params, state) -> None:
-        """Called by the step that is about to update the EMA: the average starts as a copy of the parameters AT THE FIRST STEP, so a
-        buffer that `ema_parameters()` / `ema_weights()` made earlier is copied again -- the parameters may have been loaded since."""
-        if self.ema is None:
-            self.make_ema(params, state)
-        elif not self.ema_live:
-            self.ema.copy_(self.param)
-        self.ema_live = True
+        self.ptrs = [p.data_ptr() for p in self.params]
 
     def seated(self, params) -> bool:
         return len(params) == len(self.ptrs) and all(p.data_ptr() == q for p, q in zip(params, self.ptrs))
 
+    def adopt(self, state) -> None:
+        """Take over what a checkpoint (or the store these parameters lived in before) left in the optimizer's `state`: momentum
+        buffers are copied into `mom` and replaced by its views, and so are the averages, if there are any."""
+        with torch.no_grad():
+            for p, mv in zip(self.params, self.mom_views):
+                have = state.get(p, {}).get("momentum_buffer")
+                if have is not None:
+                    mv.copy_(have.to(mv.device, torch.float32).reshape(mv.shape))
+                    state[p]["momentum_buffer"] = mv
+        emas = [state.get(p, {}).get("ema") for p in self.params]
+        if self.ema is not None or any(e is not None for e in emas):
+            self.make_ema(state, emas)
 
-class SGD(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
+    def make_ema(self, state, restored=None) -> None:
+        """The EMA buffer: a copy of the parameters, except where `restored` (one entry per parameter, or None) brings an average;
+        `state[p]['ema']` become its views."""
+        with torch.no_grad():
+            if self.ema is None:
+                self.ema = self.param.clone()
+                self.ema_views = self.layout.views(self.ema)
+            for i, (p, ev) in enumerate(zip(self.params, self.ema_views)):
+                if restored is not None and restored[i] is not None:
+                    ev.copy_(restored[i].to(ev.device, torch.float32).reshape(ev.shape))
+                    self.ema_live = True
+                state[p]["ema"] = ev
+
+    def start_ema(self, state) -> None:
+        """Called by the step that is about to update the EMA: the average starts as a copy of the parameters AT THE FIRST STEP, so a
+        buffer that `ema_parameters()` / `ema_weights()` made earlier is copied again -- the parameters may have been loaded since."""
+        if self.ema is None:
+            self.make_ema(state)
+        elif not self.ema_live:
+            self.ema.copy_(self.param)
+        self.ema_live = True
+
+
+class SGD(FusedStepMixin, torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
                  nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None,
                  max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False, schedule=None, ema_decay=None,
@@ -363,7 +408,7 @@ class SGD(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         defaults = dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False, maximize=False,
                         foreach=foreach, differentiable=False, fused=fused)
         super().__init__(params, defaults)
-        self._buffers: List[_GroupBuffers | None] = [None] * len(self.param_groups)
+        self._buffers: List[FlatStore | None] = [None] * len(self.param_groups)       # one store per parameter group
 
     def add_param_group(self, param_group) -> None:
         super().add_param_group(param_group)
@@ -385,7 +430,7 @@ class SGD(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
             if group["params"]:
                 buf = self._group_buffers(gi, group["params"])
                 if buf.ema is None:
-                    buf.make_ema(group["params"], self.state)
+                    buf.make_ema(self.state)
 
     def ema_parameters(self):
         """The averaged weights, one tensor per parameter in `param_groups` order: views of the flat EMA buffers (a copy of the
@@ -413,39 +458,15 @@ class SGD(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
             for p in group["params"]:
                 torch.autograd.graph.increment_version(p)         # as a step does: invalidate re-laid weight caches
 
-    def _group_buffers(self, gi: int, params) -> _GroupBuffers:
+    def _group_buffers(self, gi: int, params) -> FlatStore:
         buf = self._buffers[gi]
         if buf is None or not buf.seated(params):                 # first step, or the caller moved / replaced the tensors
             for p in params:
                 if p.dtype != torch.float32 or p.device.type != "cuda" or not p.is_contiguous():
                     raise ValueError("SGD: parameters must be contiguous float32 tensors on the GPU")
-            buf = self._buffers[gi] = _GroupBuffers(params, self.state)
+            buf = self._buffers[gi] = FlatStore(params, FlatLayout(params))
+            buf.adopt(self.state)                                 # restored momentum and EMA buffers
         return buf
-
-    def _launch_runs(self, buf, params, runs, lr, mom, wd, grad_scale, skip, gi=None) -> None:
-        """gi: the group's index when the rate comes from the device schedule block (then `lr` is not read), else None."""
-        if gi is not None:
-            lr_words, ema_w = self._sched_words()
-            if self.ema_decay is not None:
-                buf.start_ema(params, self.state)
-        for lo, hi, fresh in runs:
-            a = buf.offsets[lo]
-            b = buf.offsets[hi - 1] + (buf.sizes[hi - 1] + 3) // 4 * 4
-            # momentum 0: torch keeps no buffer and steps with the gradient itself = the "first step" form of the kernel
-            if gi is not None:
-                ops.sgd_momentum_sched_(buf.param[a:b], buf.grad[a:b], buf.mom[a:b], buf.ema[a:b] if self.ema_decay is not None else None,
-                                        lr_words[gi:gi + 1], ema_w, mom, wd, grad_scale, fresh or mom == 0.0, skip)
-            elif skip is None:
-                ops.sgd_momentum_(buf.param[a:b], buf.grad[a:b], buf.mom[a:b], lr, mom, wd, None, fresh or mom == 0.0)
-            else:
-                ops.sgd_momentum_guarded_(buf.param[a:b], buf.grad[a:b], buf.mom[a:b], lr, mom, wd, grad_scale, fresh or mom == 0.0, skip)
-            for i in range(lo, hi):
-                p = params[i]
-                if mom != 0.0 and fresh:
-                    # (a skipped first step leaves the buffer at zero: momentum * 0 + g is the first-step form in value)
-                    o, sz = buf.offsets[i], buf.sizes[i]
-                    self.state[p]["momentum_buffer"] = buf.mom[o:o + sz].view_as(p)
-                torch.autograd.graph.increment_version(p)     # written outside autograd: invalidate re-laid weight caches
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -453,9 +474,8 @@ class SGD(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        clip = self._clip_on()
-        sched = self._sched_on()
-        pending = []                                              # clipping / schedule: every group's runs wait for the norm and the advance
+        clip, sched = self._clip_on(), self._sched_on()
+        pending = []                                              # every group's runs: the norm covers them all, then ONE advance
         for gi, group in enumerate(self.param_groups):
             if group["dampening"] != 0 or group["nesterov"] or group.get("maximize", False):
                 raise ValueError("SGD: dampening / nesterov / maximize are not implemented")
@@ -483,22 +503,29 @@ class SGD(GradClipMixin, SchedEmaMixin, torch.optim.Optimizer):
             if not have:
                 continue
             torch._foreach_copy_([buf.grad_views[i] for i in have], [params[i].grad for i in have])
-            if clip or sched:
-                pending.append((buf, params, runs, lr, mom, wd, gi if sched else None))
-            else:
-                self._launch_runs(buf, params, runs, lr, mom, wd, None, None)
-        grad_scale = skip = None
-        if pending and clip:
-            # ONE norm over the runs the SGD launches cover: slots of parameters without a gradient hold stale data and are in no run
-            ranges = []
-            for buf, _, runs, *_rest in pending:
-                for lo, hi, _ in runs:
-                    ranges.append(buf.grad[buf.offsets[lo]:buf.offsets[hi - 1] + (buf.sizes[hi - 1] + 3) // 4 * 4])
+            pending.append((gi, buf, runs, lr, mom, wd))
+        if not pending:
+            return loss
+        # ONE norm over the runs the SGD launches cover: slots of parameters without a gradient hold stale data and are in no run
+        ranges = [buf.grad[buf.layout.span(lo, hi)] for _, buf, runs, *_ in pending for lo, hi, _ in runs]
+        if clip:
             self._clip_buffers(ranges[0].device, sum(ops.grad_norm_slots(r.numel()) for r in ranges))
-            grad_scale, skip = self._clip_run(ranges, None)
-        if pending and sched:
-            self._sched_buffers(pending[0][0].param.device)
-            self._sched_advance(skip if self.skip_nonfinite else None)
-        for buf, params, runs, lr, mom, wd, gi in pending:
-            self._launch_runs(buf, params, runs, lr, mom, wd, grad_scale, skip, gi)
+        if sched:
+            self._sched_buffers(ranges[0].device)
+        grad_scale, skip, lr_words, ema_w = self._step_controls(ranges)
+        for gi, buf, runs, lr, mom, wd in pending:
+            if self.ema_decay is not None:
+                buf.start_ema(self.state)
+            for lo, hi, fresh in runs:
+                span = buf.layout.span(lo, hi)
+                # momentum 0: torch keeps no buffer and steps with the gradient itself = the "first step" form of the kernel
+                launch_sgd(buf.param[span], buf.grad[span], buf.mom[span], lr=lr, lr_dev=lr_words[gi:gi + 1] if sched else None,
+                           ema=buf.ema[span] if self.ema_decay is not None else None, ema_w=ema_w, momentum=mom, weight_decay=wd,
+                           grad_scale=grad_scale, first=fresh or mom == 0.0, skip=skip)
+                for i in range(lo, hi):
+                    p = buf.params[i]
+                    if mom != 0.0 and fresh:
+                        # (a skipped first step leaves the buffer at zero: momentum * 0 + g is the first-step form in value)
+                        self.state[p]["momentum_buffer"] = buf.mom_views[i]
+                    torch.autograd.graph.increment_version(p)     # written outside autograd: invalidate re-laid weight caches
         return loss
