@@ -2,6 +2,7 @@
 
     python examples/train_synthetic.py [--steps 20] [--batch 20] [--fused-sgd] [--grad-clip 10.0]
                                        [--schedule none|multistep|cosine] [--warmup-steps 5] [--ema-decay 0.999]
+                                       [--decode host|device]
 
 With the reference checked out next to this repo, the same three lines (`install_dropin()`, then
 `from train_function import train_model`) run its own `train_model` unchanged -- see INTEGRATION.md.
@@ -37,6 +38,34 @@ def batches(n, bs, dev, seed=0):
         yield x, classes, boxes
 
 
+def jpeg_batches(n, bs, decode, seed=0):
+    """The reference's input side (train.py:29): synthetic JPEG files on disk, `MultiImageMultiBBoxDataset` + `collate_fn` in two
+    DataLoader workers.  decode="host": PIL decodes in the workers and pixels travel; decode="device": the files' bytes travel and
+    `inputs.to(device)` decodes them on the GPU (a progressive file among them takes the PIL path inside the same batch)."""
+    import tempfile
+    from PIL import Image
+    from Dataset import MultiImageMultiBBoxDataset, collate_fn
+    from Util import class_to_label
+    rng = np.random.default_rng(seed)
+    tmp = tempfile.TemporaryDirectory()
+    paths, boxes, labels = [], [], []
+    yy, xx = np.mgrid[0:375, 0:500]
+    for i in range(n * bs):
+        px = np.clip(np.stack([127 + 90 * np.sin(xx * rng.uniform(.01, .08) + yy * rng.uniform(.01, .08) + c) for c in range(3)], -1)
+                     + rng.normal(0, 14, (375, 500, 3)), 0, 255).astype(np.uint8)
+        paths.append(os.path.join(tmp.name, f"{i}.jpg"))
+        Image.fromarray(px).save(paths[-1], "JPEG", quality=75, progressive=(i % 7 == 3), restart_marker_rows=1)
+        k = 1 + min(int(rng.poisson(1.4)), 7)
+        x1, y1 = rng.uniform(0, 300, k), rng.uniform(0, 225, k)
+        boxes.append(np.stack([x1, y1, x1 + rng.uniform(40, 190, k), y1 + rng.uniform(40, 140, k)], 1).tolist())
+        labels.append([class_to_label[int(c)] for c in rng.integers(0, 20, k)])
+    ds = MultiImageMultiBBoxDataset(paths, boxes, labels, [[0] * len(b) for b in boxes], list(range(len(paths))), decode=decode)
+    dl = torch.utils.data.DataLoader(ds, batch_size=bs, shuffle=True, num_workers=2, collate_fn=collate_fn)
+    for inputs, classes, bboxes, _ in dl:
+        yield inputs, classes, bboxes
+    tmp.cleanup()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -51,6 +80,9 @@ def main():
     ap.add_argument("--warmup-steps", type=int, default=0, help="linear warm-up from a tenth of the rate over this many steps (with --schedule)")
     ap.add_argument("--ema-decay", type=float, default=None, metavar="FLOAT",
                     help="keep an exponential moving average of the weights inside the optimizer step (implies --fused-sgd)")
+    ap.add_argument("--decode", choices=("host", "device"), default=None,
+                    help="feed the loop from synthetic JPEG files through Dataset / DataLoader workers instead of random tensors: "
+                         "'host' decodes with PIL in the workers, 'device' ships the compressed bytes and decodes on the GPU")
     a = ap.parse_args()
     opt_kw = {}
     if a.schedule != "none" or a.warmup_steps or a.ema_decay is not None:
@@ -80,8 +112,10 @@ def main():
                     weight_decay=5e-4, **opt_kw)              # train.py:53-55
     cnn.train()
     t0 = time.time()
-    for count, (inputs, classes, bboxes) in enumerate(batches(a.steps, a.batch, device)):
-        inputs = inputs.to(device)
+    feed = batches(a.steps, a.batch, device) if a.decode is None else jpeg_batches(a.steps, a.batch, a.decode)
+    for count, (inputs, classes, bboxes) in enumerate(feed):
+        raw = inputs
+        inputs = inputs.to(device)                            # a RawBatch: upload, JPEG decode, photometric, resize + normalise
         classes = [c.to(device) for c in classes]
         bboxes = [b.to(device) for b in bboxes]
         optimizer.zero_grad()
@@ -97,6 +131,8 @@ def main():
                         f"  skipped {optimizer.skipped_steps.item()}")
             if "schedule" in opt_kw or "ema_decay" in opt_kw:
                 norm += f"  lr {optimizer.current_lr[1].item():.3g}  ema_w {optimizer.ema_weight.item():.3g}"
+            if getattr(raw, "decode_status", None) is not None:   # reading it is this loop's sync
+                norm += f"  decoded on the device {int((raw.decode_status == 0).sum())}/{len(raw)}"
             print(f"it {count:3d}  l1 {loss1.item():.4f}  l2 {loss2.item():.4f}{norm}  {time.time() - t0:.1f}s")
     if "ema_decay" in opt_kw:                                 # evaluate with the averaged weights: swapped in place, and back
         cnn.eval()

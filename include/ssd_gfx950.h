@@ -614,6 +614,55 @@ int ssd_preprocess_u8(const uint8_t* arena, const ssd_image_desc* descs_dev, con
                       int out_h, int out_w, const float* mean3_host, const float* std3_host, const uint8_t* filler3_host,
                       float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- baseline JPEG decode into the arena's pixel slots, ahead of the two calls above: what
+ * PIL.Image.open(f).convert("RGB") returns (libjpeg's default path), bit for bit -- Huffman decode, dequantise + the "islow"
+ * integer IDCT, "fancy" triangle chroma upsampling (plain replication where the down-sampled plane is at most two samples
+ * wide, as libjpeg chooses), 16-bit fixed-point YCbCr -> RGB.  Scope: SOF0, 8-bit, one interleaved scan, 1 component or 3
+ * components YCbCr with luma sampling 1x1 / 2x1 / 2x2 and chroma 1x1, restart intervals, width and height 1 .. 4096; the host
+ * parser (Dataset.parse_jpeg) keeps everything else away from this call.
+ *   One descriptor per image.  Offsets are bytes in `arena`: the entropy-coded data (from behind the SOS header to the marker
+ * that ends it) and the pixel slot of dst_bytes >= height * width * 3 bytes, which receives HWC RGB.  Segment k of the image
+ * (k = 0 .. n_segments-1) begins seg_offsets[seg_first + k] bytes into the entropy-coded data and ends two bytes -- its RSTn
+ * marker -- before segment k+1 begins, the last one at stream_bytes; it starts at MCU k * restart_interval.  restart_interval
+ * 0: one segment.  Tables: quant[t] in natural (row-major) order; Huffman table t = 0, 1 the DC tables 0, 1 and t = 2, 3 the AC
+ * tables 0, 1, as bits[t][l-1] = codes of length l and huffval[t][0 .. n_huffval[t]), n_huffval 0 = absent; per component
+ * the selectors quant_sel (0 .. 3), dc_sel and ac_sel (0 .. 1).  coef_offset / plane_offset are workspace offsets that the
+ * workspace query fills in.
+ *   Three kernels: entropy decode, one lane per restart segment, one workgroup per image (an image without restart markers is
+ * decoded by ONE lane); dequantise + IDCT, eight lanes per block; upsample + colour, one lane per pixel.  Every loop of the
+ * entropy decoder is bounded whatever the stream holds, and no store leaves the image's coefficient planes (csrc/jpeg_entropy.h).
+ * status[b] (int32, device) is 0, or a mask of 1 (no such Huffman code), 2 (coefficient index above 63), 4 (segment ends before
+ * its MCUs), 8 (fewer segments than the MCU count needs); an image with a non-zero status gets a slot of zeros.
+ *   ssd_jpeg_decode_workspace fills coef_offset / plane_offset of descs_host[0 .. B) and returns the workspace size, 0 for a
+ * descriptor outside the scope.  Upload the descriptors after it.  ssd_jpeg_decode_u8 validates EVERYTHING on the host copies
+ * before it enqueues -- NULL pointers (SSD_ERR_NULL), geometry, selectors, Huffman tables that are no canonical code or hold
+ * more than 256 values, segment offsets outside the stream or out of order, more segments than the MCU count allows, streams or
+ * slots outside the arena or overlapping one another, slots below height * width * 3 bytes, workspace offsets that are not the
+ * query's (SSD_ERR_BAD_SHAPE), a small workspace (SSD_ERR_WORKSPACE) -- and only enqueues on `stream`: no synchronisation.
+ * stages: SSD_JPEG_ALL, or a subset of the three kernels for timing them one by one (the later ones read what the earlier ones
+ * left in the workspace). */
+#define SSD_JPEG_MAX_DIM 4096
+#define SSD_JPEG_ENTROPY 1
+#define SSD_JPEG_IDCT 2
+#define SSD_JPEG_COLOUR 4
+#define SSD_JPEG_ALL 7
+typedef struct ssd_jpeg_desc {
+    int64_t stream_offset, dst_offset, dst_bytes;
+    int64_t coef_offset, plane_offset;
+    int32_t stream_bytes;
+    int32_t seg_first, n_segments, restart_interval;
+    int32_t width, height, n_components, h_samp, v_samp;
+    int32_t n_huffval[4];
+    uint8_t quant_sel[4], dc_sel[4], ac_sel[4];
+    uint16_t quant[4][64];
+    uint8_t bits[4][16];
+    uint8_t huffval[4][256];
+} ssd_jpeg_desc;
+size_t ssd_jpeg_decode_workspace(ssd_jpeg_desc* descs_host, int B);
+int ssd_jpeg_decode_u8(uint8_t* arena, size_t arena_bytes, const ssd_jpeg_desc* descs_dev, const ssd_jpeg_desc* descs_host,
+                       const int32_t* seg_offsets_dev, const int32_t* seg_offsets_host, int n_seg_offsets, int B,
+                       int32_t* status, void* workspace, size_t workspace_bytes, int stages, void* stream);
+
 /* ---- diagnostic: out32[2*xcc] = shader-clock counter, out32[2*xcc+1] = 100 MHz wall clock, for each of the (up to 16)
  * XCCs a block landed on; slots must be zeroed by the caller.  Two probes bracket a region: average shader MHz =
  * 100 * d(counter) / d(wall clock) per XCC. */

@@ -139,12 +139,23 @@ class RawBatch:
     (train_function.py:61) is where the work happens, in the main process: one pinned upload, then the photometric and
     resize / normalise kernels -> the (B,3,H,W) float32 device tensor `cnn(inputs)` expects."""
 
-    def __init__(self, arena: torch.Tensor, offsets: Sequence[int], plans: Sequence[GeomPlan], size: Tuple[int, int] = (300, 300)):
+    def __init__(self, arena: torch.Tensor, offsets: Sequence[int], plans: Sequence[GeomPlan], size: Tuple[int, int] = (300, 300),
+                 headers: Optional[Sequence[Optional["JpegHeader"]]] = None, host_offsets: Optional[Sequence[int]] = None,
+                 device_bytes: Optional[int] = None):
         if arena.dtype != torch.uint8 or arena.dim() != 1 or arena.is_cuda:
             raise ValueError("RawBatch: arena must be a 1-D CPU uint8 tensor")
         if len(offsets) != len(plans) or not plans:
             raise ValueError("RawBatch: one offset and one plan per image, at least one image")
         self.arena, self.offsets, self.plans, self.out_hw = arena, list(offsets), list(plans), tuple(size)
+        # A batch that holds JPEG streams (pack_batch): headers[i] is the image's JpegHeader, or None for one that came as pixels.
+        # `offsets` are then the pixel slots of the DEVICE arena of `device_bytes` bytes; the host arena holds only what exists --
+        # the pixels of the host-decoded images, then the entropy-coded data of the others -- at host_offsets[i].
+        self.headers = None
+        self.decode_status = None                # int32 (B,) on the device after .to() of a batch with streams; 0 = decoded
+        if headers is not None and any(h is not None for h in headers):
+            if host_offsets is None or device_bytes is None or len(headers) != len(plans) or len(host_offsets) != len(plans):
+                raise ValueError("RawBatch: a batch with JPEG streams needs one header slot and one host offset per image")
+            self.headers, self.host_offsets, self.device_bytes = list(headers), list(host_offsets), int(device_bytes)
 
     # what train_function.py reads from `inputs` (`.shape[0]`, `.size(0)`) also works before `.to(device)`
     @property
@@ -158,7 +169,9 @@ class RawBatch:
         return len(self.plans)
 
     def pin_memory(self) -> "RawBatch":          # DataLoader(pin_memory=True) calls this in its pinning thread (main process)
-        return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw)
+        if self.headers is None:
+            return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw)
+        return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw, self.headers, self.host_offsets, self.device_bytes)
 
     def cuda(self, device=None) -> torch.Tensor:
         return self.to(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
@@ -176,7 +189,7 @@ class RawBatch:
             d.flip = int(p.flip)
         host = self.arena if self.arena.is_pinned() else self.arena.pin_memory()
         with torch.cuda.device(device):
-            arena = host.to(device, non_blocking=True)
+            arena = host.to(device, non_blocking=True) if self.headers is None else self._upload_and_decode(host, device)
             if any(p.photo for p in self.plans):       # photometric_distort comes first (Util.py:586), on the source pixels
                 photo = (_lib.PhotoDesc * len(self.plans))()
                 for i, p in enumerate(self.plans):
@@ -190,31 +203,90 @@ class RawBatch:
                 ops.photometric_u8(arena, descs, photo)
             return ops.preprocess_u8(arena, descs, self.out_hw, MEAN, STD, FILLER_U8)
 
+    def _upload_and_decode(self, host: torch.Tensor, device) -> torch.Tensor:
+        """The device arena of a batch with JPEG streams: upload what exists, then decode every stream into its pixel slot
+        (csrc/jpeg.hip).  Enqueues only."""
+        arena = torch.empty(self.device_bytes, device=device, dtype=torch.uint8)
+        enc = [i for i, h in enumerate(self.headers) if h is not None]
+        stream_host = min(self.host_offsets[i] for i in enc)              # streams lie behind the pixels, on both sides
+        stream_dev = self.device_bytes - (host.numel() - stream_host)
+        arena[stream_dev:].copy_(host[stream_host:], non_blocking=True)
+        for i, (h, p) in enumerate(zip(self.headers, self.plans)):
+            if h is None:
+                n = p.src_h * p.src_w * 3
+                arena[self.offsets[i]:self.offsets[i] + n].copy_(host[self.host_offsets[i]:self.host_offsets[i] + n], non_blocking=True)
+        jd = (_lib.JpegDesc * len(enc))()
+        segs = []
+        for d, i in zip(jd, enc):
+            h = self.headers[i]
+            ops.jpeg_fill_desc(d, h, stream_dev + self.host_offsets[i] - stream_host, self.offsets[i], h.height * h.width * 3, len(segs))
+            segs.extend(int(o) - h.data_begin for o in h.seg_offsets)
+        status = ops.jpeg_decode_(arena, jd, np.asarray(segs, np.int32))
+        if len(enc) == len(self.plans):
+            self.decode_status = status
+        else:
+            self.decode_status = torch.zeros(len(self.plans), device=device, dtype=torch.int32)
+            self.decode_status[torch.tensor(enc).to(device, non_blocking=True)] = status
+        return arena
+
 
 def pack_batch(images: Sequence, plans: Optional[Sequence[GeomPlan]] = None, size: Tuple[int, int] = (300, 300)) -> RawBatch:
-    """images: HWC uint8 RGB arrays / tensors / PIL images of any sizes -> RawBatch (host only; safe in a DataLoader worker)."""
-    arrs = []
+    """images: HWC uint8 RGB arrays / tensors / PIL images of any sizes -> RawBatch (host only; safe in a DataLoader worker).
+    An entry may also be an `EncodedImage`, or the `bytes` of an image file: a baseline JPEG `parse_jpeg` accepts stays
+    compressed and is decoded on the device by `.to(device)`; any other file is decoded here with PIL."""
+    items = []                                   # per image: pixels (ndarray) or an EncodedImage
     for im in images:
+        if isinstance(im, (bytes, bytearray, memoryview)):
+            im = EncodedImage.of(bytes(im))
+            if isinstance(im, RawImage):
+                im = im.pixels
+        if isinstance(im, EncodedImage):
+            items.append(im)
+            continue
         a = im.numpy() if torch.is_tensor(im) else np.asarray(im)
         if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("images must be HWC uint8 RGB")
-        arrs.append(np.ascontiguousarray(a))
-    if not arrs:
+        items.append(np.ascontiguousarray(a))
+    if not items:
         raise ValueError("empty batch")
-    plans = [identity_plan(a.shape[0], a.shape[1]) for a in arrs] if plans is None else list(plans)
-    if len(plans) != len(arrs):
+    hw = [(a.header.height, a.header.width) if isinstance(a, EncodedImage) else a.shape[:2] for a in items]
+    plans = [identity_plan(h, w) for h, w in hw] if plans is None else list(plans)
+    if len(plans) != len(items):
         raise ValueError("one plan per image")
-    offs, total = [], 0
-    for a in arrs:
-        offs.append(total)
-        total += (a.size + 255) & ~255
-    host = torch.zeros(total, dtype=torch.uint8)
-    hv = host.numpy()
-    for a, p, o in zip(arrs, plans, offs):
-        if (p.src_h, p.src_w) != a.shape[:2]:
+    for p, (h, w) in zip(plans, hw):
+        if (p.src_h, p.src_w) != (h, w):
             raise ValueError("plan does not belong to this image")
-        hv[o:o + a.size] = a.reshape(-1)
-    return RawBatch(host, offs, plans, size)
+    offs, total = [], 0                          # the pixel slots: one per image, encoded or not
+    for h, w in hw:
+        offs.append(total)
+        total += (h * w * 3 + 255) & ~255
+    if not any(isinstance(a, EncodedImage) for a in items):
+        host = torch.zeros(total, dtype=torch.uint8)
+        hv = host.numpy()
+        for a, o in zip(items, offs):
+            hv[o:o + a.size] = a.reshape(-1)
+        return RawBatch(host, offs, plans, size)
+    # pixels that exist first, the entropy-coded data of the encoded images behind them; their pixel slots exist on the device only
+    host_offs, at = [None] * len(items), 0
+    for i, a in enumerate(items):
+        if not isinstance(a, EncodedImage):
+            host_offs[i] = at
+            at += (a.size + 255) & ~255
+    for i, a in enumerate(items):
+        if isinstance(a, EncodedImage):
+            host_offs[i] = at
+            at += (a.header.data_end - a.header.data_begin + 15) & ~15
+    host = torch.zeros(at, dtype=torch.uint8)
+    hv = host.numpy()
+    for a, o in zip(items, host_offs):
+        if isinstance(a, EncodedImage):
+            n = a.header.data_end - a.header.data_begin
+            hv[o:o + n] = np.frombuffer(a.data, np.uint8, n, a.header.data_begin)
+        else:
+            hv[o:o + a.size] = a.reshape(-1)
+    stream_bytes = at - min(o for a, o in zip(items, host_offs) if isinstance(a, EncodedImage))
+    return RawBatch(host, offs, plans, size, [a.header if isinstance(a, EncodedImage) else None for a in items], host_offs,
+                    total + stream_bytes)
 
 
 def preprocess_batch(images: Sequence, plans: Optional[Sequence[GeomPlan]] = None, size: Tuple[int, int] = (300, 300),
@@ -234,7 +306,10 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
     own line train_function.py:61, main process) makes the normalised device tensor."""
 
     def __init__(self, all_images, all_multi_bboxes, all_multi_labels, all_difficulties, all_indices, isTest=False,
-                 keep_difficult=False):
+                 keep_difficult=False, decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError("decode must be 'host' (PIL in the worker) or 'device' (baseline JPEG streams decoded on the GPU)")
+        self.decode = decode
         self.images_list = all_images
         self.multi_labels_list = all_multi_labels
         self.isTest = isTest
@@ -249,7 +324,11 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
     def __getitem__(self, index):
         from PIL import Image
         from .Util import transform
-        image = RawImage.of(Image.open(self.images_list[index]).convert("RGB"))
+        if self.decode == "device":               # the file's bytes; anything but a baseline JPEG in scope is decoded here, as below
+            with open(self.images_list[index], "rb") as f:
+                image = EncodedImage.of(f.read())
+        else:
+            image = RawImage.of(Image.open(self.images_list[index]).convert("RGB"))
         c = torch.Tensor([label_to_class[i] for i in self.multi_labels_list[index]])
         bboxes = torch.Tensor(self.multi_bbox_list[index])
         if self.keep_difficult is False:
@@ -283,6 +362,168 @@ class RawImage:
         return self.plan.size
 
 
+# ---- baseline JPEG: the host parser of the device decoder (csrc/jpeg.hip) -------------------------------------------------------
+JPEG_MAX_DIM = 4096
+_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+                    28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61,
+                    54, 47, 55, 62, 63])
+
+
+@dataclass
+class JpegHeader:
+    """What the device decoder needs of one baseline JPEG file (all offsets are bytes from the start of the file)."""
+    width: int
+    height: int
+    n_components: int                            # 1 (grayscale) or 3 (YCbCr)
+    h_samp: int                                  # luma sampling 1x1, 2x1 or 2x2; chroma is 1x1
+    v_samp: int
+    restart_interval: int                        # MCUs per restart segment, 0 = no restart markers
+    quant_tables: dict                           # id -> uint16[64], natural (row-major) order
+    huff_tables: dict                            # (class 0 DC / 1 AC, id) -> (bits uint8[16], huffval uint8[n])
+    quant_sel: Tuple[int, ...]                   # per component
+    dc_sel: Tuple[int, ...]
+    ac_sel: Tuple[int, ...]
+    data_begin: int                              # entropy-coded data: [data_begin, data_end)
+    data_end: int
+    seg_offsets: np.ndarray                      # int32: first byte of every restart segment
+    seg_first_mcu: np.ndarray                    # int32: the MCU each segment starts at
+
+
+def parse_jpeg(data: bytes) -> Optional[JpegHeader]:
+    """Walk the markers of a JPEG file.  A header for what the device decoder supports -- baseline sequential DCT (SOF0), 8-bit,
+    Huffman, ONE interleaved scan, 1 component or 3 components YCbCr with luma sampling 1x1 / 2x1 / 2x2 and chroma 1x1, any DQT /
+    DHT, restart intervals, 1 .. 4096 pixels a side -- and None for everything else (progressive, arithmetic, 12-bit, CMYK, RGB,
+    other samplings, several scans, DNL, 16-bit quantisation tables, a file that cannot be walked to its EOI): such an image is
+    decoded by PIL on the host.  Host work only."""
+    a = np.frombuffer(data, np.uint8)
+    n = a.size
+    if n < 4 or a[0] != 0xFF or a[1] != 0xD8:
+        return None
+    pos, quant, huff, frame, restart, adobe = 2, {}, {}, None, 0, None
+    while True:
+        if pos + 2 > n or a[pos] != 0xFF:
+            return None
+        while pos < n and a[pos] == 0xFF:
+            pos += 1
+        if pos >= n:
+            return None
+        m = int(a[pos])
+        pos += 1
+        if m == 0xD8 or m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m == 0xD9 or pos + 2 > n:
+            return None
+        ln = (int(a[pos]) << 8) | int(a[pos + 1])
+        if ln < 2 or pos + ln > n:
+            return None
+        seg = a[pos + 2:pos + ln]
+        if m == 0xDB:                                                  # DQT
+            q = 0
+            while q < seg.size:
+                if seg[q] >> 4 or (seg[q] & 15) > 3 or q + 65 > seg.size:
+                    return None
+                nat = np.zeros(64, np.uint16)
+                nat[_ZIGZAG] = seg[q + 1:q + 65]
+                quant[int(seg[q] & 15)] = nat
+                q += 65
+        elif m == 0xC4:                                                # DHT
+            q = 0
+            while q < seg.size:
+                if q + 17 > seg.size:
+                    return None
+                tc, th = int(seg[q] >> 4), int(seg[q] & 15)
+                bits = seg[q + 1:q + 17].copy()
+                cnt = int(bits.sum())
+                if tc > 1 or th > 1 or cnt > 256 or q + 17 + cnt > seg.size:
+                    return None
+                first = np.concatenate([[0], np.cumsum(bits.astype(np.int64) << (15 - np.arange(16)))[:-1]])      # first code of each length, as 16-bit
+                if ((first + (bits.astype(np.int64) << (15 - np.arange(16)))) > 65536).any():
+                    return None                                         # no canonical code
+                huff[(tc, th)] = (bits, seg[q + 17:q + 17 + cnt].copy())
+                q += 17 + cnt
+        elif m == 0xC0:                                                # SOF0
+            if frame is not None or seg.size < 6:
+                return None
+            h, w, nc = (int(seg[1]) << 8) | int(seg[2]), (int(seg[3]) << 8) | int(seg[4]), int(seg[5])
+            if seg[0] != 8 or nc not in (1, 3) or seg.size != 6 + 3 * nc or not (1 <= h <= JPEG_MAX_DIM and 1 <= w <= JPEG_MAX_DIM):
+                return None
+            frame = (h, w, [(int(seg[6 + 3 * i]), int(seg[7 + 3 * i] >> 4), int(seg[7 + 3 * i] & 15), int(seg[8 + 3 * i])) for i in range(nc)])
+        elif 0xC1 <= m <= 0xCF or m == 0xDC:                           # every other SOF, DAC, DNL
+            return None
+        elif m == 0xDD:
+            if seg.size != 2:
+                return None
+            restart = (int(seg[0]) << 8) | int(seg[1])
+        elif m == 0xEE and seg.size >= 12 and bytes(seg[:5]) == b"Adobe":
+            adobe = int(seg[11])
+        elif m == 0xDA:
+            break
+        pos += ln
+    if frame is None:
+        return None
+    h, w, comps = frame
+    nc = len(comps)
+    if seg.size != 4 + 2 * nc or seg[0] != nc or seg[1 + 2 * nc] != 0 or seg[2 + 2 * nc] != 63 or seg[3 + 2 * nc] != 0:
+        return None
+    dc_sel, ac_sel = [], []
+    for i, c in enumerate(comps):
+        td, ta = int(seg[2 + 2 * i] >> 4), int(seg[2 + 2 * i] & 15)
+        if seg[1 + 2 * i] != c[0] or (0, td) not in huff or (1, ta) not in huff or c[3] not in quant:
+            return None
+        dc_sel.append(td); ac_sel.append(ta)
+    hs = vs = 1
+    if nc == 3:
+        hs, vs = comps[0][1], comps[0][2]
+        if adobe == 0 or [c[0] for c in comps] == [82, 71, 66]:        # RGB, not YCbCr
+            return None
+        if (hs, vs) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+            return None
+    begin = pos + ln
+    # the entropy-coded data ends at the first FF that is followed by neither a stuffed 00 nor a restart marker D0..D7
+    e = a[begin:]
+    at = np.flatnonzero((e[:-1] == 0xFF) & (e[1:] != 0)) if e.size > 1 else np.zeros(0, np.int64)
+    other = np.flatnonzero((e[at + 1] & 0xF8) != 0xD0)
+    if other.size == 0:
+        return None
+    end = begin + int(at[other[0]])
+    if a[end + 1] != 0xD9:                                             # another scan, DNL, fill bytes: not walked
+        return None
+    segs = np.concatenate([[begin], begin + at[:other[0]] + 2]).astype(np.int32)
+    total = -(-w // (8 * hs)) * -(-h // (8 * vs))
+    if restart == 0:
+        if segs.size != 1:
+            return None
+        first = np.zeros(1, np.int32)
+    else:
+        if segs.size > -(-total // restart):
+            return None
+        first = (np.arange(segs.size) * restart).astype(np.int32)
+    return JpegHeader(w, h, nc, hs, vs, restart, quant, huff, tuple(c[3] for c in comps), tuple(dc_sel), tuple(ac_sel), begin, end, segs, first)
+
+
+@dataclass
+class EncodedImage:
+    """A sibling of `RawImage` for `decode="device"`: the bytes of a baseline JPEG file, its parsed header and the geometry /
+    photometric plan drawn for it (a plan needs only the header's width and height).  The pixels first exist on the GPU."""
+    data: bytes
+    header: JpegHeader
+    plan: GeomPlan
+
+    @staticmethod
+    def of(data: bytes):
+        """-> EncodedImage, or a RawImage decoded by PIL where `parse_jpeg` does not accept the file"""
+        header = parse_jpeg(data)
+        if header is None:
+            import io
+            from PIL import Image
+            return RawImage.of(Image.open(io.BytesIO(data)).convert("RGB"))
+        return EncodedImage(data, header, identity_plan(header.height, header.width))
+
+    @property
+    def size(self) -> Tuple[int, int]:
+        return self.plan.size
+
+
 def collate_fn(batch):
     """Reference Dataset.py:41-53: (images, classes, boxes, indices) of a list of samples.  Host work only (it runs in the
     DataLoader's workers): RawImage entries are packed into one `RawBatch`; already-normalised tensors are stacked like the
@@ -290,8 +531,8 @@ def collate_fn(batch):
     images, classes, boxes, indices = [], [], [], []
     for b in batch:
         images.append(b[0]); classes.append(b[1]); boxes.append(b[2]); indices.append(b[3])
-    if images and isinstance(images[0], RawImage):
-        x = pack_batch([r.pixels for r in images], [r.plan for r in images])
+    if images and isinstance(images[0], (RawImage, EncodedImage)):
+        x = pack_batch([r.pixels if isinstance(r, RawImage) else r for r in images], [r.plan for r in images])
     else:
         x = torch.stack(images, dim=0)
     return x, classes, boxes, indices

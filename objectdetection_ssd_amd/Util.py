@@ -119,7 +119,10 @@ def transform(image, boxes, labels):
     flip, with the reference's `random` draws in its order and its box arithmetic -- as a PLAN.  `image` is a PIL image, an HWC
     uint8 array or a `Dataset.RawImage`; the returned image is a `Dataset.RawImage` (source pixels + plan, `.size` = the
     augmented (width, height)): the pixels are produced later, on the GPU, by `Dataset.RawBatch.to(device)`."""
-    from .Dataset import RawImage, plan_transform
+    from .Dataset import EncodedImage, RawImage, plan_transform
+    if isinstance(image, EncodedImage):          # decode="device": the plan needs only the header's size
+        plan, new_boxes, new_labels = plan_transform(image.header.width, image.header.height, boxes, labels)
+        return EncodedImage(image.data, image.header, plan), new_boxes, new_labels
     raw = RawImage.of(image)
     h, w = raw.pixels.shape[:2]
     plan, new_boxes, new_labels = plan_transform(w, h, boxes, labels)

@@ -37,6 +37,15 @@ class PhotoDesc(C.Structure):
     _fields_ = [("n_ops", C.c_int32), ("kind", C.c_int32 * 4), ("alpha", C.c_float * 4), ("hue_delta", C.c_int32 * 4)]
 
 
+class JpegDesc(C.Structure):
+    """struct ssd_jpeg_desc"""
+    _fields_ = [(n, C.c_int64) for n in ("stream_offset", "dst_offset", "dst_bytes", "coef_offset", "plane_offset")] + \
+               [(n, C.c_int32) for n in ("stream_bytes", "seg_first", "n_segments", "restart_interval", "width", "height",
+                                         "n_components", "h_samp", "v_samp")] + \
+               [("n_huffval", C.c_int32 * 4), ("quant_sel", C.c_uint8 * 4), ("dc_sel", C.c_uint8 * 4), ("ac_sel", C.c_uint8 * 4),
+                ("quant", (C.c_uint16 * 64) * 4), ("bits", (C.c_uint8 * 16) * 4), ("huffval", (C.c_uint8 * 256) * 4)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -73,6 +82,8 @@ SIGNATURES = {
     "ssd_photometric_u8": (_I, [_P, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "ssd_preprocess_workspace": (_Z, [_P, _I, _I, _I]),
     "ssd_preprocess_u8": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "ssd_jpeg_decode_workspace": (_Z, [_P, _I]),
+    "ssd_jpeg_decode_u8": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _P, _P, _Z, _I, _P]),
     "ssd_map_eval_workspace": (_Z, [_I, _I]),
     "ssd_map_eval": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "ssd_eval_match_workspace": (_Z, [_I]),

@@ -43,7 +43,7 @@ def _stale(out: str, deps) -> bool:
 
 def _compile(src: str, force: bool, verbose: bool) -> str:
     obj = os.path.join(OBJ, src.replace(".hip", ".o"))
-    deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"),
+    deps = [os.path.join(CSRC, src), *(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")),
             os.path.join(os.path.dirname(PKG), "include", "ssd_gfx950.h"), os.path.abspath(__file__)]
     if force or _stale(obj, deps):
         extra = os.environ.get("SSD_HIPCC_FLAGS", "").split()          # experiments only (e.g. -DSSD_IGEMM_SETPRIO=1)

@@ -1267,6 +1267,55 @@ def photometric_u8(arena: torch.Tensor, descs, photo) -> None:
                                  ws.numel(), _stream()), "photometric_u8")
 
 
+JPEG_ENTROPY, JPEG_IDCT, JPEG_COLOUR, JPEG_ALL = 1, 2, 4, 7
+
+
+def jpeg_fill_desc(d, header, stream_offset: int, dst_offset: int, dst_bytes: int, seg_first: int) -> None:
+    """Fill one _lib.JpegDesc from a `Dataset.JpegHeader` (host only; the C entry validates what it is given)."""
+    import numpy as np
+    d.stream_offset, d.dst_offset, d.dst_bytes = int(stream_offset), int(dst_offset), int(dst_bytes)
+    d.stream_bytes = int(header.data_end - header.data_begin)
+    d.seg_first, d.n_segments, d.restart_interval = int(seg_first), len(header.seg_offsets), int(header.restart_interval)
+    d.width, d.height, d.n_components, d.h_samp, d.v_samp = header.width, header.height, header.n_components, header.h_samp, header.v_samp
+    for c in range(header.n_components):
+        d.quant_sel[c], d.dc_sel[c], d.ac_sel[c] = header.quant_sel[c], header.dc_sel[c], header.ac_sel[c]
+    for t, q in header.quant_tables.items():
+        C.memmove(d.quant[t], np.ascontiguousarray(q, np.uint16).ctypes.data, 128)
+    for (tc, th), (bits, vals) in header.huff_tables.items():
+        t = 2 * tc + th
+        if len(bits) != 16 or len(vals) > 256:
+            raise ValueError("jpeg: a Huffman table has 16 length counts and at most 256 values")
+        d.n_huffval[t] = len(vals)
+        C.memmove(d.bits[t], np.ascontiguousarray(bits, np.uint8).ctypes.data, 16)
+        C.memmove(d.huffval[t], np.ascontiguousarray(vals, np.uint8).ctypes.data, len(vals))
+
+
+def jpeg_decode_(arena: torch.Tensor, descs, seg_offsets, stages: int = JPEG_ALL) -> torch.Tensor:
+    """Decode baseline JPEG streams held in `arena` (uint8, device) into their pixel slots of the same arena, in place
+    (include/ssd_gfx950.h ssd_jpeg_decode_u8).  descs: ctypes array of _lib.JpegDesc (host); seg_offsets: int32 array, the
+    restart-segment offsets of all images.  -> status (B,) int32 on the device: 0 = decoded, else the slot is zero-filled.
+    Enqueues only; reading the status is the caller's synchronisation."""
+    import numpy as np
+    _req(arena, "arena", torch.uint8)
+    if arena.dim() != 1:
+        raise ValueError("jpeg_decode_: arena must be 1-D")
+    B = len(descs)
+    segs = np.ascontiguousarray(np.asarray(seg_offsets, np.int32))
+    if B == 0 or segs.ndim != 1 or segs.size == 0:
+        raise ValueError("jpeg_decode_: at least one image and one segment")
+    lib = _lib.load()
+    nbytes = lib.ssd_jpeg_decode_workspace(C.byref(descs), B)
+    if nbytes == 0:
+        raise ValueError("jpeg_decode_: a descriptor is outside the decoder's scope (see include/ssd_gfx950.h)")
+    ws = workspace(nbytes, arena.device, "jpeg")
+    d_dev = torch.from_numpy(np.frombuffer(bytes(descs), dtype=np.uint8).copy()).to(arena.device, non_blocking=True)
+    s_dev = torch.from_numpy(segs.copy()).to(arena.device, non_blocking=True)
+    status = torch.empty(B, device=arena.device, dtype=torch.int32)
+    check(lib.ssd_jpeg_decode_u8(arena.data_ptr(), arena.numel(), d_dev.data_ptr(), C.byref(descs), s_dev.data_ptr(), segs.ctypes.data,
+                                 int(segs.size), B, status.data_ptr(), ws.data_ptr(), ws.numel(), int(stages), _stream()), "jpeg_decode_u8")
+    return status
+
+
 # ---- Winograd F(mo x mo, 3x3), mo = 2 or 4 --------------------------------------------------------
 def wino_x3(mo: int, K: int) -> bool:
     """True if the F(4x4) plane GEMMs of reduction length K multiply three bf16 limbs per f32 operand (csrc/gemm_x3.hip); the layer's
