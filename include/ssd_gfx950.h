@@ -663,6 +663,25 @@ int ssd_jpeg_decode_u8(uint8_t* arena, size_t arena_bytes, const ssd_jpeg_desc* 
                        const int32_t* seg_offsets_dev, const int32_t* seg_offsets_host, int n_seg_offsets, int B,
                        int32_t* status, void* workspace, size_t workspace_bytes, int stages, void* stream);
 
+/* ---- the same decode with MANY lanes per restart segment, for streams without restart markers (csrc/jpeg_split.hip; algorithm and
+ * bounds in csrc/jpeg_split.h): each segment is de-stuffed into a copy in the workspace and cut into subsequences of subseq_bytes
+ * bytes (a multiple of 4 in 8 .. 4096); every subsequence is walked speculatively, the states at the boundaries are repaired until
+ * they stop changing -- one workgroup per image, at most as many rounds as the longest segment has subsequences -- and a write pass
+ * stores the coefficients.  Pixels and status are those of ssd_jpeg_decode_u8, bit for bit; a segment shorter than one subsequence
+ * is one lane as there.  Streams of more than 2^27 bytes are outside the scope.
+ *   ssd_jpeg_decode_split_workspace fills coef_offset / plane_offset exactly as ssd_jpeg_decode_workspace does, keeps that layout in
+ * front and puts the copies and the per-subsequence records behind it; 0 for anything outside the scope.  ssd_jpeg_decode_split_u8
+ * runs every host-side validation of ssd_jpeg_decode_u8, and refuses a bad subseq_bytes (SSD_ERR_BAD_SHAPE) and a workspace below
+ * the split query's (SSD_ERR_WORKSPACE), before it enqueues anything.  `stages` as above (SSD_JPEG_ENTROPY is all four kernels of
+ * the entropy decode).  stats: NULL, or B x 4 int32 on the device: subsequences, repair rounds, subsequence walks of the
+ * synchronisation, 0. */
+size_t ssd_jpeg_decode_split_workspace(ssd_jpeg_desc* descs_host, int B, const int32_t* seg_offsets_host, int n_seg_offsets,
+                                       int subseq_bytes);
+int ssd_jpeg_decode_split_u8(uint8_t* arena, size_t arena_bytes, const ssd_jpeg_desc* descs_dev, const ssd_jpeg_desc* descs_host,
+                             const int32_t* seg_offsets_dev, const int32_t* seg_offsets_host, int n_seg_offsets, int B,
+                             int32_t* status, void* workspace, size_t workspace_bytes, int stages, void* stream, int subseq_bytes,
+                             int32_t* stats);
+
 /* ---- diagnostic: out32[2*xcc] = shader-clock counter, out32[2*xcc+1] = 100 MHz wall clock, for each of the (up to 16)
  * XCCs a block landed on; slots must be zeroed by the caller.  Two probes bracket a region: average shader MHz =
  * 100 * d(counter) / d(wall clock) per XCC. */

@@ -205,7 +205,8 @@ class RawBatch:
 
     def _upload_and_decode(self, host: torch.Tensor, device) -> torch.Tensor:
         """The device arena of a batch with JPEG streams: upload what exists, then decode every stream into its pixel slot
-        (csrc/jpeg.hip).  Enqueues only."""
+        (csrc/jpeg.hip; files without restart markers through the many-lanes entropy decode of csrc/jpeg_split.hip, which
+        `ops.jpeg_decode_` chooses by the batch's longest segment).  Enqueues only."""
         arena = torch.empty(self.device_bytes, device=device, dtype=torch.uint8)
         enc = [i for i, h in enumerate(self.headers) if h is not None]
         stream_host = min(self.host_offsets[i] for i in enc)              # streams lie behind the pixels, on both sides

@@ -84,6 +84,8 @@ SIGNATURES = {
     "ssd_preprocess_u8": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_jpeg_decode_workspace": (_Z, [_P, _I]),
     "ssd_jpeg_decode_u8": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _P, _P, _Z, _I, _P]),
+    "ssd_jpeg_decode_split_workspace": (_Z, [_P, _I, _P, _I, _I]),
+    "ssd_jpeg_decode_split_u8": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _P, _P, _Z, _I, _P, _I, _P]),
     "ssd_map_eval_workspace": (_Z, [_I, _I]),
     "ssd_map_eval": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _Z, _P]),
     "ssd_eval_match_workspace": (_Z, [_I]),

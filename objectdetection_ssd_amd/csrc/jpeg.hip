@@ -13,31 +13,10 @@
 #include <vector>
 
 #include "common.h"
+#include "jpeg_common.h"
 #include "jpeg_entropy.h"
 
 namespace {
-
-struct Geom {
-    int mcus_w, mcus_h, total_mcus;
-    int blocks_w[3], blocks_h[3];
-    long n_blocks[3], total_blocks;
-};
-
-__host__ __device__ inline Geom geom_of(const ssd_jpeg_desc& d) {
-    Geom g;
-    g.mcus_w = (d.width + 8 * d.h_samp - 1) / (8 * d.h_samp);
-    g.mcus_h = (d.height + 8 * d.v_samp - 1) / (8 * d.v_samp);
-    g.total_mcus = g.mcus_w * g.mcus_h;
-    g.total_blocks = 0;
-    for (int c = 0; c < 3; ++c) {
-        const bool on = c < d.n_components;
-        g.blocks_w[c] = on ? g.mcus_w * (c == 0 ? d.h_samp : 1) : 0;
-        g.blocks_h[c] = on ? g.mcus_h * (c == 0 ? d.v_samp : 1) : 0;
-        g.n_blocks[c] = (long)g.blocks_w[c] * g.blocks_h[c];
-        g.total_blocks += g.n_blocks[c];
-    }
-    return g;
-}
 
 // ---- 1. entropy decode ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void jpeg_entropy_kernel(const uint8_t* __restrict__ arena, const ssd_jpeg_desc* __restrict__ descs,
@@ -219,41 +198,22 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(uint8_t* __restrict__ 
     }
 }
 
-// ---- host side --------------------------------------------------------------------------------------------------------------------
-bool scope_ok(const ssd_jpeg_desc& d) {
-    if (d.width < 1 || d.height < 1 || d.width > SSD_JPEG_MAX_DIM || d.height > SSD_JPEG_MAX_DIM) return false;
-    if (d.n_components == 1) return d.h_samp == 1 && d.v_samp == 1;
-    if (d.n_components != 3) return false;
-    return (d.h_samp == 1 && d.v_samp == 1) || (d.h_samp == 2 && (d.v_samp == 1 || d.v_samp == 2));
-}
-
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// coefficient planes of all images, then the component planes of all images
-size_t layout(const ssd_jpeg_desc* descs, int B, std::vector<int64_t>& coef, std::vector<int64_t>& plane, size_t* coef_bytes) {
-    size_t at = 0;
-    for (int b = 0; b < B; ++b) { coef[b] = (int64_t)at; at += up256((size_t)geom_of(descs[b]).total_blocks * 64 * sizeof(int16_t)); }
-    *coef_bytes = at;
-    for (int b = 0; b < B; ++b) { plane[b] = (int64_t)at; at += up256((size_t)geom_of(descs[b]).total_blocks * 64); }
-    return at;
-}
-
 }  // namespace
 
 extern "C" size_t ssd_jpeg_decode_workspace(ssd_jpeg_desc* descs_host, int B) {
     if (!descs_host || B <= 0 || B > 65535) return 0;
     for (int b = 0; b < B; ++b)
-        if (!scope_ok(descs_host[b])) return 0;
+        if (!jpeg_scope_ok(descs_host[b])) return 0;
     std::vector<int64_t> coef(B), plane(B);
     size_t coef_bytes;
-    const size_t total = layout(descs_host, B, coef, plane, &coef_bytes);
+    const size_t total = jpeg_layout(descs_host, B, coef, plane, &coef_bytes);
     for (int b = 0; b < B; ++b) { descs_host[b].coef_offset = coef[b]; descs_host[b].plane_offset = plane[b]; }
     return total + 256;
 }
 
-extern "C" int ssd_jpeg_decode_u8(uint8_t* arena, size_t arena_bytes, const ssd_jpeg_desc* descs_dev, const ssd_jpeg_desc* descs_host,
-                                  const int32_t* seg_offsets_dev, const int32_t* seg_offsets_host, int n_seg_offsets, int B,
-                                  int32_t* status, void* workspace, size_t workspace_bytes, int stages, void* stream) {
+int jpeg_validate_batch(const uint8_t* arena, size_t arena_bytes, const ssd_jpeg_desc* descs_dev, const ssd_jpeg_desc* descs_host,
+                        const int32_t* seg_offsets_dev, const int32_t* seg_offsets_host, int n_seg_offsets, int B, const int32_t* status,
+                        const void* workspace, int stages, JpegBatchInfo* info) {
     if (!arena || !descs_dev || !descs_host || !seg_offsets_dev || !seg_offsets_host || !status || !workspace) return SSD_ERR_NULL;
     if (B <= 0 || B > 65535 || n_seg_offsets <= 0 || stages <= 0 || stages > SSD_JPEG_ALL) return SSD_ERR_BAD_SHAPE;
     if (!ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
@@ -264,7 +224,7 @@ extern "C" int ssd_jpeg_decode_u8(uint8_t* arena, size_t arena_bytes, const ssd_
     int max_segments = 1;
     for (int b = 0; b < B; ++b) {
         const ssd_jpeg_desc& d = descs_host[b];
-        if (!scope_ok(d)) return SSD_ERR_BAD_SHAPE;
+        if (!jpeg_scope_ok(d)) return SSD_ERR_BAD_SHAPE;
         const Geom g = geom_of(d);
         for (int t = 0; t < 4; ++t) {
             if (d.n_huffval[t] < 0 || d.n_huffval[t] > 256) return SSD_ERR_BAD_SHAPE;
@@ -297,29 +257,49 @@ extern "C" int ssd_jpeg_decode_u8(uint8_t* arena, size_t arena_bytes, const ssd_
     for (size_t i = 0; i + 1 < spans.size(); ++i)
         if (spans[i].second > spans[i + 1].first) return SSD_ERR_BAD_SHAPE;          // a slot over a stream or another slot
     size_t coef_bytes;
-    const size_t total = layout(descs_host, B, coef, plane, &coef_bytes);
+    const size_t total = jpeg_layout(descs_host, B, coef, plane, &coef_bytes);
     for (int b = 0; b < B; ++b)
         if (descs_host[b].coef_offset != coef[b] || descs_host[b].plane_offset != plane[b]) return SSD_ERR_BAD_SHAPE;
-    if (workspace_bytes < total) return SSD_ERR_WORKSPACE;
+    info->layout_bytes = total;
+    info->coef_bytes = coef_bytes;
+    info->max_blocks = max_blocks;
+    info->max_px = max_px;
+    info->max_segments = max_segments;
+    return SSD_OK;
+}
+
+int jpeg_launch_idct_colour(uint8_t* arena, const ssd_jpeg_desc* descs_dev, int B, const int32_t* status, uint8_t* ws,
+                            const JpegBatchInfo& info, int stages, hipStream_t st) {
+    if (stages & SSD_JPEG_IDCT) {
+        const int gx = (int)std::min<long>((info.max_blocks + 31) / 32, 512);
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3(gx, B), dim3(256), 0, st, descs_dev, ws);
+        SSD_CHECK_LAUNCH();
+    }
+    if (stages & SSD_JPEG_COLOUR) {
+        const int gx = (int)std::min<long>((info.max_px + 255) / 256, 1024);
+        hipLaunchKernelGGL(jpeg_colour_kernel, dim3(gx, B), dim3(256), 0, st, arena, descs_dev, ws, status);
+        SSD_CHECK_LAUNCH();
+    }
+    return SSD_OK;
+}
+
+extern "C" int ssd_jpeg_decode_u8(uint8_t* arena, size_t arena_bytes, const ssd_jpeg_desc* descs_dev, const ssd_jpeg_desc* descs_host,
+                                  const int32_t* seg_offsets_dev, const int32_t* seg_offsets_host, int n_seg_offsets, int B,
+                                  int32_t* status, void* workspace, size_t workspace_bytes, int stages, void* stream) {
+    JpegBatchInfo info;
+    const int bad = jpeg_validate_batch(arena, arena_bytes, descs_dev, descs_host, seg_offsets_dev, seg_offsets_host, n_seg_offsets, B, status,
+                                        workspace, stages, &info);
+    if (bad != SSD_OK) return bad;
+    if (workspace_bytes < info.layout_bytes) return SSD_ERR_WORKSPACE;
 
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
     if (stages & SSD_JPEG_ENTROPY) {
         if (hipMemsetAsync(status, 0, (size_t)B * sizeof(int32_t), st) != hipSuccess) return SSD_ERR_LAUNCH;
-        if (hipMemsetAsync(ws, 0, coef_bytes, st) != hipSuccess) return SSD_ERR_LAUNCH;
-        const int threads = 64 * std::min(16, max_segments);
+        if (hipMemsetAsync(ws, 0, info.coef_bytes, st) != hipSuccess) return SSD_ERR_LAUNCH;
+        const int threads = 64 * std::min(16, info.max_segments);
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(B), dim3(threads), 0, st, arena, descs_dev, seg_offsets_dev, ws, status);
         SSD_CHECK_LAUNCH();
     }
-    if (stages & SSD_JPEG_IDCT) {
-        const int gx = (int)std::min<long>((max_blocks + 31) / 32, 512);
-        hipLaunchKernelGGL(jpeg_idct_kernel, dim3(gx, B), dim3(256), 0, st, descs_dev, ws);
-        SSD_CHECK_LAUNCH();
-    }
-    if (stages & SSD_JPEG_COLOUR) {
-        const int gx = (int)std::min<long>((max_px + 255) / 256, 1024);
-        hipLaunchKernelGGL(jpeg_colour_kernel, dim3(gx, B), dim3(256), 0, st, arena, descs_dev, ws, status);
-        SSD_CHECK_LAUNCH();
-    }
-    return SSD_OK;
+    return jpeg_launch_idct_colour(arena, descs_dev, B, status, ws, info, stages, st);
 }

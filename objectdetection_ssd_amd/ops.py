@@ -1290,12 +1290,48 @@ def jpeg_fill_desc(d, header, stream_offset: int, dst_offset: int, dst_bytes: in
         C.memmove(d.huffval[t], np.ascontiguousarray(vals, np.uint8).ctypes.data, len(vals))
 
 
-def jpeg_decode_(arena: torch.Tensor, descs, seg_offsets, stages: int = JPEG_ALL) -> torch.Tensor:
-    """Decode baseline JPEG streams held in `arena` (uint8, device) into their pixel slots of the same arena, in place
-    (include/ssd_gfx950.h ssd_jpeg_decode_u8).  descs: ctypes array of _lib.JpegDesc (host); seg_offsets: int32 array, the
-    restart-segment offsets of all images.  -> status (B,) int32 on the device: 0 = decoded, else the slot is zero-filled.
-    Enqueues only; reading the status is the caller's synchronisation."""
+# The entropy decode gives a restart segment to ONE lane ("segment") or cuts it into subsequences that many lanes decode and repair
+# ("split", csrc/jpeg_split.hip).  Both constants are measured (tools/jpeg_decode_bench.py, profiles/jpeg_split_bench.json).
+JPEG_SUBSEQUENCE_BYTES = 64          # the default subsequence size of "split": the fastest of 64 / 128 / 256 / 512 on 32 files of 44 KB
+JPEG_SPLIT_AUTO_BYTES = 2361         # "auto" takes "split" when the batch's longest segment has more bytes than this: the shortest
+#                                      segments of the restart-interval sweep at which "split" beat "segment" by more than the windows spread
+JPEG_ENTROPY_MODES = ("segment", "split", "auto")
+
+
+def _jpeg_longest_segment(descs, segs) -> int:
+    longest = 0
+    for d in descs:
+        first, n = int(d.seg_first), int(d.n_segments)
+        if n < 1 or first < 0 or first + n > len(segs):
+            raise ValueError("jpeg: a descriptor's segments lie outside seg_offsets")
+        ends = [int(segs[first + k + 1]) - 2 for k in range(n - 1)] + [int(d.stream_bytes)]
+        longest = max(longest, max(e - int(segs[first + k]) for k, e in enumerate(ends)))
+    return longest
+
+
+def jpeg_entropy_auto(descs, seg_offsets) -> str:
+    """What `entropy="auto"` chooses for a batch (host only): "split" when its longest restart segment exceeds
+    JPEG_SPLIT_AUTO_BYTES -- files without restart markers, one segment each -- else "segment"."""
     import numpy as np
+    segs = np.asarray(seg_offsets, np.int32).reshape(-1)
+    return "split" if _jpeg_longest_segment(descs, segs) > JPEG_SPLIT_AUTO_BYTES else "segment"
+
+
+def jpeg_decode_(arena: torch.Tensor, descs, seg_offsets, stages: int = JPEG_ALL, entropy: str = "auto",
+                 subsequence_bytes: Optional[int] = None, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Decode baseline JPEG streams held in `arena` (uint8, device) into their pixel slots of the same arena, in place
+    (include/ssd_gfx950.h ssd_jpeg_decode_u8 / ssd_jpeg_decode_split_u8).  descs: ctypes array of _lib.JpegDesc (host);
+    seg_offsets: int32 array, the restart-segment offsets of all images.  entropy: "segment" (one lane per restart segment), "split"
+    (many lanes per segment, subsequence_bytes each: a multiple of 4 in 8 .. 4096, default JPEG_SUBSEQUENCE_BYTES) or "auto"
+    (`jpeg_entropy_auto`); the pixels and the status do not depend on it.  stats ("split" only): int32 (B, 4) on the device, receives
+    subsequences, repair rounds, subsequence walks, 0 per image.  -> status (B,) int32 on the device: 0 = decoded, else the slot is
+    zero-filled.  Enqueues only; reading the status is the caller's synchronisation."""
+    import numpy as np
+    if entropy not in JPEG_ENTROPY_MODES:
+        raise ValueError(f"jpeg_decode_: entropy must be one of {JPEG_ENTROPY_MODES}, not {entropy!r}")
+    sub = JPEG_SUBSEQUENCE_BYTES if subsequence_bytes is None else subsequence_bytes
+    if not isinstance(sub, int) or isinstance(sub, bool) or sub < 8 or sub > 4096 or sub % 4:
+        raise ValueError("jpeg_decode_: subsequence_bytes must be a multiple of 4 in 8 .. 4096")
     _req(arena, "arena", torch.uint8)
     if arena.dim() != 1:
         raise ValueError("jpeg_decode_: arena must be 1-D")
@@ -1303,16 +1339,32 @@ def jpeg_decode_(arena: torch.Tensor, descs, seg_offsets, stages: int = JPEG_ALL
     segs = np.ascontiguousarray(np.asarray(seg_offsets, np.int32))
     if B == 0 or segs.ndim != 1 or segs.size == 0:
         raise ValueError("jpeg_decode_: at least one image and one segment")
+    if entropy == "auto":
+        entropy = jpeg_entropy_auto(descs, segs)
+    if stats is not None:
+        if entropy != "split":
+            raise ValueError("jpeg_decode_: stats are those of entropy='split'")
+        _req(stats, "stats", torch.int32)
+        if tuple(stats.shape) != (B, 4) or stats.device != arena.device:
+            raise ValueError("jpeg_decode_: stats must be (B, 4) int32 on the arena's device")
     lib = _lib.load()
-    nbytes = lib.ssd_jpeg_decode_workspace(C.byref(descs), B)
+    if entropy == "split":
+        nbytes = lib.ssd_jpeg_decode_split_workspace(C.byref(descs), B, segs.ctypes.data, int(segs.size), sub)
+    else:
+        nbytes = lib.ssd_jpeg_decode_workspace(C.byref(descs), B)
     if nbytes == 0:
         raise ValueError("jpeg_decode_: a descriptor is outside the decoder's scope (see include/ssd_gfx950.h)")
     ws = workspace(nbytes, arena.device, "jpeg")
     d_dev = torch.from_numpy(np.frombuffer(bytes(descs), dtype=np.uint8).copy()).to(arena.device, non_blocking=True)
     s_dev = torch.from_numpy(segs.copy()).to(arena.device, non_blocking=True)
     status = torch.empty(B, device=arena.device, dtype=torch.int32)
-    check(lib.ssd_jpeg_decode_u8(arena.data_ptr(), arena.numel(), d_dev.data_ptr(), C.byref(descs), s_dev.data_ptr(), segs.ctypes.data,
-                                 int(segs.size), B, status.data_ptr(), ws.data_ptr(), ws.numel(), int(stages), _stream()), "jpeg_decode_u8")
+    if entropy == "split":
+        check(lib.ssd_jpeg_decode_split_u8(arena.data_ptr(), arena.numel(), d_dev.data_ptr(), C.byref(descs), s_dev.data_ptr(),
+                                           segs.ctypes.data, int(segs.size), B, status.data_ptr(), ws.data_ptr(), ws.numel(), int(stages),
+                                           _stream(), sub, None if stats is None else stats.data_ptr()), "jpeg_decode_split_u8")
+    else:
+        check(lib.ssd_jpeg_decode_u8(arena.data_ptr(), arena.numel(), d_dev.data_ptr(), C.byref(descs), s_dev.data_ptr(), segs.ctypes.data,
+                                     int(segs.size), B, status.data_ptr(), ws.data_ptr(), ws.numel(), int(stages), _stream()), "jpeg_decode_u8")
     return status
 
 
