@@ -17,7 +17,7 @@
 // (lane half h takes k = 8q+4h+e): A and B use the same permutation, so the sum is
 // the same set of products.
 #include <atomic>
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -1438,7 +1438,7 @@ static double g_prof_flops[PROF_MAX];
 static int g_prof_kind[PROF_MAX];                 // 0: batched igemm (Winograd plane GEMMs), 1: fused GEMM + output transform kernel
 
 // Internal: bracket one launch of another file's kernel with the recorder's events (kind as above).  begin returns the slot or -1.
-__attribute__((visibility("hidden"))) int ssd_internal_prof_open(double flops, int kind, hipStream_t st) {
+int ssd_internal_prof_open(double flops, int kind, hipStream_t st) {
     const int i = g_prof_on.load(std::memory_order_acquire) ? g_prof_n.fetch_add(1, std::memory_order_relaxed) : PROF_MAX;
     if (i >= PROF_MAX) return -1;
     g_prof_flops[i] = flops;
@@ -1446,19 +1446,16 @@ __attribute__((visibility("hidden"))) int ssd_internal_prof_open(double flops, i
     (void)hipEventRecord(g_prof_ev[2 * i], st);
     return i;
 }
-__attribute__((visibility("hidden"))) void ssd_internal_prof_close(int slot, hipStream_t st) {
+void ssd_internal_prof_close(int slot, hipStream_t st) {
     if (slot >= 0) (void)hipEventRecord(g_prof_ev[2 * slot + 1], st);
 }
 
-int ssd_internal_gemm_nt_wants(int M, int K, int N, int n_rows, int nbatch);
-int ssd_internal_gemm_nt(const float* a, const float* w, float* out, int M, int K, int N, int n_rows, int nbatch, size_t batch_a_elems,
-                         size_t batch_w_elems, hipStream_t st);
 // Internal (not part of the C ABI): `nbatch` independent GEMMs out[b][M][N] = a[b][M][K] * w[b][N][K]^T on the 64x64 f32 kernel
 // (the sixteen planes of a Winograd F(2x2,3x3) convolution).  K % 32 == 0; rows of w beyond n_rows read as zero.
 // ksplit > 1: every GEMM is cut into K slices that write raw partial tiles to out[b][slice][M][N] (the caller adds them up).
-__attribute__((visibility("hidden"))) int ssd_internal_gemm_batched(const float* a, const float* w, float* out, int M, int K, int N,
-                                                                     int n_rows, int nbatch, size_t batch_a_elems, size_t batch_w_elems,
-                                                                     int ksplit, hipStream_t st) {
+int ssd_internal_gemm_batched(const float* a, const float* w, float* out, int M, int K, int N,
+                              int n_rows, int nbatch, size_t batch_a_elems, size_t batch_w_elems,
+                              int ksplit, hipStream_t st) {
     if (K % 32 != 0 || M <= 0 || N <= 0 || nbatch <= 0 || nbatch > 65535 || ksplit < 1 || ksplit > 65535) return SSD_ERR_BAD_SHAPE;
     const size_t ab = (size_t)M * K * 4, wb = (size_t)n_rows * K * 4;
     if (ab >= 0xF0000000ull || wb >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;

@@ -16,7 +16,7 @@
 //   * the items of one XCD (block id mod 8) are a contiguous eighth of the list, handed out round-robin to its blocks: at any time the
 //     blocks that share an L2 work on neighbouring tiles of one plane (shared A panels, one 1 MB filter plane).
 // Rows beyond M / beyond the filter rows are clamped to the last valid row on load and never stored.
-#include "common.h"
+#include "internal.h"
 
 #ifdef SSD_EXPERIMENTAL
 namespace {
@@ -227,7 +227,7 @@ extern "C" int ssd_tune_set_gemm_nt(int mode) {
 }
 
 // Internal (not part of the C ABI; called by ssd_internal_gemm_batched): 1 when this kernel takes the launch.
-__attribute__((visibility("hidden"))) int ssd_internal_gemm_nt_wants(int M, int K, int N, int n_rows, int nbatch) {
+int ssd_internal_gemm_nt_wants(int M, int K, int N, int n_rows, int nbatch) {
     if (g_nt_mode == 0) return 0;
     if (K % 32 != 0 || K < 64 || N % 4 != 0 || n_rows < 1 || M < 1 || nbatch < 1) return 0;
     // Measured at batch 32 (tools/gemm_bench.py): 106-118 TFLOP/s against the generic kernel's 108-129 on the same launches, and 113-129
@@ -236,8 +236,8 @@ __attribute__((visibility("hidden"))) int ssd_internal_gemm_nt_wants(int M, int 
     return g_nt_mode == 1;
 }
 
-__attribute__((visibility("hidden"))) int ssd_internal_gemm_nt(const float* a, const float* w, float* out, int M, int K, int N, int n_rows,
-                                                               int nbatch, size_t batch_a_elems, size_t batch_w_elems, hipStream_t st) {
+int ssd_internal_gemm_nt(const float* a, const float* w, float* out, int M, int K, int N, int n_rows,
+                         int nbatch, size_t batch_a_elems, size_t batch_w_elems, hipStream_t st) {
     if (!a || !w || !out) return SSD_ERR_NULL;
     if (K % 32 != 0 || K < 64 || M < 1 || N < 1 || n_rows < 1 || nbatch < 1) return SSD_ERR_BAD_SHAPE;
 #ifndef SSD_EXPERIMENTAL

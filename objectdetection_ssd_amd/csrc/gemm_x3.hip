@@ -25,10 +25,7 @@
 // (MI355X_MICROARCH.md LDS table).  The same kernel with an epilogue (bias / ReLU / += / ReLU mask, row stride) is the forward and the
 // data gradient of the 1x1 layers with long reductions (fc7, seq8.0); the TN form below is every weight gradient.
 #include <type_traits>
-#include "common.h"
-
-int ssd_internal_prof_open(double flops, int kind, hipStream_t st);      // conv_igemm.hip: the per-launch recorder behind ssd_prof_gemm_begin / _collect
-void ssd_internal_prof_close(int slot, hipStream_t st);
+#include "internal.h"
 
 namespace {
 
@@ -832,13 +829,11 @@ extern "C" int ssd_gemm_x3_split_weights(const float* w, void* w3, int rows, int
     return SSD_OK;
 }
 
-int ssd_internal_gemm_batched_x3s(const float* a, const void* w3, float* out, int M, int K, int N, int n_rows, int nbatch, size_t batch_a_elems,
-                                  hipStream_t st);       // csrc/gemm_x3v2.hip: 256 x 256 tiles, two wave groups in ping-pong
 static int g_x3_big = 0;       // ssd_tune_set_x3_big (SSD_EXPERIMENTAL builds): 0 = every launch on the 128 x 128 kernel (default), 1 = the large launches on the 256 x 256 ping-pong kernel, 2 = all that fit
 static int g_x3_m16 = 0;      // ssd_tune_set_x3_mfma: 1 = the plane GEMMs on v_mfma_f32_16x16x32_bf16 (limb pairs concatenated along K), 0 = 32x32x16
 // Internal (not part of the C ABI): the x3 form of ssd_internal_gemm_batched (conv_igemm.hip); w3 from ssd_gemm_x3_split_weights
-__attribute__((visibility("hidden"))) int ssd_internal_gemm_batched_x3(const float* a, const void* w3, float* out, int M, int K, int N, int n_rows,
-                                                                        int nbatch, size_t batch_a_elems, hipStream_t st) {
+int ssd_internal_gemm_batched_x3(const float* a, const void* w3, float* out, int M, int K, int N, int n_rows,
+                                 int nbatch, size_t batch_a_elems, hipStream_t st) {
     if (K % 32 != 0 || M <= 0 || N <= 0 || n_rows <= 0 || ssd_cdiv(n_rows, 128) * 128 < N || nbatch <= 0) return SSD_ERR_BAD_SHAPE;
     if ((size_t)M * K * 4 >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;
     GemmX3Params p{};
@@ -905,9 +900,9 @@ extern "C" int ssd_tune_set_x3_mfma(int rows) {
 
 // Internal: TN split-K plane GEMMs from limbs; out[b][split][M][N] raw partial sums, K steps of 16 rows, `ksplit` slices of
 // `ksteps_per_split` steps each (ksplit * ksteps_per_split >= ceil(K / 16))
-__attribute__((visibility("hidden"))) int ssd_internal_gemm_tn_x3(const float* a, const float* c, float* out, int M, int N, int K, int lda, int ldc,
-                                                                   int nbatch, int ksplit, int ksteps_per_split, size_t batch_a, size_t batch_c,
-                                                                   hipStream_t st) {
+int ssd_internal_gemm_tn_x3(const float* a, const float* c, float* out, int M, int N, int K, int lda, int ldc,
+                            int nbatch, int ksplit, int ksteps_per_split, size_t batch_a, size_t batch_c,
+                            hipStream_t st) {
     if (M <= 0 || N <= 0 || K <= 0 || lda % 4 != 0 || ldc % 4 != 0 || nbatch <= 0 || ksplit < 1 || ksteps_per_split < 1) return SSD_ERR_BAD_SHAPE;
     if ((size_t)ksplit * ksteps_per_split * 16 < (size_t)K) return SSD_ERR_BAD_SHAPE;
     if (batch_a * 4 >= 0xF0000000ull || batch_c * 4 >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;

@@ -27,7 +27,7 @@
 // MFMA gaps: 0.372; in the read phase beside a prio-1 matrix phase: 0.361) gives it back, and writing limb planes from the transform kernels
 // costs 6 instead of 4 bytes per plane element (+0.4 ms per step) for -0.4 ms of GEMM time.  NOT in the default build (SSD_EXPERIMENTAL=1,
 // like gemm_nt.hip); the 128 x 128 kernel stays on the path.  Step A/B with the x3s dispatch: 20.17 vs 20.18 ms.
-#include "common.h"
+#include "internal.h"
 
 #ifdef SSD_EXPERIMENTAL
 namespace {
@@ -405,8 +405,8 @@ extern "C" int ssd_gemm_planes_x3v2(const void* a3, const void* w3, float* out, 
 }
 
 // Internal (csrc/gemm_x3.hip dispatches here for the large launches): a [nbatch][M][K] f32 split in the kernel, w3 limb planes.
-__attribute__((visibility("hidden"))) int ssd_internal_gemm_batched_x3s(const float* a, const void* w3, float* out, int M, int K, int N, int n_rows,
-                                                                         int nbatch, size_t batch_a_elems, hipStream_t st) {
+int ssd_internal_gemm_batched_x3s(const float* a, const void* w3, float* out, int M, int K, int N, int n_rows,
+                                  int nbatch, size_t batch_a_elems, hipStream_t st) {
 #ifndef SSD_EXPERIMENTAL
     return SSD_ERR_BAD_SHAPE;
 #else

@@ -16,7 +16,7 @@
 // MFMA: v_mfma_f32_16x16x4_f32, wave tile 16 tiles x 16 channels; its C/D layout puts a (tile, channel) pair's 36 plane values in one
 // lane.  K is walked in the permuted order k = 16j + 4(lane>>4) + e for both operands (a sum does not care).
 // Rows beyond the last tile / beyond the filter rows are clamped to the last valid row: their results are never stored.
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -296,10 +296,6 @@ __global__ __launch_bounds__(512, 2) void wino4_gemm_out_kernel(const FusedParam
     }
 }
 
-}  // namespace
-int ssd_internal_prof_open(double flops, int kind, hipStream_t st);
-void ssd_internal_prof_close(int slot, hipStream_t st);
-namespace {
 unsigned long long* g_fused_stamps = nullptr;
 int g_fused_stagger = -1;         // -1 / 0: none; > 0: delay step in shader cycles
 }  // namespace
@@ -316,21 +312,19 @@ extern "C" int ssd_tune_set_wino_fused_stamps(uint64_t* device_buffer) {
 }
 
 // Internal (not part of the C ABI; called by winograd.hip's wino_conv): the GEMMs + output transform of one F(4x4,3x3) convolution on
-// planes V [36][tiles][K] and filters U [36][Nrows][K].  Returns SSD_ERR_BAD_SHAPE when the geometry is not the kernel's (K % 64).
-__attribute__((visibility("hidden"))) int ssd_internal_wino4_gemm_out(const float* V, const float* U, int tiles, int K, int Nrows, int Nout,
-                                                                       float* out, int ldo, int Cvalid, const float* bias, const float* mask,
-                                                                       const unsigned long long* mask_bits, int relu, int accumulate, int H, int W,
-                                                                       int TH, int TW, float* yp, uint8_t* am, int Ho, int Wo, hipStream_t st) {
+// planes V [36][tiles][K] and filters c.U [36][Nrows][K].  Returns SSD_ERR_BAD_SHAPE when the geometry is not the kernel's (K % 64).
+int ssd_internal_wino4_gemm_out(const WinoConv& c, const float* V, int tiles, int H, int W, int TH, int TW, hipStream_t st) {
+    const int K = c.K, Nrows = c.U_rows, Nout = (c.U_rows + 3) / 4 * 4;       // whole 4-channel vectors: filter rows beyond Nrows read as zero
     if ((K != 64 && K != 128 && K != 256) || tiles <= 0 || Nout <= 0 || Nout % 4 != 0 || Nrows <= 0) return SSD_ERR_BAD_SHAPE;
     if ((size_t)tiles * K >= (1ull << 32) || (size_t)Nrows * K >= (1ull << 32)) return SSD_ERR_BAD_SHAPE;
     FusedParams p;
-    p.V = V; p.U = U;
+    p.V = V; p.U = c.U;
     p.plane_v = (size_t)tiles * K; p.plane_u = (size_t)Nrows * K;
     p.tiles = tiles; p.K = K; p.Nrows = Nrows; p.Nout = Nout;
     p.groups = ssd_cdiv(tiles, FG); p.nblk_n = ssd_cdiv(Nout, FN);
-    p.out = out; p.ldo = ldo; p.Cvalid = Cvalid; p.bias = bias; p.mask = mask; p.mask_bits = mask_bits; p.relu = relu; p.accumulate = accumulate;
+    p.out = c.out; p.ldo = c.ldo; p.Cvalid = Nrows; p.bias = c.bias; p.mask = c.mask; p.mask_bits = c.mask_bits; p.relu = c.relu; p.accumulate = c.accumulate;
     p.H = H; p.W = W; p.TH = TH; p.TW = TW;
-    p.yp = yp; p.am = am; p.Ho = Ho; p.Wo = Wo;
+    p.yp = c.pooled.y; p.am = c.pooled.argmax; p.Ho = c.pooled.Ho; p.Wo = c.pooled.Wo;
     p.stamps = g_fused_stamps;
     // The first-round start stagger (eight phases over about one workgroup's life: (K / 64) * 36 * 160 cycles per phase) made the kernel
     // 1-3 % faster by itself, but in the train step its idle start costs more than it returns (23.69 vs 23.84 ms, interleaved A/B): off
@@ -655,27 +649,24 @@ __global__ __launch_bounds__(512, 2) void wino4_full_kernel(const FullParams p) 
 
 }  // namespace
 
-// Internal: the whole convolution from the NHWC activation (K = 64 or 128 channels).  V_keep / bits_out may be NULL.
-__attribute__((visibility("hidden"))) int ssd_internal_wino4_full(const float* x, const float* U, int tiles, int K, int Nrows, int Nout, float* out,
-                                                                   int ldo, int Cvalid, const float* bias, const float* mask,
-                                                                   const unsigned long long* mask_bits, int relu, int accumulate, int H, int W,
-                                                                   int TH, int TW, float* yp, uint8_t* am, int Ho, int Wo, float* V_keep,
-                                                                   unsigned long long* bits_out, hipStream_t st) {
+// Internal: the whole convolution from the NHWC activation c.in (K = 64 or 128 channels).  c.planes_keep / c.bits_out may be NULL.
+int ssd_internal_wino4_full(const WinoConv& c, int tiles, int H, int W, int TH, int TW, hipStream_t st) {
 #ifndef SSD_EXPERIMENTAL
     return SSD_ERR_BAD_SHAPE;                       // not in this build (SSD_EXPERIMENTAL=1 python -m objectdetection_ssd_amd.build)
 #else
+    const int K = c.K, Nrows = c.U_rows, Nout = (c.U_rows + 3) / 4 * 4;
     if ((K != 64 && K != 128) || tiles <= 0 || Nout <= 0 || Nout % 4 != 0 || Nrows <= 0) return SSD_ERR_BAD_SHAPE;
     if ((size_t)Nrows * K >= (1ull << 32)) return SSD_ERR_BAD_SHAPE;
     FullParams p;
     const size_t xb = (size_t)(tiles / (TH * TW)) * H * W * K * 4;
     if (xb >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;
-    p.x = x; p.x_bytes = (unsigned)xb; p.U = U; p.plane_u = (size_t)Nrows * K;
+    p.x = c.in; p.x_bytes = (unsigned)xb; p.U = c.U; p.plane_u = (size_t)Nrows * K;
     p.tiles = tiles; p.K = K; p.Nrows = Nrows; p.Nout = Nout;
     p.groups = ssd_cdiv(tiles, GT); p.nblk_n = ssd_cdiv(Nout, FN);
-    p.out = out; p.ldo = ldo; p.Cvalid = Cvalid; p.bias = bias; p.mask = mask; p.mask_bits = mask_bits; p.relu = relu; p.accumulate = accumulate;
+    p.out = c.out; p.ldo = c.ldo; p.Cvalid = Nrows; p.bias = c.bias; p.mask = c.mask; p.mask_bits = c.mask_bits; p.relu = c.relu; p.accumulate = c.accumulate;
     p.H = H; p.W = W; p.TH = TH; p.TW = TW;
-    p.yp = yp; p.am = am; p.Ho = Ho; p.Wo = Wo;
-    p.V_keep = V_keep; p.bits_out = bits_out;
+    p.yp = c.pooled.y; p.am = c.pooled.argmax; p.Ho = c.pooled.Ho; p.Wo = c.pooled.Wo;
+    p.V_keep = c.planes_keep; p.bits_out = c.bits_out;
     p.stamps = g_fused_stamps;
     const long long nblk = (long long)p.groups * p.nblk_n;
     if (nblk >= (1ll << 31)) return SSD_ERR_BAD_SHAPE;

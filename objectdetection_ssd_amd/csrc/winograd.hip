@@ -8,21 +8,11 @@
 // The transforms are exact in binary arithmetic up to the usual rounding of their additions (factors 1, 1/2, 1/4); the result
 // differs from the direct sum at the 1e-6 level.  V and M live in a caller-provided workspace (16 planes each).
 #include <cstdlib>
-#include "common.h"
-
-int ssd_internal_gemm_batched(const float* a, const float* w, float* out, int M, int K, int N, int n_rows, int nbatch,
-                              size_t batch_a_elems, size_t batch_w_elems, int ksplit, hipStream_t st);
-int ssd_internal_gemm_batched_x3(const float* a, const void* w3, float* out, int M, int K, int N, int n_rows, int nbatch, size_t batch_a_elems,
-                                 hipStream_t st);
-int ssd_internal_gemm_tn_x3(const float* a, const float* c, float* out, int M, int N, int K, int lda, int ldc, int nbatch, int ksplit,
-                            int ksteps_per_split, size_t batch_a, size_t batch_c, hipStream_t st);
-int ssd_internal_wino4_gemm_out(const float* V, const float* U, int tiles, int K, int Nrows, int Nout, float* out, int ldo, int Cvalid,
-                                const float* bias, const float* mask, const unsigned long long* mask_bits, int relu, int accumulate, int H,
-                                int W, int TH, int TW, float* yp, uint8_t* am, int Ho, int Wo, hipStream_t st);
-
-int ssd_internal_wino4_full(const float* x, const float* U, int tiles, int K, int Nrows, int Nout, float* out, int ldo, int Cvalid,
-                            const float* bias, const float* mask, const unsigned long long* mask_bits, int relu, int accumulate, int H, int W,
-                            int TH, int TW, float* yp, uint8_t* am, int Ho, int Wo, float* V_keep, unsigned long long* bits_out, hipStream_t st);
+//
+// Host side: a forward or data-gradient entry point fills in a WinoConv record (internal.h); its direction's one validator (wino_fwd /
+// wino_dgrad) holds the common rules and hands the record to wino_conv, the one launch sequence.  The weight gradient is wino_wgrad
+// in one call or dy_transform + ssd_wino4_wgrad_gemm in two; both end in wgrad4_tail.
+#include "internal.h"
 
 namespace {
 
@@ -1204,50 +1194,44 @@ void launch_dy_pass(const float* dy, float* Y, const ssd_conv_geom* g, int ldy, 
     }
 }
 
-// one Winograd convolution, F(mo x mo, 3x3) with mo = 2 or 4: in (N,H,W,Cin) -> out (N,H,W,ldo) first Cout channels
-struct PooledOut { float* y; uint8_t* argmax; int Ho, Wo; };     // destination of the fused conv -> ReLU -> 2x2/s2 max pool form
-int wino_conv(int mo, const float* in, int Cin, const float* U, int U_rows, float* out, int ldo, int Cout, const float* bias,
-              const float* mask, int relu, int accumulate, int N, int H, int W, void* ws, size_t ws_bytes, hipStream_t st,
-              const PooledOut* pooled = nullptr, float* V_keep = nullptr, const float* V_given = nullptr,
-              unsigned long long* bits_out = nullptr, const unsigned long long* mask_bits = nullptr, int D = 1) {
-    if (D < 1 || D > 4 || (D > 1 && (mo != 4 || pooled != nullptr))) return SSD_ERR_BAD_SHAPE;      // dilation: F(4x4), not into a pool
+// one Winograd convolution of the map g describes (its N, H, W and dilation; the channels are the record's): c.in or c.planes -> c.out
+// or c.pooled; the record comes checked (wino_fwd / wino_dgrad)
+int wino_conv(const WinoConv& c, const ssd_conv_geom* g, void* ws, size_t ws_bytes, hipStream_t st) {
+    const int mo = c.mo, D = g->dil, N = g->N, H = g->H, W = g->W, Cin = c.K;
+    const bool pooled = c.pooled.y != nullptr;
+    if (D < 1 || D > 4 || (D > 1 && (mo != 4 || pooled))) return SSD_ERR_BAD_SHAPE;      // dilation: F(4x4), not into a pool
     const LatPlan lp = lat_plan(H, W, D);
     const int TH = mo == 4 ? lp.TH : (H + mo - 1) / mo, TW = mo == 4 ? lp.TW : (W + mo - 1) / mo, P = (mo + 2) * (mo + 2);
     const size_t tiles = (size_t)N * TH * TW;
-    const int Cvalid = Cout;
-    Cout = (Cout + 3) / 4 * 4;                 // the GEMM and the output transform work on whole 4-channel vectors: the filter rows
-    if (tiles >= (1ull << 31) || Cin % 32 != 0 || Cout > ldo) return SSD_ERR_BAD_SHAPE;     // beyond Cvalid read as zero
+    const int Cvalid = c.U_rows;
+    const int Cout = (Cvalid + 3) / 4 * 4;     // the GEMM and the output transform work on whole 4-channel vectors: the filter rows
+    if (tiles >= (1ull << 31) || Cin % 32 != 0 || Cout > c.ldo || c.ldo % 4 != 0) return SSD_ERR_BAD_SHAPE;   // beyond Cvalid read as zero
     const size_t vb = align256((size_t)P * tiles * Cin * 4), mb = align256((size_t)P * tiles * Cout * 4);
     if (ws_bytes < vb + mb) return SSD_ERR_WORKSPACE;
-    float* V = V_keep != nullptr ? V_keep : static_cast<float*>(ws);       // kept planes: the weight gradient multiplies them again
+    float* V = c.planes_keep != nullptr ? c.planes_keep : static_cast<float*>(ws);      // kept planes: the weight gradient multiplies them again
     float* Mx = reinterpret_cast<float*>(static_cast<char*>(ws) + vb);
-    if (D == 1 && V_given == nullptr && use_full(mo, Cin, Cout))            // one kernel from the activation to the output
-        return ssd_internal_wino4_full(in, U, (int)tiles, Cin, U_rows, Cout, out, ldo, Cvalid, bias, mask, mask_bits, relu, accumulate, H, W, TH,
-                                       TW, pooled ? pooled->y : nullptr, pooled ? pooled->argmax : nullptr, pooled ? pooled->Ho : 0,
-                                       pooled ? pooled->Wo : 0, V_keep, bits_out, st);
-    if (V_given != nullptr) V = const_cast<float*>(V_given);                // input planes already formed (by the dy pass of the wgrad)
-    else if (mo == 2) hipLaunchKernelGGL(wino_input_kernel, dim3(grid_for(tiles * (Cin / 4))), dim3(256), 0, st, in, V, N, H, W, Cin, TH, TW);
-    else hipLaunchKernelGGL(wino4_input_kernel, dim3(grid_for(tiles * (Cin / 4))), dim3(256), 0, st, in, V, N, H, W, Cin, TH, TW, bits_out, lp.lat);
+    if (D == 1 && c.planes == nullptr && use_full(mo, Cin, Cout))          // one kernel from the activation to the output
+        return ssd_internal_wino4_full(c, (int)tiles, H, W, TH, TW, st);
+    if (c.planes != nullptr) V = const_cast<float*>(c.planes);             // input planes already formed (by the dy pass of the wgrad)
+    else if (mo == 2) hipLaunchKernelGGL(wino_input_kernel, dim3(grid_for(tiles * (Cin / 4))), dim3(256), 0, st, c.in, V, N, H, W, Cin, TH, TW);
+    else hipLaunchKernelGGL(wino4_input_kernel, dim3(grid_for(tiles * (Cin / 4))), dim3(256), 0, st, c.in, V, N, H, W, Cin, TH, TW, c.bits_out, lp.lat);
     SSD_CHECK_LAUNCH();
-    if (mask_bits != nullptr && mo != 4) return SSD_ERR_BAD_SHAPE;
-    if (D == 1 && use_fused(mo, Cin, Cout))
-        return ssd_internal_wino4_gemm_out(V, U, (int)tiles, Cin, U_rows, Cout, out, ldo, Cvalid, bias, mask, mask_bits, relu, accumulate, H, W, TH, TW,
-                                           pooled ? pooled->y : nullptr, pooled ? pooled->argmax : nullptr, pooled ? pooled->Ho : 0,
-                                           pooled ? pooled->Wo : 0, st);
+    if (c.mask_bits != nullptr && mo != 4) return SSD_ERR_BAD_SHAPE;
+    if (D == 1 && use_fused(mo, Cin, Cout)) return ssd_internal_wino4_gemm_out(c, V, (int)tiles, H, W, TH, TW, st);
     if (use_x3(mo, Cin)) {
-        if (int e = ssd_internal_gemm_batched_x3(V, U, Mx, (int)tiles, Cin, Cout, U_rows, P, tiles * Cin, st)) return e;
-    } else if (int e = ssd_internal_gemm_batched(V, U, Mx, (int)tiles, Cin, Cout, U_rows, P, tiles * Cin, (size_t)U_rows * Cin, 1, st)) {
+        if (int e = ssd_internal_gemm_batched_x3(V, c.U, Mx, (int)tiles, Cin, Cout, c.U_rows, P, tiles * Cin, st)) return e;
+    } else if (int e = ssd_internal_gemm_batched(V, c.U, Mx, (int)tiles, Cin, Cout, c.U_rows, P, tiles * Cin, (size_t)c.U_rows * Cin, 1, st)) {
         return e;
     }
-    if (pooled != nullptr)
-        hipLaunchKernelGGL(wino4_output_pool_kernel, dim3(grid_for(tiles * (Cout / 4))), dim3(256), 0, st, Mx, pooled->y, pooled->argmax, N, H, W,
-                           Cout, TH, TW, bias, pooled->Ho, pooled->Wo);
+    if (pooled)
+        hipLaunchKernelGGL(wino4_output_pool_kernel, dim3(grid_for(tiles * (Cout / 4))), dim3(256), 0, st, Mx, c.pooled.y, c.pooled.argmax, N, H, W,
+                           Cout, TH, TW, c.bias, c.pooled.Ho, c.pooled.Wo);
     else if (mo == 2)
-        hipLaunchKernelGGL(wino_output_kernel, dim3(grid_for(tiles * (Cout / 4))), dim3(256), 0, st, Mx, out, N, H, W, Cout, Cvalid, ldo, TH, TW,
-                           bias, mask, relu, accumulate);
+        hipLaunchKernelGGL(wino_output_kernel, dim3(grid_for(tiles * (Cout / 4))), dim3(256), 0, st, Mx, c.out, N, H, W, Cout, Cvalid, c.ldo, TH, TW,
+                           c.bias, c.mask, c.relu, c.accumulate);
     else
-        hipLaunchKernelGGL(wino4_output_kernel, dim3(grid_for(tiles * (Cout / 4))), dim3(256), 0, st, Mx, out, N, H, W, Cout, Cvalid, ldo, TH,
-                           TW, bias, mask, relu, accumulate, mask_bits, lp.lat);
+        hipLaunchKernelGGL(wino4_output_kernel, dim3(grid_for(tiles * (Cout / 4))), dim3(256), 0, st, Mx, c.out, N, H, W, Cout, Cvalid, c.ldo, TH,
+                           TW, c.bias, c.mask, c.relu, c.accumulate, c.mask_bits, lp.lat);
     SSD_CHECK_LAUNCH();
     return SSD_OK;
 }
@@ -1287,13 +1271,52 @@ extern "C" size_t ssd_conv3x3_wino_workspace(const ssd_conv_geom* g, int directi
     return align256(P * tiles * cin * 4) + align256(P * tiles * cout * 4);
 }
 
+namespace {
+inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+inline unsigned long long* bit_words(uint64_t* p) { return reinterpret_cast<unsigned long long*>(p); }
+inline const unsigned long long* bit_words(const uint64_t* p) { return reinterpret_cast<const unsigned long long*>(p); }
+
+// The forward, all entries.  Their common rules in the order the status shows them: NULL, alignment of the bit words, shape, 16-byte
+// alignment, size of the pooled map.  shape_ok / align_ok: what the entry requires beyond them at those two stages (computed with
+// g possibly NULL).
+int wino_fwd(WinoConv& c, const ssd_conv_geom* g, bool shape_ok, bool align_ok, int ceil_mode, void* ws, size_t ws_bytes, void* stream) {
+    const float* src = c.planes ? c.planes : c.in;
+    const float* dst = c.pooled.y ? c.pooled.y : c.out;
+    if (!src || !c.U || !dst || !ws) return SSD_ERR_NULL;
+    if (!aligned8(c.bits_out)) return SSD_ERR_ALIGN;
+    if (!wino_geom_ok(g) || g->Ci % 32 != 0 || (c.mo != 2 && c.mo != 4) || !shape_ok) return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(src) || !ssd_aligned16(dst) || !ssd_aligned16(ws) || !ssd_aligned16(c.U) || !ssd_aligned16(c.planes_keep) ||
+        ((uintptr_t)c.pooled.argmax & 3) || !align_ok)
+        return SSD_ERR_ALIGN;
+    c.K = g->Ci; c.U_rows = g->Co;
+    if (c.pooled.y) {
+        c.ldo = g->Co;
+        c.pooled.Ho = ceil_mode ? (g->H + 1) / 2 : g->H / 2; c.pooled.Wo = ceil_mode ? (g->W + 1) / 2 : g->W / 2;
+        if (c.pooled.Ho <= 0 || c.pooled.Wo <= 0) return SSD_ERR_BAD_SHAPE;
+    }
+    return wino_conv(c, g, ws, ws_bytes, (hipStream_t)stream);
+}
+// what the forms into a pool or from given planes require of the geometry: no dilation, whole channel quads
+inline bool plain_quads(const ssd_conv_geom* g) { return g && g->dil == 1 && g->Co % 4 == 0; }
+
+// The data gradient, all four entries: dy (N,H,W,ldy) in c.in or its planes in c.planes, c.U = U_bwd [P][Ci][Co_pad] -> c.out = dx
+int wino_dgrad(WinoConv& c, int ldy, int Co_pad, const ssd_conv_geom* g, void* ws, size_t ws_bytes, void* stream) {
+    const float* src = c.planes ? c.planes : c.in;
+    if (!src || !c.U || !c.out || !ws) return SSD_ERR_NULL;
+    if (!wino_geom_ok(g) || Co_pad % 32 != 0 || Co_pad < g->Co || ldy != Co_pad || g->Ci % 4 != 0 || (c.mo != 2 && c.mo != 4))
+        return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(src) || !ssd_aligned16(c.out) || !ssd_aligned16(ws) || !ssd_aligned16(c.U) || !ssd_aligned16(c.mask) || !aligned8(c.mask_bits))
+        return SSD_ERR_ALIGN;
+    c.K = Co_pad; c.U_rows = c.ldo = g->Ci;
+    return wino_conv(c, g, ws, ws_bytes, (hipStream_t)stream);
+}
+}  // namespace
+
 extern "C" int ssd_conv3x3_wino_fwd(const float* x, const float* U_fwd, const float* bias, float* y, int ldy, const ssd_conv_geom* g,
                                     int relu, int mo, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !U_fwd || !y || !workspace) return SSD_ERR_NULL;
-    if (!wino_geom_ok(g) || g->Ci % 32 != 0 || ldy < (g->Co + 3) / 4 * 4 || (mo != 2 && mo != 4)) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(x) || !ssd_aligned16(y) || !ssd_aligned16(workspace) || !ssd_aligned16(U_fwd) || ldy % 4 != 0) return SSD_ERR_ALIGN;
-    return wino_conv(mo, x, g->Ci, U_fwd, g->Co, y, ldy, g->Co, bias, nullptr, relu, 0, g->N, g->H, g->W, workspace, workspace_bytes,
-                     (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, nullptr, g->dil);
+    WinoConv c{};
+    c.mo = mo; c.in = x; c.U = U_fwd; c.bias = bias; c.out = y; c.ldo = ldy; c.relu = relu;
+    return wino_fwd(c, g, g && ldy >= (g->Co + 3) / 4 * 4, ldy % 4 == 0, 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ssd_conv3x3_wino_fwd_keep(const float* x, const float* U_fwd, const float* bias, float* y, int ldy, const ssd_conv_geom* g,
@@ -1304,13 +1327,11 @@ extern "C" int ssd_conv3x3_wino_fwd_keep(const float* x, const float* U_fwd, con
 extern "C" int ssd_conv3x3_wino_fwd_keep_bits(const float* x, const float* U_fwd, const float* bias, float* y, int ldy, const ssd_conv_geom* g,
                                               int relu, float* planes_keep, uint64_t* relu_bits_out, void* workspace, size_t workspace_bytes,
                                               void* stream) {
-    if (!x || !U_fwd || !y || !workspace || !planes_keep) return SSD_ERR_NULL;
-    if (relu_bits_out && ((uintptr_t)relu_bits_out & 7)) return SSD_ERR_ALIGN;
-    if (!wino_geom_ok(g) || g->Ci % 32 != 0 || ldy < (g->Co + 3) / 4 * 4) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(x) || !ssd_aligned16(y) || !ssd_aligned16(workspace) || !ssd_aligned16(U_fwd) || !ssd_aligned16(planes_keep) || ldy % 4 != 0)
-        return SSD_ERR_ALIGN;
-    return wino_conv(4, x, g->Ci, U_fwd, g->Co, y, ldy, g->Co, bias, nullptr, relu, 0, g->N, g->H, g->W, workspace, workspace_bytes,
-                     (hipStream_t)stream, nullptr, planes_keep, nullptr, reinterpret_cast<unsigned long long*>(relu_bits_out), nullptr, g->dil);
+    if (!planes_keep) return SSD_ERR_NULL;
+    WinoConv c{};
+    c.mo = 4; c.in = x; c.U = U_fwd; c.bias = bias; c.out = y; c.ldo = ldy; c.relu = relu;
+    c.planes_keep = planes_keep; c.bits_out = bit_words(relu_bits_out);
+    return wino_fwd(c, g, g && ldy >= (g->Co + 3) / 4 * 4, ldy % 4 == 0, 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ssd_conv3x3_wino_fwd_pool(const float* x, const float* U_fwd, const float* bias, float* y_pooled, uint8_t* argmax,
@@ -1322,16 +1343,10 @@ extern "C" int ssd_conv3x3_wino_fwd_pool(const float* x, const float* U_fwd, con
 extern "C" int ssd_conv3x3_wino_fwd_pool_bits(const float* x, const float* U_fwd, const float* bias, float* y_pooled, uint8_t* argmax,
                                               const ssd_conv_geom* g, int ceil_mode, float* planes_keep, uint64_t* relu_bits_out,
                                               void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !U_fwd || !y_pooled || !workspace) return SSD_ERR_NULL;
-    if (relu_bits_out && ((uintptr_t)relu_bits_out & 7)) return SSD_ERR_ALIGN;
-    if (!wino_geom_ok(g) || g->dil != 1 || g->Ci % 32 != 0 || g->Co % 4 != 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(x) || !ssd_aligned16(y_pooled) || !ssd_aligned16(workspace) || !ssd_aligned16(U_fwd) || (bias && !ssd_aligned16(bias)) ||
-        (argmax && ((uintptr_t)argmax & 3)) || (planes_keep && !ssd_aligned16(planes_keep)))
-        return SSD_ERR_ALIGN;
-    const PooledOut po = {y_pooled, argmax, ceil_mode ? (g->H + 1) / 2 : g->H / 2, ceil_mode ? (g->W + 1) / 2 : g->W / 2};
-    if (po.Ho <= 0 || po.Wo <= 0) return SSD_ERR_BAD_SHAPE;
-    return wino_conv(4, x, g->Ci, U_fwd, g->Co, nullptr, g->Co, g->Co, bias, nullptr, 1, 0, g->N, g->H, g->W, workspace, workspace_bytes,
-                     (hipStream_t)stream, &po, planes_keep, nullptr, reinterpret_cast<unsigned long long*>(relu_bits_out));
+    WinoConv c{};
+    c.mo = 4; c.in = x; c.U = U_fwd; c.bias = bias; c.pooled.y = y_pooled; c.pooled.argmax = argmax; c.relu = 1;
+    c.planes_keep = planes_keep; c.bits_out = bit_words(relu_bits_out);
+    return wino_fwd(c, g, plain_quads(g), ssd_aligned16(bias), ceil_mode, workspace, workspace_bytes, stream);
 }
 
 // Forward of an F(4x4) layer whose input planes already exist (written by the producer of its input: ssd_conv1_first_wino_fwd): the plane
@@ -1340,33 +1355,42 @@ extern "C" int ssd_conv3x3_wino_fwd_pool_bits(const float* x, const float* U_fwd
 extern "C" int ssd_conv3x3_wino_fwd_from_planes(const float* planes, const float* U_fwd, const float* bias, float* y, int ldy, float* y_pooled,
                                                 uint8_t* argmax, const ssd_conv_geom* g, int relu, int ceil_mode, void* workspace,
                                                 size_t workspace_bytes, void* stream) {
-    if (!planes || !U_fwd || !workspace || (!y && !y_pooled)) return SSD_ERR_NULL;
-    if (!wino_geom_ok(g) || g->dil != 1 || g->Ci % 32 != 0 || g->Co % 4 != 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(planes) || !ssd_aligned16(U_fwd) || !ssd_aligned16(workspace) || (y && !ssd_aligned16(y)) || (y_pooled && !ssd_aligned16(y_pooled)) ||
-        (bias && !ssd_aligned16(bias)) || (argmax && ((uintptr_t)argmax & 3)))
-        return SSD_ERR_ALIGN;
-    if (y_pooled) {
-        const PooledOut po = {y_pooled, argmax, ceil_mode ? (g->H + 1) / 2 : g->H / 2, ceil_mode ? (g->W + 1) / 2 : g->W / 2};
-        if (po.Ho <= 0 || po.Wo <= 0) return SSD_ERR_BAD_SHAPE;
-        return wino_conv(4, nullptr, g->Ci, U_fwd, g->Co, nullptr, g->Co, g->Co, bias, nullptr, 1, 0, g->N, g->H, g->W, workspace, workspace_bytes,
-                         (hipStream_t)stream, &po, nullptr, planes);
-    }
-    if (ldy < g->Co || ldy % 4 != 0) return SSD_ERR_BAD_SHAPE;
-    return wino_conv(4, nullptr, g->Ci, U_fwd, g->Co, y, ldy, g->Co, bias, nullptr, relu, 0, g->N, g->H, g->W, workspace, workspace_bytes,
-                     (hipStream_t)stream, nullptr, nullptr, planes);
+    WinoConv c{};
+    c.mo = 4; c.planes = planes; c.U = U_fwd; c.bias = bias;
+    if (y_pooled) { c.pooled.y = y_pooled; c.pooled.argmax = argmax; c.relu = 1; }
+    else { c.out = y; c.ldo = ldy; c.relu = relu; }
+    // both destinations and the argmax bytes are held to their alignment, whichever of them is used
+    const bool align_ok = ssd_aligned16(bias) && ssd_aligned16(y) && ((uintptr_t)argmax & 3) == 0;
+    return wino_fwd(c, g, plain_quads(g), align_ok, ceil_mode, workspace, workspace_bytes, stream);      // (ldy: wino_conv's own rules)
 }
 
 extern "C" int ssd_conv3x3_wino_dgrad(const float* dy, int ldy, const float* U_bwd, int Co_pad, float* dx, const float* relu_mask,
                                       int accumulate, const ssd_conv_geom* g, int mo, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-    if (!dy || !U_bwd || !dx || !workspace) return SSD_ERR_NULL;
-    if (!wino_geom_ok(g) || Co_pad % 32 != 0 || Co_pad < g->Co || ldy != Co_pad || g->Ci % 4 != 0 || (mo != 2 && mo != 4))
-        return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(dy) || !ssd_aligned16(dx) || !ssd_aligned16(workspace) || !ssd_aligned16(U_bwd) ||
-        (relu_mask && !ssd_aligned16(relu_mask)))
-        return SSD_ERR_ALIGN;
-    return wino_conv(mo, dy, Co_pad, U_bwd, g->Ci, dx, g->Ci, g->Ci, nullptr, relu_mask, 0, accumulate, g->N, g->H, g->W, workspace,
-                     workspace_bytes, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, nullptr, g->dil);
+    WinoConv c{};
+    c.mo = mo; c.in = dy; c.U = U_bwd; c.out = dx; c.mask = relu_mask; c.accumulate = accumulate;
+    return wino_dgrad(c, ldy, Co_pad, g, workspace, workspace_bytes, stream);
+}
+extern "C" int ssd_conv3x3_wino_dgrad_bits(const float* dy, int ldy, const float* U_bwd, int Co_pad, float* dx, const uint64_t* relu_bits,
+                                           int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!relu_bits) return SSD_ERR_NULL;
+    WinoConv c{};
+    c.mo = 4; c.in = dy; c.U = U_bwd; c.out = dx; c.mask_bits = bit_words(relu_bits); c.accumulate = accumulate;
+    return wino_dgrad(c, ldy, Co_pad, g, workspace, workspace_bytes, stream);
+}
+extern "C" int ssd_conv3x3_wino_dgrad_planes(const float* dy_planes, const float* U_bwd, int Co_pad, float* dx, const float* relu_mask,
+                                             int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream) {
+    WinoConv c{};
+    c.mo = 4; c.planes = dy_planes; c.U = U_bwd; c.out = dx; c.mask = relu_mask; c.accumulate = accumulate;
+    return wino_dgrad(c, Co_pad, Co_pad, g, workspace, workspace_bytes, stream);
+}
+extern "C" int ssd_conv3x3_wino_dgrad_planes_bits(const float* dy_planes, const float* U_bwd, int Co_pad, float* dx, const uint64_t* relu_bits,
+                                                  int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes,
+                                                  void* stream) {
+    if (!relu_bits) return SSD_ERR_NULL;
+    WinoConv c{};
+    c.mo = 4; c.planes = dy_planes; c.U = U_bwd; c.out = dx; c.mask_bits = bit_words(relu_bits); c.accumulate = accumulate;
+    return wino_dgrad(c, Co_pad, Co_pad, g, workspace, workspace_bytes, stream);
 }
 
 namespace {
@@ -1495,57 +1519,57 @@ extern "C" size_t ssd_conv3x3_wino_wgrad_workspace(const ssd_conv_geom* g, int l
     return w.yb + w.vb + w.zb + w.pb;
 }
 
-// dw (Co,Ci,3,3) OIHW and, if asked, dbias (Co) from x (N,H,W,Ci) and dy (N,H,W,ldy; columns >= Co zero); mo = 2 or 4
 namespace {
+// Blocks of a pass over dy that also leaves the bias gradient's partial sums, one row per block (0: more than 1024 channels, no such
+// pass).  Who launches the pass and who sums its rows must agree, so this is the only copy.  Never below `unit`: the count is rounded
+// UP to a multiple of unit (<= 256) and one unit comes off only from above DY_BIAS_BLOCKS (checked over every c4 and grid_for value).
+int dy_bias_blocks_for(int ldy, size_t tiles) {
+    const int c4 = ldy / 4;
+    if (c4 > 256) return 0;
+    int gcd = 256, r = c4;
+    while (r) { const int tmp = gcd % r; gcd = r; r = tmp; }
+    const int unit = c4 / gcd;
+    int blocks = grid_for(tiles * c4);
+    if (blocks > DY_BIAS_BLOCKS) blocks = DY_BIAS_BLOCKS;
+    blocks = (blocks + unit - 1) / unit * unit;
+    if (blocks > DY_BIAS_BLOCKS) blocks -= unit;
+    return blocks;
+}
+
+// Second half of an F(4x4) weight gradient: the TN GEMMs Zs = Y^T V on untransposed planes (Y NULL: Zs holds the products already), the
+// pre-sum of the K slices, the inverse transform into dw and -- from the bias_blocks rows of partial sums a dy pass left in `part` --
+// dbias.  one_call (wino_wgrad) and the two-call form (ssd_wino4_wgrad_gemm) differ in two places:
+//   bias tail    the final sums ride along as extra blocks of the finish kernel; one_call honours g_bias_tail = 0 (their own launch);
+//   wide layers  dbias asked for without partial sums (bias_blocks == 0): one_call leaves it to its column sums, the two-call form refuses.
+int wgrad4_tail(const float* Y, const float* V, float* Zs, const float* part, int bias_blocks, float* dw, float* dbias, const ssd_conv_geom* g,
+                int ldy, const WinoWgradPlan& w, bool one_call, hipStream_t st) {
+    if (Y != nullptr)
+        if (int e = launch_wgrad_tn(Y, V, Zs, g, ldy, w, st)) return e;
+    const size_t total = (size_t)g->Co * g->Ci;
+    int ks_left = w.ks;
+    if (w.ks > 1 && total / 4 < 65536) {                 // few entries, many splits: sum the splits with a wide grid first
+        hipLaunchKernelGGL(wino_splitk_sum_kernel, dim3(grid_for(total / 4 * w.P)), dim3(256), 0, st, Zs, total, w.P, w.ks);
+        SSD_CHECK_LAUNCH();
+        ks_left = 1;
+    }
+    if (dbias && bias_blocks == 0 && !one_call) return SSD_ERR_BAD_SHAPE;       // more than 1024 channels: use ssd_conv3x3_wino_wgrad_planes
+    const int nfin = grid_for(total / 4), ldp = (g->Co + 3) / 4 * 4;
+    const bool tail = dbias && bias_blocks > 0 && (g_bias_tail || !one_call);
+    const BiasTail bt{tail ? part : nullptr, dbias, bias_blocks, g->Co, ldp};
+    hipLaunchKernelGGL(wino4_wgrad_finish_kernel, dim3(nfin + (tail ? (ldp + 15) / 16 : 0)), dim3(256), 0, st, Zs, dw, g->Co, g->Ci, ks_left,
+                       (size_t)w.ks * total, nfin, bt);
+    SSD_CHECK_LAUNCH();
+    if (dbias && bias_blocks > 0 && !tail) {
+        hipLaunchKernelGGL(colsum_final4_kernel, dim3((ldp + 15) / 16), dim3(256), 0, st, part, dbias, bias_blocks, g->Co, ldp);
+        SSD_CHECK_LAUNCH();
+    }
+    return SSD_OK;
+}
+
+// dw (Co,Ci,3,3) OIHW and, if asked, dbias (Co) from x (N,H,W,Ci) or its kept planes and dy (N,H,W,ldy; columns >= Co zero, or the
+// pooled source `pool` describes); mo = 2 or 4
 int wino_wgrad(const float* x, const float* planes, const float* dy, int ldy, float* dw_oihw, float* dbias, const ssd_conv_geom* g, int mo,
-               float* dgrad_planes, void* workspace, size_t workspace_bytes, void* stream, const PoolSrc* pool = nullptr);
-}
-extern "C" int ssd_conv3x3_wino_wgrad(const float* x, const float* dy, int ldy, float* dw_oihw, float* dbias, const ssd_conv_geom* g,
-                                      int mo, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x) return SSD_ERR_NULL;
-    if (!ssd_aligned16(x)) return SSD_ERR_ALIGN;
-    return wino_wgrad(x, nullptr, dy, ldy, dw_oihw, dbias, g, mo, nullptr, workspace, workspace_bytes, stream);
-}
-extern "C" int ssd_conv3x3_wino_wgrad_planes(const float* planes, const float* dy, int ldy, float* dw_oihw, float* dbias,
-                                             const ssd_conv_geom* g, float* dgrad_planes_out, void* workspace, size_t workspace_bytes,
-                                             void* stream) {
-    if (!planes) return SSD_ERR_NULL;
-    if (!ssd_aligned16(planes) || (dgrad_planes_out && !ssd_aligned16(dgrad_planes_out))) return SSD_ERR_ALIGN;
-    return wino_wgrad(nullptr, planes, dy, ldy, dw_oihw, dbias, g, 4, dgrad_planes_out, workspace, workspace_bytes, stream);
-}
-extern "C" int ssd_conv3x3_wino_dgrad_bits(const float* dy, int ldy, const float* U_bwd, int Co_pad, float* dx, const uint64_t* relu_bits,
-                                           int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!dy || !U_bwd || !dx || !workspace || !relu_bits) return SSD_ERR_NULL;
-    if (!wino_geom_ok(g) || Co_pad % 32 != 0 || Co_pad < g->Co || ldy != Co_pad || g->Ci % 4 != 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(dy) || !ssd_aligned16(dx) || !ssd_aligned16(workspace) || !ssd_aligned16(U_bwd) || ((uintptr_t)relu_bits & 7))
-        return SSD_ERR_ALIGN;
-    return wino_conv(4, dy, Co_pad, U_bwd, g->Ci, dx, g->Ci, g->Ci, nullptr, nullptr, 0, accumulate, g->N, g->H, g->W, workspace, workspace_bytes,
-                     (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<const unsigned long long*>(relu_bits), g->dil);
-}
-extern "C" int ssd_conv3x3_wino_dgrad_planes_bits(const float* dy_planes, const float* U_bwd, int Co_pad, float* dx, const uint64_t* relu_bits,
-                                                  int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes,
-                                                  void* stream) {
-    if (!dy_planes || !U_bwd || !dx || !workspace || !relu_bits) return SSD_ERR_NULL;
-    if (!wino_geom_ok(g) || Co_pad % 32 != 0 || Co_pad < g->Co || g->Ci % 4 != 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(dy_planes) || !ssd_aligned16(dx) || !ssd_aligned16(workspace) || !ssd_aligned16(U_bwd) || ((uintptr_t)relu_bits & 7))
-        return SSD_ERR_ALIGN;
-    return wino_conv(4, nullptr, Co_pad, U_bwd, g->Ci, dx, g->Ci, g->Ci, nullptr, nullptr, 0, accumulate, g->N, g->H, g->W, workspace,
-                     workspace_bytes, (hipStream_t)stream, nullptr, nullptr, dy_planes, nullptr,
-                     reinterpret_cast<const unsigned long long*>(relu_bits), g->dil);
-}
-extern "C" int ssd_conv3x3_wino_dgrad_planes(const float* dy_planes, const float* U_bwd, int Co_pad, float* dx, const float* relu_mask,
-                                             int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!dy_planes || !U_bwd || !dx || !workspace) return SSD_ERR_NULL;
-    if (!wino_geom_ok(g) || Co_pad % 32 != 0 || Co_pad < g->Co || g->Ci % 4 != 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(dy_planes) || !ssd_aligned16(dx) || !ssd_aligned16(workspace) || !ssd_aligned16(U_bwd) ||
-        (relu_mask && !ssd_aligned16(relu_mask)))
-        return SSD_ERR_ALIGN;
-    return wino_conv(4, nullptr, Co_pad, U_bwd, g->Ci, dx, g->Ci, g->Ci, nullptr, relu_mask, 0, accumulate, g->N, g->H, g->W, workspace,
-                     workspace_bytes, (hipStream_t)stream, nullptr, nullptr, dy_planes, nullptr, nullptr, g->dil);
-}
-namespace {
-int wino_wgrad(const float* x, const float* planes, const float* dy, int ldy, float* dw_oihw, float* dbias, const ssd_conv_geom* g, int mo,
-               float* dgrad_planes, void* workspace, size_t workspace_bytes, void* stream, const PoolSrc* pool) {
+               float* dgrad_planes, void* workspace, size_t workspace_bytes, void* stream, const PoolSrc* pool = nullptr) {
     if (!dy || !dw_oihw || !workspace) return SSD_ERR_NULL;
     if (!wino_geom_ok(g) || g->Ci % 4 != 0 || ldy % 4 != 0 || ldy < g->Co || (mo != 2 && mo != 4)) return SSD_ERR_BAD_SHAPE;
     if (!ssd_aligned16(dy) || !ssd_aligned16(workspace) || !ssd_aligned16(dw_oihw)) return SSD_ERR_ALIGN;
@@ -1558,65 +1582,38 @@ int wino_wgrad(const float* x, const float* planes, const float* dy, int ldy, fl
     float* Vt = reinterpret_cast<float*>(base + w.yb);
     float* Zs = reinterpret_cast<float*>(base + w.yb + w.vb);
     float* part = reinterpret_cast<float*>(base + w.yb + w.vb + w.zb);
-    const int gy = (w.Tpad / 32) * ((ldy / 4 + 7) / 8), gx = (w.Tpad / 32) * ((g->Ci / 4 + 7) / 8);
-    const dim3 gyd(gy > 16384 ? 16384 : gy), gxd(gx > 16384 ? 16384 : gx);
-    int dy_bias_blocks = 0;
-    if (dgrad_planes != nullptr && !(mo == 4 && (g_wgrad_tn || planes != nullptr))) return SSD_ERR_BAD_SHAPE;
-    if (g->dil != 1 && (pool != nullptr || !(mo == 4 && (g_wgrad_tn || planes != nullptr)))) return SSD_ERR_BAD_SHAPE;   // dilation: the lattice-aware kernels only
-    if (mo == 4 && (g_wgrad_tn || planes != nullptr)) {
+    const bool tn = mo == 4 && (g_wgrad_tn || planes != nullptr);
+    if (dgrad_planes != nullptr && !tn) return SSD_ERR_BAD_SHAPE;
+    if (g->dil != 1 && (pool != nullptr || !tn)) return SSD_ERR_BAD_SHAPE;   // dilation: the lattice-aware kernels only
+    const int dy_bias_blocks = tn && dbias ? dy_bias_blocks_for(ldy, w.tiles) : 0;       // > 0: bias gradient from the same pass over dy
+    if (tn) {
         // planes in the forward layout [plane][tile][channel]; the GEMM reduces over the tile rows of both.  The x planes are the
         // forward convolution's own B^T d B when the caller kept them.
-        const int c4 = ldy / 4;
-        if (dbias != nullptr && c4 <= 256) {                 // bias gradient from the same pass over dy
-            int gcd = 256, r = c4;
-            while (r) { const int tmp = gcd % r; gcd = r; r = tmp; }
-            const int unit = c4 / gcd;                       // grid must be a multiple of this
-            int blocks = grid_for(w.tiles * c4);
-            if (blocks > DY_BIAS_BLOCKS) blocks = DY_BIAS_BLOCKS;
-            blocks = (blocks + unit - 1) / unit * unit;
-            if (blocks > DY_BIAS_BLOCKS) blocks -= unit;
-            dy_bias_blocks = blocks;
-            launch_dy_pass(dy, Yt, g, ldy, w.lp, part, blocks, dgrad_planes, pool, st);
-        } else
-            launch_dy_pass(dy, Yt, g, ldy, w.lp, nullptr, 0, dgrad_planes, pool, st);
+        launch_dy_pass(dy, Yt, g, ldy, w.lp, part, dy_bias_blocks, dgrad_planes, pool, st);
         if (planes == nullptr)
             hipLaunchKernelGGL(wino4_input_kernel, dim3(grid_for(w.tiles * (g->Ci / 4))), dim3(256), 0, st, x, Vt, g->N, g->H, g->W, g->Ci, w.TH,
                                w.TW, static_cast<unsigned long long*>(nullptr), w.lp.lat);
         SSD_CHECK_LAUNCH();
-        if (int e = launch_wgrad_tn(Yt, planes != nullptr ? planes : Vt, Zs, g, ldy, w, st)) return e;
-    } else if (mo == 2) {
-        hipLaunchKernelGGL(wino_xform_t_kernel<1>, gyd, dim3(256), 0, st, dy, Yt, g->N, g->H, g->W, ldy, w.TH, w.TW, w.Tpad);
-        hipLaunchKernelGGL(wino_xform_t_kernel<0>, gxd, dim3(256), 0, st, x, Vt, g->N, g->H, g->W, g->Ci, w.TH, w.TW, w.Tpad);
+        if (int e = wgrad4_tail(Yt, planes != nullptr ? planes : Vt, Zs, part, dy_bias_blocks, dw_oihw, dbias, g, ldy, w, true, st)) return e;
     } else {
-        hipLaunchKernelGGL(wino4_xform_t_kernel<1>, gyd, dim3(256), 0, st, dy, Yt, g->N, g->H, g->W, ldy, w.TH, w.TW, w.Tpad);
-        hipLaunchKernelGGL(wino4_xform_t_kernel<0>, gxd, dim3(256), 0, st, x, Vt, g->N, g->H, g->W, g->Ci, w.TH, w.TW, w.Tpad);
-    }
-    SSD_CHECK_LAUNCH();
-    if (!(mo == 4 && (g_wgrad_tn || planes != nullptr)))
+        const int gy = (w.Tpad / 32) * ((ldy / 4 + 7) / 8), gx = (w.Tpad / 32) * ((g->Ci / 4 + 7) / 8);
+        const dim3 gyd(gy > 16384 ? 16384 : gy), gxd(gx > 16384 ? 16384 : gx);
+        if (mo == 2) {
+            hipLaunchKernelGGL(wino_xform_t_kernel<1>, gyd, dim3(256), 0, st, dy, Yt, g->N, g->H, g->W, ldy, w.TH, w.TW, w.Tpad);
+            hipLaunchKernelGGL(wino_xform_t_kernel<0>, gxd, dim3(256), 0, st, x, Vt, g->N, g->H, g->W, g->Ci, w.TH, w.TW, w.Tpad);
+        } else {
+            hipLaunchKernelGGL(wino4_xform_t_kernel<1>, gyd, dim3(256), 0, st, dy, Yt, g->N, g->H, g->W, ldy, w.TH, w.TW, w.Tpad);
+            hipLaunchKernelGGL(wino4_xform_t_kernel<0>, gxd, dim3(256), 0, st, x, Vt, g->N, g->H, g->W, g->Ci, w.TH, w.TW, w.Tpad);
+        }
+        SSD_CHECK_LAUNCH();
         if (int e = ssd_internal_gemm_batched(Yt, Vt, Zs, g->Co, w.Tpad, g->Ci, g->Ci, w.P, (size_t)ldy * w.Tpad, (size_t)g->Ci * w.Tpad, w.ks, st))
             return e;
-    if (mo == 2)
-        hipLaunchKernelGGL(wino_wgrad_finish_kernel, dim3(grid_for((size_t)g->Co * g->Ci)), dim3(256), 0, st, Zs, dw_oihw, g->Co, g->Ci, w.ks);
-    else
-    {
-        const size_t total = (size_t)g->Co * g->Ci;
-        int ks_left = w.ks;
-        if (w.ks > 1 && total / 4 < 65536) {                 // few entries, many splits: sum the splits with a wide grid first
-            hipLaunchKernelGGL(wino_splitk_sum_kernel, dim3(grid_for(total / 4 * w.P)), dim3(256), 0, st, Zs, total, w.P, w.ks);
+        if (mo == 2) {
+            hipLaunchKernelGGL(wino_wgrad_finish_kernel, dim3(grid_for((size_t)g->Co * g->Ci)), dim3(256), 0, st, Zs, dw_oihw, g->Co, g->Ci, w.ks);
             SSD_CHECK_LAUNCH();
-            ks_left = 1;
+        } else if (int e = wgrad4_tail(nullptr, nullptr, Zs, part, 0, dw_oihw, dbias, g, ldy, w, true, st)) {
+            return e;
         }
-        const int nfin = grid_for(total / 4), ldp = (g->Co + 3) / 4 * 4;
-        const bool tail = dbias && dy_bias_blocks > 0 && g_bias_tail;    // the bias gradient's final sums ride along as extra blocks
-        const BiasTail bt{tail ? part : nullptr, dbias, dy_bias_blocks, g->Co, ldp};
-        hipLaunchKernelGGL(wino4_wgrad_finish_kernel, dim3(nfin + (tail ? (ldp + 15) / 16 : 0)), dim3(256), 0, st, Zs, dw_oihw, g->Co, g->Ci,
-                           ks_left, (size_t)w.ks * total, nfin, bt);
-    }
-    SSD_CHECK_LAUNCH();
-    if (dbias && dy_bias_blocks > 0 && !g_bias_tail) {
-        const int ldp = (g->Co + 3) / 4 * 4;
-        hipLaunchKernelGGL(colsum_final4_kernel, dim3((ldp + 15) / 16), dim3(256), 0, st, part, dbias, dy_bias_blocks, g->Co, ldp);
-        SSD_CHECK_LAUNCH();
     }
     if (dbias && dy_bias_blocks == 0) {                                  // no partial sums from a dy pass (F(2x2), transposed planes, > 1024 channels)
         const size_t M = (size_t)g->N * g->H * g->W;
@@ -1631,25 +1628,22 @@ int wino_wgrad(const float* x, const float* planes, const float* dy, int ldy, fl
 }
 }  // namespace
 
+extern "C" int ssd_conv3x3_wino_wgrad(const float* x, const float* dy, int ldy, float* dw_oihw, float* dbias, const ssd_conv_geom* g,
+                                      int mo, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x) return SSD_ERR_NULL;
+    if (!ssd_aligned16(x)) return SSD_ERR_ALIGN;
+    return wino_wgrad(x, nullptr, dy, ldy, dw_oihw, dbias, g, mo, nullptr, workspace, workspace_bytes, stream);
+}
+extern "C" int ssd_conv3x3_wino_wgrad_planes(const float* planes, const float* dy, int ldy, float* dw_oihw, float* dbias,
+                                             const ssd_conv_geom* g, float* dgrad_planes_out, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+    if (!planes) return SSD_ERR_NULL;
+    if (!ssd_aligned16(planes) || (dgrad_planes_out && !ssd_aligned16(dgrad_planes_out))) return SSD_ERR_ALIGN;
+    return wino_wgrad(nullptr, planes, dy, ldy, dw_oihw, dbias, g, 4, dgrad_planes_out, workspace, workspace_bytes, stream);
+}
 
 // ---- the weight gradient in two calls: the pass over dy (the data gradient waits for its planes) and the GEMMs + inverse transform
 // (nothing in the backward pass waits for them: the caller may enqueue them on another stream) -----------------------------------------
-namespace {
-int dy_bias_blocks_for(const ssd_conv_geom* g, int ldy, size_t tiles) {
-    const int c4 = ldy / 4;
-    if (c4 > 256) return 0;
-    int gcd = 256, r = c4;
-    while (r) { const int tmp = gcd % r; gcd = r; r = tmp; }
-    const int unit = c4 / gcd;
-    int blocks = grid_for(tiles * c4);
-    if (blocks > DY_BIAS_BLOCKS) blocks = DY_BIAS_BLOCKS;
-    blocks = (blocks + unit - 1) / unit * unit;
-    if (blocks > DY_BIAS_BLOCKS) blocks -= unit;
-    if (blocks < unit) blocks = unit;
-    return blocks;
-}
-}  // namespace
-
 extern "C" size_t ssd_wino4_bias_partial_floats(const ssd_conv_geom* g, int ldy) {
     if (!wino_geom_ok(g) || ldy < g->Co || ldy % 4 != 0) return 0;
     return (size_t)DY_BIAS_BLOCKS * ldy;
@@ -1668,7 +1662,7 @@ int dy_transform(const float* dy, int ldy, const ssd_conv_geom* g, float* wgrad_
     const size_t tiles = (size_t)g->N * lp.TH * lp.TW;
     if (tiles >= (1ull << 31)) return SSD_ERR_BAD_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    const int blocks = bias_partial ? dy_bias_blocks_for(g, ldy, tiles) : 0;
+    const int blocks = bias_partial ? dy_bias_blocks_for(ldy, tiles) : 0;
     if (bias_partial && blocks == 0) return SSD_ERR_BAD_SHAPE;             // more than 1024 channels: use ssd_conv3x3_wino_wgrad_planes
     launch_dy_pass(dy, wgrad_planes, g, ldy, lp, bias_partial, blocks, dgrad_planes_out, pool, st);
     SSD_CHECK_LAUNCH();
@@ -1725,24 +1719,8 @@ extern "C" int ssd_wino4_wgrad_gemm(const float* wgrad_planes, const float* x_pl
     if (!ssd_aligned16(wgrad_planes) || !ssd_aligned16(x_planes) || !ssd_aligned16(dw_oihw) || !ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
     const WinoWgradPlan w = wino_wgrad_plan(g, ldy, 4);
     if (workspace_bytes < w.zb) return SSD_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    float* Zs = static_cast<float*>(workspace);
-    if (int e = launch_wgrad_tn(wgrad_planes, x_planes, Zs, g, ldy, w, st)) return e;
-    const size_t total = (size_t)g->Co * g->Ci;
-    int ks_left = w.ks;
-    if (w.ks > 1 && total / 4 < 65536) {
-        hipLaunchKernelGGL(wino_splitk_sum_kernel, dim3(grid_for(total / 4 * w.P)), dim3(256), 0, st, Zs, total, w.P, w.ks);
-        SSD_CHECK_LAUNCH();
-        ks_left = 1;
-    }
-    const int blocks = dbias ? dy_bias_blocks_for(g, ldy, w.tiles) : 0;
-    if (dbias && blocks == 0) return SSD_ERR_BAD_SHAPE;
-    const int nfin = grid_for(total / 4), ldp = (g->Co + 3) / 4 * 4;
-    const BiasTail bt{dbias ? bias_partial : nullptr, dbias, blocks, g->Co, ldp};
-    hipLaunchKernelGGL(wino4_wgrad_finish_kernel, dim3(nfin + (dbias ? (ldp + 15) / 16 : 0)), dim3(256), 0, st, Zs, dw_oihw, g->Co, g->Ci, ks_left,
-                       (size_t)w.ks * total, nfin, bt);
-    SSD_CHECK_LAUNCH();
-    return SSD_OK;
+    return wgrad4_tail(wgrad_planes, x_planes, static_cast<float*>(workspace), bias_partial, dbias ? dy_bias_blocks_for(ldy, w.tiles) : 0,
+                       dw_oihw, dbias, g, ldy, w, false, (hipStream_t)stream);
 }
 
 // ---- the adjoint-form data gradient (wino4_adj_out_kernel): GEMMs, stand-alone output, output fused with the next dy transform ------
@@ -1807,7 +1785,7 @@ extern "C" int ssd_wino4_adj_output_to_planes(const float* md_planes, const floa
     const size_t tiles = (size_t)g->N * lp.TH * lp.TW;
     hipStream_t st = (hipStream_t)stream;
     if (bias_partial) {
-        const int blocks = dy_bias_blocks_for(g_below, g->Ci, tiles);
+        const int blocks = dy_bias_blocks_for(g->Ci, tiles);
         if (blocks == 0) return SSD_ERR_BAD_SHAPE;
         hipLaunchKernelGGL((wino4_adj_out_kernel<true, true>), dim3(blocks), dim3(256), 0, st, md_planes, g->N, g->H, g->W, g->Ci, lp.TH, lp.TW,
                            static_cast<float*>(nullptr), g->Ci, relu_mask, reinterpret_cast<const unsigned long long*>(relu_bits), 0, y_planes, bias_partial,

@@ -1519,38 +1519,60 @@ def wino_relu_bits(g: ConvGeom, device) -> torch.Tensor:
     return torch.empty((wino_tiles(g), g.Ci // 4), device=device, dtype=torch.int64)
 
 
+def _fwd_wino(name: str, src: torch.Tensor, u_fwd: torch.Tensor, bias: Optional[torch.Tensor], g: ConvGeom, relu: bool, from_planes: bool = False,
+              ld: Optional[int] = None, pool_ceil: Optional[bool] = None, want_argmax: bool = True, keep_planes: bool = False,
+              want_bits: bool = False):
+    """What the three Winograd forward wrappers share once each has checked its own source: filter and bias checks, the workspace,
+    the outputs and the call -> (y or pooled y, argmax or None, kept planes or None, bits or None)."""
+    _wino_filter(u_fwd, "u_fwd", g.Co, g.Ci)
+    if bias is not None:
+        _req(bias, "bias")
+    lib, dev, mo = _lib.load(), src.device, _wino_mo(u_fwd)
+    nbytes = lib.ssd_conv3x3_wino_workspace(C.byref(g), 0, mo)
+    if nbytes == 0:
+        raise ValueError(f"{name}: not a 3x3 / stride 1 / pad 1 geometry")
+    ws = workspace(nbytes, dev, "wino")
+    am = None
+    if pool_ceil is None:
+        ld = g.Co if ld is None else ld
+        y = (torch.empty if ld == g.Co else torch.zeros)((g.N, g.H, g.W, ld), device=dev, dtype=torch.float32)
+    else:
+        ho, wo = pool_out(g.H, 2, 2, 0, pool_ceil), pool_out(g.W, 2, 2, 0, pool_ceil)
+        y = torch.empty((g.N, ho, wo, g.Co), device=dev, dtype=torch.float32)
+        am = torch.empty((g.N, ho, wo, g.Co), device=dev, dtype=torch.uint8) if want_argmax else None
+    planes = wino_planes(g, dev) if keep_planes else None
+    bits = wino_relu_bits(g, dev) if want_bits else None
+    head, tail = (src.data_ptr(), u_fwd.data_ptr(), _ptr(bias)), (ws.data_ptr(), ws.numel(), _stream())
+    if from_planes:
+        dst = (y.data_ptr(), ld, None, None, C.byref(g), int(relu), 0) if pool_ceil is None else \
+            (None, 0, y.data_ptr(), _ptr(am), C.byref(g), 1, int(pool_ceil))
+        status = lib.ssd_conv3x3_wino_fwd_from_planes(*head, *dst, *tail)
+    elif pool_ceil is not None:
+        status = lib.ssd_conv3x3_wino_fwd_pool_bits(*head, y.data_ptr(), _ptr(am), C.byref(g), int(pool_ceil), _ptr(planes), _ptr(bits), *tail)
+    elif keep_planes:
+        status = lib.ssd_conv3x3_wino_fwd_keep_bits(*head, y.data_ptr(), ld, C.byref(g), int(relu), planes.data_ptr(), _ptr(bits), *tail)
+    else:
+        status = lib.ssd_conv3x3_wino_fwd(*head, y.data_ptr(), ld, C.byref(g), int(relu), mo, *tail)
+    check(status, name)
+    return y, am, planes, bits
+
+
 def conv2d_fwd_wino(x: torch.Tensor, u_fwd: torch.Tensor, bias: Optional[torch.Tensor], g: ConvGeom, relu: bool,
                     ld: Optional[int] = None, keep_planes: bool = False, want_bits: bool = False):
     """keep_planes: also return the transformed input (F(4x4) only) for `conv2d_wgrad_wino(..., planes=)` -> (y, planes);
     want_bits (with keep_planes): also the bit mask x > 0 for `conv2d_dgrad_wino(..., bits=)` -> (y, planes, bits)."""
     _req(x, "x")
     mo = _wino_mo(u_fwd)
-    _wino_filter(u_fwd, "u_fwd", g.Co, g.Ci)
     if tuple(x.shape) != (g.N, g.H, g.W, g.Ci):
         raise ValueError("conv2d_fwd_wino: shapes do not match the geometry")
-    if bias is not None:
-        _req(bias, "bias")
-    ld = g.Co if ld is None else ld
-    out = torch.empty((g.N, g.H, g.W, ld), device=x.device, dtype=torch.float32) if ld == g.Co else \
-        torch.zeros((g.N, g.H, g.W, ld), device=x.device, dtype=torch.float32)
-    lib = _lib.load()
-    nbytes = lib.ssd_conv3x3_wino_workspace(C.byref(g), 0, mo)
-    if nbytes == 0:
-        raise ValueError("conv2d_fwd_wino: not a 3x3 / stride 1 / pad 1 geometry")
-    ws = workspace(nbytes, x.device, "wino")
-    if keep_planes:
-        if mo != 4:
-            raise ValueError("conv2d_fwd_wino: keep_planes needs F(4x4,3x3) filters")
-        planes = wino_planes(g, x.device)
-        bits = wino_relu_bits(g, x.device) if want_bits else None
-        check(lib.ssd_conv3x3_wino_fwd_keep_bits(x.data_ptr(), u_fwd.data_ptr(), _ptr(bias), out.data_ptr(), ld, C.byref(g), int(relu),
-                                                 planes.data_ptr(), _ptr(bits), ws.data_ptr(), ws.numel(), _stream()), "conv2d_fwd_wino")
-        return (out, planes, bits) if want_bits else (out, planes)
-    if want_bits:
+    if keep_planes and mo != 4:
+        raise ValueError("conv2d_fwd_wino: keep_planes needs F(4x4,3x3) filters")
+    if want_bits and not keep_planes:
         raise ValueError("conv2d_fwd_wino: want_bits needs keep_planes")
-    check(lib.ssd_conv3x3_wino_fwd(x.data_ptr(), u_fwd.data_ptr(), _ptr(bias), out.data_ptr(), ld, C.byref(g), int(relu), mo, ws.data_ptr(),
-                                   ws.numel(), _stream()), "conv2d_fwd_wino")
-    return out
+    y, _, planes, bits = _fwd_wino("conv2d_fwd_wino", x, u_fwd, bias, g, relu, ld=ld, keep_planes=keep_planes, want_bits=want_bits)
+    if want_bits:
+        return y, planes, bits
+    return (y, planes) if keep_planes else y
 
 
 def conv2d_fwd_wino_pool(x: torch.Tensor, u_fwd: torch.Tensor, bias: Optional[torch.Tensor], g: ConvGeom, ceil_mode: bool,
@@ -1560,23 +1582,10 @@ def conv2d_fwd_wino_pool(x: torch.Tensor, u_fwd: torch.Tensor, bias: Optional[to
     _req(x, "x")
     if _wino_mo(u_fwd) != 4:
         raise ValueError("conv2d_fwd_wino_pool: needs F(4x4,3x3) filters")
-    _wino_filter(u_fwd, "u_fwd", g.Co, g.Ci)
     if tuple(x.shape) != (g.N, g.H, g.W, g.Ci) or g.Co % 4 != 0:
         raise ValueError("conv2d_fwd_wino_pool: shapes do not match the geometry")
-    if bias is not None:
-        _req(bias, "bias")
-    ho, wo = pool_out(g.H, 2, 2, 0, ceil_mode), pool_out(g.W, 2, 2, 0, ceil_mode)
-    y = torch.empty((g.N, ho, wo, g.Co), device=x.device, dtype=torch.float32)
-    am = torch.empty((g.N, ho, wo, g.Co), device=x.device, dtype=torch.uint8) if want_argmax else None
-    lib = _lib.load()
-    nbytes = lib.ssd_conv3x3_wino_workspace(C.byref(g), 0, 4)
-    if nbytes == 0:
-        raise ValueError("conv2d_fwd_wino_pool: not a 3x3 / stride 1 / pad 1 geometry")
-    ws = workspace(nbytes, x.device, "wino")
-    planes = wino_planes(g, x.device) if keep_planes else None
-    bits = wino_relu_bits(g, x.device) if want_bits else None
-    check(lib.ssd_conv3x3_wino_fwd_pool_bits(x.data_ptr(), u_fwd.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(am), C.byref(g), int(ceil_mode),
-                                             _ptr(planes), _ptr(bits), ws.data_ptr(), ws.numel(), _stream()), "conv2d_fwd_wino_pool")
+    y, am, planes, bits = _fwd_wino("conv2d_fwd_wino_pool", x, u_fwd, bias, g, True, pool_ceil=bool(ceil_mode), want_argmax=want_argmax,
+                                    keep_planes=keep_planes, want_bits=want_bits)
     if want_bits:
         return y, am, planes, bits
     return (y, am, planes) if keep_planes else (y, am)
@@ -1589,25 +1598,9 @@ def conv2d_fwd_wino_from_planes(planes: torch.Tensor, u_fwd: torch.Tensor, bias:
     _req(planes, "planes")
     if _wino_mo(u_fwd) != 4 or tuple(planes.shape) != tuple(wino_planes_shape(g)) or g.Co % 4 != 0:
         raise ValueError("conv2d_fwd_wino_from_planes: planes / filters do not match the geometry")
-    _wino_filter(u_fwd, "u_fwd", g.Co, g.Ci)
-    if bias is not None:
-        _req(bias, "bias")
-    lib = _lib.load()
-    nbytes = lib.ssd_conv3x3_wino_workspace(C.byref(g), 0, 4)
-    if nbytes == 0:
-        raise ValueError("conv2d_fwd_wino_from_planes: not a 3x3 / stride 1 / pad 1 geometry")
-    ws = workspace(nbytes, planes.device, "wino")
-    if pool_ceil is None:
-        y = torch.empty((g.N, g.H, g.W, g.Co), device=planes.device, dtype=torch.float32)
-        check(lib.ssd_conv3x3_wino_fwd_from_planes(planes.data_ptr(), u_fwd.data_ptr(), _ptr(bias), y.data_ptr(), g.Co, None, None, C.byref(g), int(relu),
-                                                   0, ws.data_ptr(), ws.numel(), _stream()), "conv2d_fwd_wino_from_planes")
-        return y
-    ho, wo = pool_out(g.H, 2, 2, 0, pool_ceil), pool_out(g.W, 2, 2, 0, pool_ceil)
-    y = torch.empty((g.N, ho, wo, g.Co), device=planes.device, dtype=torch.float32)
-    am = torch.empty((g.N, ho, wo, g.Co), device=planes.device, dtype=torch.uint8) if want_argmax else None
-    check(lib.ssd_conv3x3_wino_fwd_from_planes(planes.data_ptr(), u_fwd.data_ptr(), _ptr(bias), None, 0, y.data_ptr(), _ptr(am), C.byref(g), 1,
-                                               int(pool_ceil), ws.data_ptr(), ws.numel(), _stream()), "conv2d_fwd_wino_from_planes")
-    return y, am
+    y, am, _, _ = _fwd_wino("conv2d_fwd_wino_from_planes", planes, u_fwd, bias, g, relu, from_planes=True, pool_ceil=pool_ceil,
+                            want_argmax=want_argmax)
+    return y if pool_ceil is None else (y, am)
 
 
 def conv2d_dgrad_wino(dy: Optional[torch.Tensor], u_bwd: torch.Tensor, g: ConvGeom, dx: Optional[torch.Tensor] = None,
@@ -1640,19 +1633,12 @@ def conv2d_dgrad_wino(dy: Optional[torch.Tensor], u_bwd: torch.Tensor, g: ConvGe
         _req(bits, "bits", torch.int64)
         if mo != 4 or tuple(bits.shape) != (wino_planes_shape(g)[1], g.Ci // 4) or g.Ci % 4 != 0:
             raise ValueError("conv2d_dgrad_wino: bits need F(4x4) filters and one word per (tile, channel quad)")
-        if planes is None:
-            check(lib.ssd_conv3x3_wino_dgrad_bits(dy.data_ptr(), co_pad, u_bwd.data_ptr(), co_pad, dx.data_ptr(), bits.data_ptr(), int(accumulate),
-                                                  C.byref(g), ws.data_ptr(), ws.numel(), _stream()), "conv2d_dgrad_wino")
-            return dx
-        check(lib.ssd_conv3x3_wino_dgrad_planes_bits(planes.data_ptr(), u_bwd.data_ptr(), co_pad, dx.data_ptr(), bits.data_ptr(), int(accumulate),
-                                                     C.byref(g), ws.data_ptr(), ws.numel(), _stream()), "conv2d_dgrad_wino")
-        return dx
-    if planes is not None:
-        check(lib.ssd_conv3x3_wino_dgrad_planes(planes.data_ptr(), u_bwd.data_ptr(), co_pad, dx.data_ptr(), _ptr(relu_mask), int(accumulate),
-                                                C.byref(g), ws.data_ptr(), ws.numel(), _stream()), "conv2d_dgrad_wino")
-        return dx
-    check(lib.ssd_conv3x3_wino_dgrad(dy.data_ptr(), co_pad, u_bwd.data_ptr(), co_pad, dx.data_ptr(), _ptr(relu_mask), int(accumulate),
-                                     C.byref(g), mo, ws.data_ptr(), ws.numel(), _stream()), "conv2d_dgrad_wino")
+    # one argument list: source (dy and its row length, or the planes), filter, dx, mask (the bits win), then the rest
+    src = (dy.data_ptr(), co_pad) if planes is None else (planes.data_ptr(),)
+    args = (*src, u_bwd.data_ptr(), co_pad, dx.data_ptr(), _ptr(relu_mask) if bits is None else bits.data_ptr(), int(accumulate), C.byref(g),
+            *((mo,) if planes is None and bits is None else ()), ws.data_ptr(), ws.numel(), _stream())
+    entry = "ssd_conv3x3_wino_dgrad" + ("" if planes is None else "_planes") + ("" if bits is None else "_bits")
+    check(getattr(lib, entry)(*args), "conv2d_dgrad_wino")
     return dx
 
 
@@ -1688,18 +1674,14 @@ def conv2d_wgrad_wino(x: Optional[torch.Tensor], dy: torch.Tensor, g: ConvGeom, 
     db = _grad_dst(db_out, (g.Co,), dev, "db_out") if want_bias else None
     if dgrad_planes and planes is None:
         raise ValueError("conv2d_wgrad_wino: dgrad_planes needs the kept forward planes")
-    if planes is not None:
-        pd = torch.empty((36, planes.shape[1], ldy), device=dev, dtype=torch.float32) if dgrad_planes else None
-        if pooled:
-            check(lib.ssd_conv3x3_wino_wgrad_planes_pooled(planes.data_ptr(), *_pooled_args(dy, g, ldy), ldy, dw.data_ptr(), _ptr(db), C.byref(g),
-                                                           _ptr(pd), ws.data_ptr(), ws.numel(), _stream()), "conv2d_wgrad_wino_pooled")
-            return (dw, db, pd) if dgrad_planes else (dw, db)
-        check(lib.ssd_conv3x3_wino_wgrad_planes(planes.data_ptr(), dy.data_ptr(), ldy, dw.data_ptr(), _ptr(db), C.byref(g), _ptr(pd),
-                                                ws.data_ptr(), ws.numel(), _stream()), "conv2d_wgrad_wino")
-        return (dw, db, pd) if dgrad_planes else (dw, db)
-    check(lib.ssd_conv3x3_wino_wgrad(x.data_ptr(), dy.data_ptr(), ldy, dw.data_ptr(), _ptr(db), C.byref(g), mo, ws.data_ptr(), ws.numel(),
-                                     _stream()), "conv2d_wgrad_wino")
-    return dw, db
+    pd = torch.empty((36, planes.shape[1], ldy), device=dev, dtype=torch.float32) if dgrad_planes else None
+    suffix, src = _dy_source(dy, g, ldy)
+    # one argument list: x or its kept planes, the gradient's source, the outputs, then mo (from x) or the dgrad planes (from planes)
+    args = ((x if planes is None else planes).data_ptr(), *src, ldy, dw.data_ptr(), _ptr(db), C.byref(g), mo if planes is None else _ptr(pd),
+            ws.data_ptr(), ws.numel(), _stream())
+    entry = "ssd_conv3x3_wino_wgrad" + ("" if planes is None else "_planes" + suffix)
+    check(getattr(lib, entry)(*args), "conv2d_wgrad_wino" + suffix)
+    return (dw, db, pd) if dgrad_planes else (dw, db)
 
 
 def wino_dy_transform(dy: torch.Tensor, g: ConvGeom, ldy: int, dgrad_planes: bool = True, want_bias: bool = True):
@@ -1714,11 +1696,9 @@ def wino_dy_transform(dy: torch.Tensor, g: ConvGeom, ldy: int, dgrad_planes: boo
     Y = torch.empty((36, tiles, ldy), device=dev, dtype=torch.float32)
     Vd = torch.empty((36, tiles, ldy), device=dev, dtype=torch.float32) if dgrad_planes else None
     part = torch.empty((lib.ssd_wino4_bias_partial_floats(C.byref(g), ldy),), device=dev, dtype=torch.float32) if want_bias else None
-    if pooled:
-        check(lib.ssd_wino4_dy_transform_pooled(*_pooled_args(dy, g, ldy), ldy, C.byref(g), Y.data_ptr(), _ptr(Vd), _ptr(part), _stream()),
-              "wino_dy_transform_pooled")
-    else:
-        check(lib.ssd_wino4_dy_transform(dy.data_ptr(), ldy, C.byref(g), Y.data_ptr(), _ptr(Vd), _ptr(part), _stream()), "wino_dy_transform")
+    suffix, src = _dy_source(dy, g, ldy)
+    check(getattr(lib, "ssd_wino4_dy_transform" + suffix)(*src, ldy, C.byref(g), Y.data_ptr(), _ptr(Vd), _ptr(part), _stream()),
+          "wino_dy_transform" + suffix)
     return Y, Vd, part
 
 
@@ -1825,10 +1805,14 @@ class PooledGrad:
         return maxpool_bwd(self.dpool, self.argmax, self.in_shape, 2, 2, 0, dx, y_gate=self.y_pooled)
 
 
-def _pooled_args(dy: "PooledGrad", g: ConvGeom, ldy: int):
+def _dy_source(dy, g: ConvGeom, ldy: int):
+    """The gradient a weight-gradient entry reads -> (suffix of the entry's name, its leading arguments): a tensor, or a `PooledGrad`
+    for the `_pooled` entries."""
+    if not isinstance(dy, PooledGrad):
+        return "", (dy.data_ptr(),)
     if dy.in_shape != (g.N, g.H, g.W, g.Co) or ldy != g.Co:
         raise ValueError("pooled gradient does not match the geometry")
-    return dy.dpool.data_ptr(), dy.argmax.data_ptr(), dy.y_pooled.data_ptr(), dy.dpool.shape[1], dy.dpool.shape[2]
+    return "_pooled", (dy.dpool.data_ptr(), dy.argmax.data_ptr(), dy.y_pooled.data_ptr(), dy.dpool.shape[1], dy.dpool.shape[2])
 
 
 def wino_wgrad_gemm(wgrad_planes: torch.Tensor, x_planes: torch.Tensor, bias_partial: Optional[torch.Tensor], g: ConvGeom, ldy: int,
