@@ -131,8 +131,25 @@ int ssd_conv1_first_fwd_bf16(const float* x_nchw, const float* w_rows, const flo
 int ssd_conv1_first_wgrad_bf16(const float* x_nchw, const void* dy_nhwc_bf16, float* dw_rows, float* dbias, int N, int H, int W,
                                void* workspace, size_t workspace_bytes, void* stream);
 /* Max pooling (Model.py:135-142), conv4_3 L2 normalisation (Model.py:206-209) and the heads' gradient gather on bf16 NHWC tensors
- * (C % 8 == 0; argmax codes as in ssd_maxpool_fwd; f32 arithmetic, one rounding at the store).  ssd_maxpool_bwd_bf16: relu_mask (the bf16
- * activation, dx kept where > 0) and accumulate, or y_gate (the bf16 pooled output: the gated form, no accumulate). */
+ * (C % 8 == 0; argmax codes as in ssd_maxpool_fwd; f32 arithmetic, one rounding at the store; the L2 norm's backward carries its two row sums and dx, whose two
+ * terms cancel, in f64, so that dx is the exact value rounded).  ssd_maxpool_bwd_bf16: relu_mask (the bf16
+ * activation, dx kept where > 0) and accumulate, or y_gate (the bf16 pooled output: the gated form, no accumulate).
+ *
+ * REFUSALS of the pool, L2-norm, head, cast and channel_affine entries, f32 and bf16 alike.  Each is made before anything is enqueued,
+ * and where several apply the first of this list is returned:
+ *   1. SSD_ERR_NULL       a required pointer is NULL (optional: the forward's argmax, relu_mask, the bf16 backward's y_gate);
+ *   2. SSD_ERR_BAD_SHAPE  a count (N, H, W, C, Ho, Wo, M, HW, A, n_classes, n) <= 0; C no multiple of the vector (4 channels in f32 and in
+ *                         channel_affine, 8 in bf16; 512 exactly for the L2 norm; n % 8 for the casts); k outside 1..15, stride <= 0, pad < 0;
+ *                         in the pool forward also 2*pad > k and a last window that lies wholly outside the input
+ *                         ((Ho-1)*stride - pad >= H, the same for W); y_gate together with relu_mask or accumulate; heads: ld below
+ *                         A*(4+n_classes), prior_off < 0, prior_off + HW*A > P;
+ *   3. SSD_ERR_ALIGN      a tensor, gamma, scale, shift, a given relu_mask or y_gate not 16-byte aligned; given argmax codes not aligned to
+ *                         one thread's codes (4 bytes in f32, 8 in bf16).  The heads' buffers are accessed by element: no alignment rule;
+ *   4. SSD_ERR_WORKSPACE  workspace_bytes below the entry's query.
+ * The other entries of the same two source files -- the weight re-layouts, ssd_im2col_first, ssd_im2col_nchw3, ssd_clock_probe,
+ * ssd_graph_node_counts, ssd_sgd_momentum(_guarded) -- refuse in the same order: a NULL required pointer (grad_scale_dev is optional); then
+ * a count <= 0, Co_pad < Co, pad < 0, Kpad no multiple of 4 or below R*S*3, Ho / Wo that are not the convolution's; then an im2col `out`
+ * that is not 16-byte aligned.  The SGD entries take n == 0 as SSD_OK. */
 int ssd_maxpool_fwd_bf16(const void* x, void* y, uint8_t* argmax, int N, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo,
                          void* stream);
 int ssd_maxpool_bwd_bf16(const void* dy, const uint8_t* argmax, void* dx, const void* relu_mask, const void* y_gate, int accumulate, int N,
@@ -143,7 +160,9 @@ int ssd_l2norm_bwd_bf16(const void* x, const float* gamma, const void* dy, void*
                         size_t workspace_bytes, void* stream);
 int ssd_heads_gather_bf16(const float* dloc, const float* dconf, void* packed_bf16, int ld, int N, int HW, int A, int prior_off, int P,
                           int ncls, void* stream);
-int ssd_cast_f32_bf16(const float* x, void* y_bf16, size_t n, void* stream);      /* n % 8 == 0 */
+/* n % 8 == 0.  f32 -> bf16 rounds to nearest even over the whole range -- ties, f32 and bf16 subnormals, overflow to inf -- and keeps a
+ * NaN a NaN; bf16 -> f32 is exact, bit for bit. */
+int ssd_cast_f32_bf16(const float* x, void* y_bf16, size_t n, void* stream);
 int ssd_cast_bf16_f32(const void* x_bf16, float* y, size_t n, void* stream);
 /* ssd_weights_prepare job kind 3: out_fwd = bf16 OHWI [co_pad][taps][ci], out_bwd = bf16 IHWO [ci][taps][pad1] (pad1 >= co, zero filled). */
 
@@ -397,7 +416,8 @@ int ssd_channel_affine(const float* x, const float* scale, const float* shift, f
                        void* stream);
 
 /* ---- max pooling (Model.py:137,142 nn.MaxPool2d incl. ceil_mode; features[4,9,23]) ----
- * argmax: uint8 window-relative index (r*k+s) of the first maximum, for backward. */
+ * argmax: uint8 window-relative index (r*k+s) of the first maximum, for backward.  A NaN replaces the running maximum (torch's rule), so
+ * the last NaN of a window wins.  What these entries, the L2 norm and the heads refuse: REFUSALS above, next to the bf16 forms. */
 int ssd_maxpool_fwd(const float* x, float* y, uint8_t* argmax, int N, int H, int W, int C,
                     int k, int stride, int pad, int Ho, int Wo, void* stream);
 /* dx (+)= routed dy; if relu_mask != NULL dx = relu_mask > 0 ? dx : 0. */

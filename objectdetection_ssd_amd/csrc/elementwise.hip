@@ -509,10 +509,11 @@ extern "C" int ssd_channel_affine(const float* x, const float* scale, const floa
 extern "C" int ssd_maxpool_fwd(const float* x, float* y, uint8_t* argmax, int N, int H, int W, int C, int k, int stride,
                                int pad, int Ho, int Wo, void* stream) {
     if (!x || !y) return SSD_ERR_NULL;
-    if (C % 4 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0 || 2 * pad > k || Ho <= 0 || Wo <= 0) return SSD_ERR_BAD_SHAPE;
+    if (C <= 0 || C % 4 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0 || 2 * pad > k || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
+        return SSD_ERR_BAD_SHAPE;
     // every window must contain at least one valid element (torch guarantees this for its own Ho/Wo)
     if ((Ho - 1) * stride - pad >= H || (Wo - 1) * stride - pad >= W) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(x) || !ssd_aligned16(y)) return SSD_ERR_ALIGN;
+    if (!ssd_aligned16(x) || !ssd_aligned16(y) || (argmax && ((uintptr_t)argmax & 3))) return SSD_ERR_ALIGN;
     const size_t total = (size_t)N * Ho * Wo * (C / 4);
     hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, argmax, N, H, W, C, k, stride, pad, Ho, Wo);
     SSD_CHECK_LAUNCH();
@@ -521,8 +522,9 @@ extern "C" int ssd_maxpool_fwd(const float* x, float* y, uint8_t* argmax, int N,
 extern "C" int ssd_maxpool_bwd(const float* dy, const uint8_t* argmax, float* dx, const float* relu_mask, int accumulate,
                                int N, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo, void* stream) {
     if (!dy || !argmax || !dx) return SSD_ERR_NULL;
-    if (C % 4 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(dy) || !ssd_aligned16(dx)) return SSD_ERR_ALIGN;
+    if (C <= 0 || C % 4 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0 || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
+        return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(dy) || !ssd_aligned16(dx) || ((uintptr_t)argmax & 3) || (relu_mask && !ssd_aligned16(relu_mask))) return SSD_ERR_ALIGN;
     const size_t total = (size_t)N * H * W * (C / 4);
     hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, dy, argmax, dx, relu_mask,
                        static_cast<const float*>(nullptr), accumulate, N, H, W, C, k, stride, pad, Ho, Wo);
@@ -532,9 +534,10 @@ extern "C" int ssd_maxpool_bwd(const float* dy, const uint8_t* argmax, float* dx
 extern "C" int ssd_maxpool_bwd_gated(const float* dy, const uint8_t* argmax, const float* y, float* dx, int N, int H, int W, int C,
                                      int k, int stride, int pad, int Ho, int Wo, void* stream) {
     if (!dy || !argmax || !y || !dx) return SSD_ERR_NULL;
-    if (C % 4 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(dy) || !ssd_aligned16(dx) || !ssd_aligned16(y)) return SSD_ERR_ALIGN;
-    if (k == 2 && stride == 2 && pad == 0 && 2 * Ho >= H && 2 * Wo >= W && ((uintptr_t)argmax & 3) == 0) {
+    if (C <= 0 || C % 4 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0 || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
+        return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(dy) || !ssd_aligned16(dx) || !ssd_aligned16(y) || ((uintptr_t)argmax & 3)) return SSD_ERR_ALIGN;
+    if (k == 2 && stride == 2 && pad == 0 && 2 * Ho >= H && 2 * Wo >= W) {
         hipLaunchKernelGGL(maxpool2_bwd_scatter_kernel, dim3(grid_for((size_t)N * Ho * Wo * (C / 4))), dim3(256), 0, (hipStream_t)stream, dy,
                            argmax, y, dx, N, H, W, C, Ho, Wo);
         SSD_CHECK_LAUNCH();
@@ -550,6 +553,7 @@ extern "C" int ssd_maxpool_bwd_gated(const float* dy, const uint8_t* argmax, con
 extern "C" int ssd_l2norm_fwd(const float* x, const float* gamma, float* y, int M, int C, void* stream) {
     if (!x || !gamma || !y) return SSD_ERR_NULL;
     if (C != 512 || M <= 0) return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(x) || !ssd_aligned16(y) || !ssd_aligned16(gamma)) return SSD_ERR_ALIGN;
     const int blocks = ssd_cdiv(M, 4) > 2048 ? 2048 : ssd_cdiv(M, 4);
     hipLaunchKernelGGL(l2norm_fwd_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, gamma, y, M);
     SSD_CHECK_LAUNCH();
@@ -561,6 +565,7 @@ extern "C" int ssd_l2norm_bwd(const float* x, const float* gamma, const float* d
                               void* ws, size_t ws_bytes, void* stream) {
     if (!x || !gamma || !dy || !dx || !dgamma || !ws) return SSD_ERR_NULL;
     if (C != 512 || M <= 0) return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(x) || !ssd_aligned16(dy) || !ssd_aligned16(dx) || !ssd_aligned16(gamma)) return SSD_ERR_ALIGN;
     if (ws_bytes < ssd_l2norm_bwd_workspace(M, C)) return SSD_ERR_WORKSPACE;
     const int blocks = l2norm_bwd_blocks(M);
     hipStream_t st = (hipStream_t)stream;
@@ -574,7 +579,7 @@ extern "C" int ssd_l2norm_bwd(const float* x, const float* gamma, const float* d
 extern "C" int ssd_heads_scatter(const float* packed, int ld, float* loc, float* conf, int N, int HW, int A, int prior_off,
                                  int P, int ncls, void* stream) {
     if (!packed || !loc || !conf) return SSD_ERR_NULL;
-    if (ld < A * (4 + ncls) || prior_off < 0 || prior_off + HW * A > P) return SSD_ERR_BAD_SHAPE;
+    if (N <= 0 || HW <= 0 || A <= 0 || ncls <= 0 || ld < A * (4 + ncls) || prior_off < 0 || prior_off + HW * A > P) return SSD_ERR_BAD_SHAPE;
     const size_t total = (size_t)N * HW * A * (4 + ncls);
     hipLaunchKernelGGL(heads_scatter_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, packed, ld, loc, conf, N, HW, A, prior_off, P, ncls);
     SSD_CHECK_LAUNCH();
@@ -583,7 +588,7 @@ extern "C" int ssd_heads_scatter(const float* packed, int ld, float* loc, float*
 extern "C" int ssd_heads_gather(const float* dloc, const float* dconf, float* packed, int ld, int N, int HW, int A,
                                 int prior_off, int P, int ncls, void* stream) {
     if (!packed || !dloc || !dconf) return SSD_ERR_NULL;
-    if (ld < A * (4 + ncls) || prior_off < 0 || prior_off + HW * A > P) return SSD_ERR_BAD_SHAPE;
+    if (N <= 0 || HW <= 0 || A <= 0 || ncls <= 0 || ld < A * (4 + ncls) || prior_off < 0 || prior_off + HW * A > P) return SSD_ERR_BAD_SHAPE;
     const size_t total = (size_t)N * HW * ld;
     hipLaunchKernelGGL(heads_gather_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, dloc, dconf, packed, ld, N, HW, A, prior_off, P, ncls);
     SSD_CHECK_LAUNCH();

@@ -1,7 +1,7 @@
 // HBM-bound NHWC kernels of the bf16-tensor mode (BASELINE.json configs[2]; activations and gradients stored in bf16):
 // max pooling (Model.py:135-142 pools), conv4_3 L2 normalisation (Model.py:206-209), the heads' gradient gather, casts.
 // Same arithmetic as csrc/elementwise.hip in f32 registers; tensors move as 8 channels = 16 bytes per lane, results are
-// rounded to bf16 once, at the store.  Max pooling of bf16 values is exact (max commutes with the monotone rounding).
+// rounded to bf16 once, at the store (the L2 norm's backward forms dx in f64: see there).  Max pooling of bf16 values is exact (max commutes with the monotone rounding).
 #include "common.h"
 
 namespace {
@@ -26,6 +26,12 @@ __device__ __forceinline__ void st8(__bf16* p, const f32x8 v) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (__bf16)v[e];
     *reinterpret_cast<bf16x8*>(p) = o;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
 }
 
 // thread = (n, oh, ow, 8 channels); torch semantics: the first valid element seeds the max, a later one replaces it if larger or NaN
@@ -178,21 +184,25 @@ __global__ __launch_bounds__(256) void l2norm_bwd_bf16_kernel(const __bf16* __re
     for (int m = blockIdx.x * 4 + wave; m < M; m += gridDim.x * 4) {
         const size_t o = (size_t)m * 512 + lane * 8;
         const f32x8 v = ld8(x + o), d = ld8(dy + o);
-        float ss = 0.f, dot = 0.f;
+        // The two terms of dx cancel (dx is orthogonal to x after the gamma scaling): to a millionth of their size on real rows.  The
+        // stored bf16 value must still be the exact one rounded, so the row sums and the difference are carried in f64 (products of
+        // two bf16 values are exact in f32); the kernel stays bound by its loads and stores.
+        double ss = 0.0, dot = 0.0;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            ss += v[e] * v[e];
-            dot += v[e] * d[e] * g[e];
+            ss += (double)(v[e] * v[e]);
+            dot += (double)(v[e] * d[e]) * (double)g[e];
         }
-        ss = wave_sum(ss);
-        dot = wave_sum(dot);
-        const float inv = 1.f / sqrtf(ss);
-        const float coef = dot * inv * inv * inv;
+        ss = wave_sum_f64(ss);
+        dot = wave_sum_f64(dot);
+        const double inv = 1.0 / sqrt(ss);
+        const double coef = dot * inv * inv * inv;
+        const float inv32 = (float)inv;
         f32x8 r;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            r[e] = g[e] * d[e] * inv - v[e] * coef;
-            dg[e] += d[e] * v[e] * inv;
+            r[e] = (float)((double)g[e] * (double)d[e] * inv - (double)v[e] * coef);
+            dg[e] += d[e] * v[e] * inv32;
         }
         st8(dx + o, r);
     }
@@ -256,7 +266,10 @@ __global__ __launch_bounds__(256) void cast_bf16_f32_kernel(const __bf16* __rest
 extern "C" int ssd_maxpool_fwd_bf16(const void* x, void* y, uint8_t* argmax, int N, int H, int W, int C, int k, int stride, int pad, int Ho,
                                     int Wo, void* stream) {
     if (!x || !y) return SSD_ERR_NULL;
-    if (C % 8 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0 || N <= 0 || Ho <= 0 || Wo <= 0) return SSD_ERR_BAD_SHAPE;
+    if (C <= 0 || C % 8 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0 || 2 * pad > k || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
+        return SSD_ERR_BAD_SHAPE;
+    // every window must contain at least one valid element (torch guarantees this for its own Ho/Wo): `best` starts unset
+    if ((Ho - 1) * stride - pad >= H || (Wo - 1) * stride - pad >= W) return SSD_ERR_BAD_SHAPE;
     if (!ssd_aligned16(x) || !ssd_aligned16(y) || (argmax && ((uintptr_t)argmax & 7))) return SSD_ERR_ALIGN;
     const size_t total = (size_t)N * Ho * Wo * (C / 8);
     hipLaunchKernelGGL(maxpool_fwd_bf16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, static_cast<const __bf16*>(x),
@@ -268,7 +281,8 @@ extern "C" int ssd_maxpool_fwd_bf16(const void* x, void* y, uint8_t* argmax, int
 extern "C" int ssd_maxpool_bwd_bf16(const void* dy, const uint8_t* argmax, void* dx, const void* relu_mask, const void* y_gate, int accumulate,
                                     int N, int H, int W, int C, int k, int stride, int pad, int Ho, int Wo, void* stream) {
     if (!dy || !argmax || !dx) return SSD_ERR_NULL;
-    if (C % 8 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0 || N <= 0) return SSD_ERR_BAD_SHAPE;
+    if (C <= 0 || C % 8 != 0 || k <= 0 || k > 15 || stride <= 0 || pad < 0 || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
+        return SSD_ERR_BAD_SHAPE;
     if (y_gate && (accumulate || relu_mask)) return SSD_ERR_BAD_SHAPE;
     if (!ssd_aligned16(dy) || !ssd_aligned16(dx) || ((uintptr_t)argmax & 7) || (relu_mask && !ssd_aligned16(relu_mask)) ||
         (y_gate && !ssd_aligned16(y_gate)))
@@ -290,7 +304,7 @@ extern "C" int ssd_maxpool_bwd_bf16(const void* dy, const uint8_t* argmax, void*
 extern "C" int ssd_l2norm_fwd_bf16(const void* x, const float* gamma, void* y, int M, int C, void* stream) {
     if (!x || !gamma || !y) return SSD_ERR_NULL;
     if (C != 512 || M <= 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(x) || !ssd_aligned16(y)) return SSD_ERR_ALIGN;
+    if (!ssd_aligned16(x) || !ssd_aligned16(y) || !ssd_aligned16(gamma)) return SSD_ERR_ALIGN;
     const int blocks = ssd_cdiv(M, 4) > 2048 ? 2048 : ssd_cdiv(M, 4);
     hipLaunchKernelGGL(l2norm_fwd_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, static_cast<const __bf16*>(x), gamma,
                        static_cast<__bf16*>(y), M);
@@ -304,7 +318,7 @@ extern "C" int ssd_l2norm_bwd_bf16(const void* x, const float* gamma, const void
                                    size_t workspace_bytes, void* stream) {
     if (!x || !gamma || !dy || !dx || !dgamma || !workspace) return SSD_ERR_NULL;
     if (C != 512 || M <= 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(x) || !ssd_aligned16(dy) || !ssd_aligned16(dx)) return SSD_ERR_ALIGN;
+    if (!ssd_aligned16(x) || !ssd_aligned16(dy) || !ssd_aligned16(dx) || !ssd_aligned16(gamma)) return SSD_ERR_ALIGN;
     const int blocks = l2norm_bwd_bf16_blocks(M);
     if (workspace_bytes < (size_t)blocks * 512 * sizeof(float)) return SSD_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -320,7 +334,7 @@ extern "C" int ssd_l2norm_bwd_bf16(const void* x, const float* gamma, const void
 extern "C" int ssd_heads_gather_bf16(const float* dloc, const float* dconf, void* packed, int ld, int N, int HW, int A, int prior_off, int P,
                                      int ncls, void* stream) {
     if (!dloc || !dconf || !packed) return SSD_ERR_NULL;
-    if (N <= 0 || HW <= 0 || A <= 0 || ld < A * (4 + ncls) || prior_off < 0 || prior_off + HW * A > P) return SSD_ERR_BAD_SHAPE;
+    if (N <= 0 || HW <= 0 || A <= 0 || ncls <= 0 || ld < A * (4 + ncls) || prior_off < 0 || prior_off + HW * A > P) return SSD_ERR_BAD_SHAPE;
     const size_t total = (size_t)N * HW * ld;
     hipLaunchKernelGGL(heads_gather_bf16_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, dloc, dconf,
                        static_cast<__bf16*>(packed), ld, N, HW, A, prior_off, P, ncls);
