@@ -14,8 +14,8 @@ from __future__ import annotations
 
 import numbers
 from collections import namedtuple
-from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from dataclasses import dataclass, replace
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -178,6 +178,96 @@ def _stacked(tensors) -> torch.Tensor:
     return tensors[0] if len(tensors) == 1 else torch.cat(list(tensors), 0)
 
 
+@dataclass
+class _Filter:
+    """One layer's filter re-laid in one layout family (`_FAMILIES`): what the weight cache holds."""
+    sig: tuple                                  # (data_ptr, _version) per source tensor (+ limb-GEMM form, adjoint flag: Winograd)
+    fwd: torch.Tensor                           # the forward's layout
+    bwd: Optional[torch.Tensor] = None          # the data gradient's layout (`layout`: built on first request)
+    fwd_limbs: Optional[torch.Tensor] = None    # `layout`, f32x3 and bf16-operand modes: the bf16 limb planes of fwd / bwd
+    bwd_limbs: Optional[torch.Tensor] = None
+    oihw: Optional[torch.Tensor] = None         # `layout`, built per layer: the stacked OIHW source a later bwd is made from
+
+
+@dataclass(frozen=True)
+class _Family:
+    """One filter layout family: how its record is built for one layer, and how the batched weight table builds the same."""
+    slot: str                                   # family part of the cache key (the two Winograd forms share one slot per layer)
+    job: int                                    # kind number of its `ssd_weights_prepare` job
+    alloc: Callable                             # (co, ci, taps, co_pad, device) -> (fwd, bwd or None): the job's output buffers
+    build: Callable                             # (engine, layer, contiguous stacked OIHW filter, adj) -> (fwd, bwd or None), per layer
+    adj: bool = False                           # Winograd: bwd in the adjoint form
+    job_fields: Callable = lambda co, bwd: {}   # what its job sets besides the common fields
+    lazy: Optional[Callable] = None             # (engine, layer, record, need_bwd): fields filled on request, at every lookup
+
+
+def _build_wino(eng, L, w, adj):
+    uf, ub = ops.wino_weights(w, L.co_pad, want_bwd=not adj, mo=eng.WINO_TILE)
+    return uf, ops.wino_adj_weights(w, L.co_pad) if adj else ub
+
+
+def _layout_on_request(eng, L, rec, need_bwd):
+    if need_bwd and rec.bwd is None:
+        rec.bwd = ops.weight_ihwo(rec.oihw, L.co_pad)
+    if eng.x3 or (eng.bf16 and not eng.bf16_tensors):         # pre-split limb planes of the layouts in use
+        if rec.fwd_limbs is None:
+            rec.fwd_limbs = ops.weight_split3(rec.fwd)
+        if need_bwd and rec.bwd_limbs is None:
+            rec.bwd_limbs = ops.weight_split3(rec.bwd)
+
+
+# Keyed by what `_Engine._table_kind` answers, plus conv1_1's own family.  A new family is a row here and an answer there.
+_FAMILIES: Dict[str, _Family] = {
+    "first": _Family("first", 2, lambda co, ci, taps, co_pad, dev: (ops.first_rows_alloc(co, dev), None),       # conv1_1: [64][32] rows
+                     lambda eng, L, w, adj: (ops.first_weight_rows(w), None)),
+    "layout": _Family("layout", 1,                             # direct kernels: OHWI [co_pad][T][Ci] / IHWO [Ci][T][co_pad]
+                      lambda co, ci, taps, co_pad, dev: tuple(ops.layout_filter_alloc(ci, taps, co_pad, dev, bwd=b) for b in (False, True)),
+                      lambda eng, L, w, adj: (ops.weight_ohwi(w, L.co_pad), None), lazy=_layout_on_request),
+    "wino": _Family("wino", 0,                                 # Winograd domain: U_fwd [P][Co][Ci], U_bwd [P][Ci][co_pad] of the rotated filter
+                    lambda co, ci, taps, co_pad, dev: (ops.wino_filter_alloc(4, co, ci, dev), ops.wino_filter_alloc(4, ci, co_pad, dev)),
+                    _build_wino),
+    "x31": _Family("x31", 4,                                   # limb planes of a 1x1 filter and of its transpose
+                   lambda co, ci, taps, co_pad, dev: (ops.x3_filter_alloc(co, ci, dev), ops.x3_filter_alloc(ci, co_pad, dev)),
+                   lambda eng, L, w, adj: ops.conv1x1_weights_x3(w, L.co_pad)),
+    "b16": _Family("b16", 3,                                   # bf16 OHWI / IHWO copies of a 3x3 filter; the job's row counts are the buffers'
+                   lambda co, ci, taps, co_pad, dev: tuple(ops.bf16_filter_alloc(co, ci, dev, bwd=b) for b in (False, True)),
+                   lambda eng, L, w, adj: ops.weights_bf16(w), job_fields=lambda co, bwd: dict(co_pad=co, pad1=int(bwd.shape[2]))),
+}
+# ... U_bwd instead the forward transform laid out [Ci][co_pad], for the adjoint data gradient
+_FAMILIES["wino_adj"] = replace(_FAMILIES["wino"], adj=True, job_fields=lambda co, bwd: dict(adj=True))
+
+# A training forward's batched weight table: what it was built for, the `ops.WeightTable`, per job (family name, layer, fwd buffer, bwd or None)
+_TableFill = namedtuple("_TableFill", "sig table entries")
+
+
+class _FilterCache(dict):
+    """The engine's re-laid filters: (family slot, layer key) -> `_Filter`.  `clear()` drops the records; the weight table `fill`,
+    whose buffers persist across steps, stays."""
+    fill: Optional[_TableFill] = None
+
+    @staticmethod
+    def sig(fam: _Family, L: _Layer, P) -> tuple:
+        sig = tuple((t.data_ptr(), t._version) for t in L.filter(P))
+        return sig + (ops.wino_x3(4, 256), fam.adj) if fam.slot == "wino" else sig      # + the GEMM form the filters were laid out for
+
+    def lookup(self, fam: _Family, L: _Layer, P, build: Callable) -> _Filter:
+        """The layer's record in this family if it was made from what `sig` sees now; else build(sig, the layer's contiguous stacked
+        OIHW filter), stored in its place."""
+        sig, at = self.sig(fam, L, P), (fam.slot, L.key)
+        rec = self.get(at)
+        if rec is None or rec.sig != sig:
+            rec = self[at] = build(sig, _stacked(L.filter(P)).detach().contiguous())
+        return rec
+
+    def tensors(self) -> list:
+        """Every tensor of every record (what a captured graph that read them must keep alive)."""
+        return [t for r in self.values() for t in (r.fwd, r.bwd, r.fwd_limbs, r.bwd_limbs, r.oihw) if t is not None]
+
+    def kinds(self) -> Dict[str, str]:
+        """{layer key: family name} of the last table filling (kept, like the table, across `clear()`)."""
+        return {} if self.fill is None else {L.key: name for name, L, _, _ in self.fill.entries}
+
+
 # What `_Engine._path` answers for one layer:
 #   kind        "b16" (csrc/conv_bf16.hip on bf16 tensors) | "wino" (Winograd F(4x4) / F(2x2)) | "x31" (1x1 limb GEMMs) | "direct" (igemm)
 #   cast16      b16: the input is an f32 tensor and the layer (a head) runs on a bf16 copy of it; its dx goes back as f32
@@ -257,8 +347,7 @@ class _Engine:
         self.overlap_wgrad = False
         self._wgrad_stream = None
         self.batch_weights = True     # training forward: all ~56 filter transforms / re-layouts of the step in ONE launch (ops.WeightTable)
-        self._wtable = None           # (signature, WeightTable, [(cache key, kind, layer signature fn, buffers)])
-        self._wcache: Dict[str, tuple] = {}
+        self._wcache = _FilterCache()
         self.consumers: Dict[str, int] = {}
         for op in self.ops:
             self.consumers[op["x"]] = self.consumers.get(op["x"], 0) + 1
@@ -284,6 +373,9 @@ class _Engine:
                 rows0=4 * op["a"] if head else co, co=co, co_pad=ops.pad32(co) if head else co, ld16=ops.pad64(co) if head else co,
                 conv=(op["ci"], 3, 1, 1, 1) if head else (op["ci"], op["k"], op["s"], op["pad"], op["dil"]),
                 first_dx=[o for o in self.ops if o["x"] == op["x"]][-1] is op)
+        p = self.ops[0]["p"]          # conv_first has a path of its own; the weight cache sees it as one more layer
+        self._first = _Layer(key=p, x="x", y=self.ops[0]["y"], head=False, relu=True, weights=(p + ".weight",), biases=(p + ".bias",),
+                             rows0=64, co=64, co_pad=64, ld16=64, conv=(3, 3, 1, 1, 1), first_dx=True)
         self.grad_sink = None     # callable(name, gradient): called during backward the moment a parameter's gradient is ready
         self.grad_out = None      # callable(names) -> flat f32 tensor or None: where the gradient of these consecutive parameters is to be written
         self.sink_owns_grads = False   # True (ddp.py): gradients live in the listener's buffer, autograd is handed None for them
@@ -346,27 +438,14 @@ class _Engine:
         return self.batch_weights and not self.x3 and (not self.bf16 or self.bf16_tensors)
 
     # -- weights ----------------------------------------------------------------------------
-    def _layouts(self, L: _Layer, P, need_bwd: bool):
-        """Cached [Co_pad][T][Ci] / [Ci][T][Co_pad] copies, refreshed when a parameter changes."""
-        tensors = L.filter(P)
-        sig = tuple((t.data_ptr(), t._version) for t in tensors)
-        ent = self._wcache.get(L.key)
-        if ent is None or ent[0] != sig:
-            ent = [sig, _stacked(tensors).detach().contiguous(), None, None]
-            ent[2] = ops.weight_ohwi(ent[1], L.co_pad)
-            self._wcache[L.key] = ent
-        if need_bwd and ent[3] is None:
-            ent[3] = ops.weight_ihwo(ent[1], L.co_pad)
-        if self.x3 or (self.bf16 and not self.bf16_tensors):      # pre-split limb planes of the layouts in use
-            if len(ent) == 4:
-                ent += [None, None]
-            if ent[4] is None:
-                ent[4] = ops.weight_split3(ent[2])
-            if need_bwd and ent[5] is None:
-                ent[5] = ops.weight_split3(ent[3])
-            if self.x3:
-                return ent[4], ent[5]
-        return ent[2], ent[3]
+    def _filter(self, what: str, L: _Layer, P, need_bwd: bool = False) -> _Filter:
+        """THE lookup of a layer's re-laid filter in the family `what` (a name of `_FAMILIES`): the cached record while its signature
+        holds (`_FilterCache.sig`), else built for this layer alone.  need_bwd: the caller reads the data gradient's layout."""
+        fam = _FAMILIES[what]
+        rec = self._wcache.lookup(fam, L, P, lambda sig, w: _Filter(sig, *fam.build(self, L, w, fam.adj), oihw=w if fam.lazy else None))
+        if fam.lazy:
+            fam.lazy(self, L, rec, need_bwd)
+        return rec
 
     WINO_TILE = 4                 # forward / dgrad output tile: F(4x4,3x3) (36 multiplies per 16 outputs; ~1e-5 of the output scale) or 2
     WINO_WGRAD_MAX_HW = 512       # Winograd weight gradient on maps up to this size and from this many input channels.  Steps measured in
@@ -389,17 +468,6 @@ class _Engine:
         return (self.wino and not self.bf16 and not self.x3 and ops.wino_x3(4, 256) and g.R == 1 and g.S == 1 and g.stride == 1 and g.pad == 0
                 and g.Ci % 32 == 0 and g.Ci >= 256 and g.Co % 32 == 0 and g.Co >= 128 and g.N * g.H * g.W >= self.X31_MIN_PIXELS)
 
-    def _x31_weights(self, L: _Layer, P):
-        """Cached limb planes of a 1x1 filter and of its transpose, refreshed when the parameter changes."""
-        tensors = L.filter(P)
-        sig = tuple((t.data_ptr(), t._version) for t in tensors)
-        ent = self._wcache.get("x31:" + L.key)
-        if ent is None or ent[0] != sig:
-            wf, wb = ops.conv1x1_weights_x3(_stacked(tensors).detach().contiguous(), L.co_pad)
-            ent = (sig, wf, wb)
-            self._wcache["x31:" + L.key] = ent
-        return ent[1], ent[2]
-
     def _wino_wgrad_ok(self, g, head: bool) -> bool:
         """Weight gradient of this layer in the Winograd domain (else: the fused direct kernels)."""
         return (self._wino_ok(g) and g.H <= self.WINO_WGRAD_MAX_HW and g.Ci >= self.WINO_WGRAD_MIN_CI
@@ -420,28 +488,6 @@ class _Engine:
             return False
         g = ops.make_geom(bs, x.shape[2], x.shape[3], nxt["ci"], nxt["co"], nxt["k"], nxt["s"], nxt["pad"], nxt["dil"])
         return self._wino_ok(g) and g.dil == 1 and g.Co % 4 == 0 and not ops.wino_uses_full(g, 0)
-
-    def _wino_weights(self, L: _Layer, P, adj: bool = False):
-        """Cached Winograd-domain filters (U_fwd [16][Co][Ci], U_bwd [16][Ci][co_pad]), refreshed when a parameter changes.
-        adj: U_bwd in the adjoint form (the forward transform laid out [Ci][co_pad]) instead of the rotated filter's transform."""
-        tensors = L.filter(P)
-        sig = tuple((t.data_ptr(), t._version) for t in tensors) + (ops.wino_x3(4, 256), bool(adj))     # + the GEMM form the filters were laid out for
-        ent = self._wcache.get("wino:" + L.key)
-        if ent is None or ent[0] != sig:
-            w = _stacked(tensors)
-            uf, ub = ops.wino_weights(w.detach().contiguous(), L.co_pad, want_bwd=not adj, mo=self.WINO_TILE)
-            if adj:
-                ub = ops.wino_adj_weights(w.detach().contiguous(), L.co_pad)
-            ent = (sig, uf, ub)
-            self._wcache["wino:" + L.key] = ent
-        return ent[1], ent[2]
-
-    def _planes(self, key: str, bwd: bool):
-        """bf16 mode: the limb planes of a cached layout (plane 0 feeds the halo-tile kernel); None otherwise."""
-        if not self.bf16:
-            return None
-        ent = self._wcache.get(key)
-        return None if ent is None or len(ent) < 6 else ent[5 if bwd else 4]
 
     def _t16(self, g) -> bool:
         """bf16-tensor mode: this convolution, given a bf16 input, runs csrc/conv_bf16.hip (3x3 / stride 1 / pad 1, Ci a multiple of 64)."""
@@ -500,71 +546,29 @@ class _Engine:
             return None if self.WINO_TILE != 4 else "wino_adj" if path.adj else "wino"
         return {"b16": "b16", "x31": "x31", "direct": "layout"}[path.kind]
 
-    def _bf16_weights(self, L: _Layer, P):
-        """bf16 OHWI (co, 9, ci) and IHWO (ci, 9, pad64(co)) copies of a 3x3 filter (+ the bias padded to a multiple of 4), cached."""
-        tensors = L.filter(P)
-        sig = tuple((t.data_ptr(), t._version) for t in tensors)
-        ent = self._wcache.get("b16:" + L.key)
-        if ent is None or ent[0] != sig:
-            w = _stacked(tensors).detach()
-            co, ci = int(w.shape[0]), int(w.shape[1])
-            wf = w.permute(0, 2, 3, 1).reshape(co, 9, ci).contiguous().to(torch.bfloat16)
-            wb = torch.zeros((ci, 9, ops.pad64(co)), device=w.device, dtype=torch.bfloat16)
-            wb[:, :, :co] = w.permute(1, 2, 3, 0).reshape(ci, 9, co)
-            ent = (sig, wf, wb)
-            self._wcache["b16:" + L.key] = ent
-        return ent[1], ent[2]
-
     def _prepare_weights_batched(self, x: torch.Tensor, P: Dict[str, torch.Tensor]) -> None:
         """Fill the weight cache for a training step with one launch.  The output buffers persist across steps (rewritten in place, on the
         caller's stream, after the previous step's last use); the job table is rebuilt only when a parameter's storage or the input
         size changes."""
         sig = (x.shape[2], x.shape[3]) + self.schedule_key() + tuple(P[n].data_ptr() for n in self.names)
-        if self._wtable is None or self._wtable[0] != sig:
+        fill = self._wcache.fill
+        if fill is None or fill.sig != sig:
             jobs, entries = [], []
-            bs, dev = x.shape[0], x.device
-            first = self.ops[0]                    # conv_first: its [64][32] rows
-            w = P[first["p"] + ".weight"]
-            rows = torch.empty((64, 1, 32), device=dev, dtype=torch.float32)
-            jobs.append(dict(kind=2, w0=w.detach(), co0=64, co=64, ci=3, taps=9, co_pad=64, out_fwd=rows))
-            entries.append((first["p"], "first", (w,), (rows,)))
-            for _, L, g, path in self._plan(bs, x.shape[2], x.shape[3]):
-                what = self._table_kind(path)
-                if what is None:
-                    continue
-                tensors, co_pad, taps = L.filter(P), L.co_pad, g.R * g.S
-                co_all = sum(t.shape[0] for t in tensors)
-                job = dict(w0=tensors[0].detach(), w1=tensors[1].detach() if len(tensors) > 1 else None, co0=tensors[0].shape[0], co=co_all,
-                           ci=g.Ci, taps=taps, co_pad=co_pad)
-                if what == "b16":
-                    bufs = (torch.empty((co_all, 9, g.Ci), device=dev, dtype=torch.bfloat16),
-                            torch.empty((g.Ci, 9, ops.pad64(co_all)), device=dev, dtype=torch.bfloat16))
-                    job.update(kind=3, co_pad=co_all, pad1=ops.pad64(co_all))
-                elif what == "x31":
-                    bufs = (ops.x3_filter_alloc(co_all, g.Ci, dev), ops.x3_filter_alloc(g.Ci, co_pad, dev))
-                    job.update(kind=4)
-                elif what == "layout":
-                    bufs = (torch.empty((co_pad, taps, g.Ci), device=dev, dtype=torch.float32),
-                            torch.empty((g.Ci, taps, co_pad), device=dev, dtype=torch.float32))
-                    job.update(kind=1)
-                else:
-                    bufs = (ops.wino_filter_alloc(4, co_all, g.Ci, dev), ops.wino_filter_alloc(4, g.Ci, co_pad, dev))
-                    job.update(kind=0, adj=path.adj)
-                jobs.append(dict(job, out_fwd=bufs[0], out_bwd=bufs[1]))
-                entries.append((L.key, what, tensors, bufs))
-            self._wtable = (sig, ops.WeightTable(jobs, dev), entries)
-        _, table, entries = self._wtable
-        table.run()
-        for key, what, tensors, bufs in entries:
-            lsig = tuple((t.data_ptr(), t._version) for t in tensors)
-            if what == "first":
-                self._wcache[key] = [lsig[0], None, bufs[0], None]
-            elif what == "layout":
-                self._wcache[key] = [lsig, None, bufs[0], bufs[1]]
-            elif what in ("b16", "x31"):
-                self._wcache[what + ":" + key] = (lsig, bufs[0], bufs[1])
-            else:
-                self._wcache["wino:" + key] = (lsig + (ops.wino_x3(4, 256), what == "wino_adj"), bufs[0], bufs[1])
+            layers = [("first", self._first, 3, 9)] + [(self._table_kind(path), L, g.Ci, g.R * g.S)
+                                                       for _, L, g, path in self._plan(x.shape[0], x.shape[2], x.shape[3])]
+            for what, L, ci, taps in (row for row in layers if row[0] is not None):
+                fam, tensors = _FAMILIES[what], L.filter(P)
+                co = sum(t.shape[0] for t in tensors)
+                fwd, bwd = fam.alloc(co, ci, taps, L.co_pad, x.device)
+                jobs.append(dict(dict(kind=fam.job, w0=tensors[0].detach(), w1=tensors[1].detach() if len(tensors) > 1 else None,
+                                      co0=tensors[0].shape[0], co=co, ci=ci, taps=taps, co_pad=L.co_pad, out_fwd=fwd, out_bwd=bwd),
+                                 **fam.job_fields(co, bwd)))
+                entries.append((what, L, fwd, bwd))
+            fill = self._wcache.fill = _TableFill(sig, ops.WeightTable(jobs, x.device), entries)
+        fill.table.run()
+        for what, L, fwd, bwd in fill.entries:            # the records `_filter` would have built
+            fam = _FAMILIES[what]
+            self._wcache[(fam.slot, L.key)] = _Filter(self._wcache.sig(fam, L, P), fwd, bwd)
 
     # -- forward ----------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], save: bool):
@@ -629,36 +633,30 @@ class _Engine:
                 side_ctx[0].__enter__()
             if kind == "conv_first":
                 g = ops.make_geom(bs, x.shape[2], x.shape[3], 32, 64, 1, 1, 0, 1)
-                wkey = P[op["p"] + ".weight"]
-                sig = (wkey.data_ptr(), wkey._version)
-                ent = self._wcache.get(op["p"])
-                if ent is None or ent[0] != sig:
-                    ent = [sig, None, ops.first_weight_rows(wkey), None]
-                    self._wcache[op["p"]] = ent
-                bias = P[op["p"] + ".bias"].detach()
+                rows, bias = self._filter("first", self._first, P).fwd, self._first.bias(P)
                 flops1 = 2.0 * bs * g.Ho * g.Wo * 64 * 27
                 if self.bf16 and self.bf16_tensors:
                     # bf16-tensor mode: operands rounded to bf16 inside the kernel, bf16 NHWC out; the weight gradient reads x itself
                     T[op["y"]] = self._timed("fwd " + op["p"], "conv_first_fwd_kernel", flops1,
-                                             lambda: ops.conv1_first_fwd_bf16(x, ent[2], bias, True))
+                                             lambda: ops.conv1_first_fwd_bf16(x, rows, bias, True))
                     col = None
                 elif (self.first_fused and not self.bf16 and not self.x3 and self._first_wino_ok(op, bs, x)
                       and (not save or (self.relu_bits and self.dual_dy and self.keep_planes))):
                     # ... and, where its only reader is a Winograd layer, straight into that layer's input planes: no activation tensor at all
                     pre = self._timed("fwd " + op["p"], "conv_first_fwd_kernel", flops1,
-                                      lambda: ops.conv1_first_wino_fwd(x, ent[2], bias, want_bits=save and self.relu_bits))
+                                      lambda: ops.conv1_first_wino_fwd(x, rows, bias, want_bits=save and self.relu_bits))
                     T[op["y"]] = _Elided((bs, x.shape[2], x.shape[3], 64))
                     aux["preplanes:" + op["y"]] = pre
                     col = None
                 elif self.first_fused and not self.bf16 and not self.x3:
                     # one kernel from the NCHW batch: halo tile in LDS, K = 27 on the MFMA, bias + ReLU; the weight gradient's rows ride along
                     T[op["y"]], col = self._timed("fwd " + op["p"], "conv_first_fwd_kernel", flops1,
-                                                  lambda: ops.conv1_first_fwd(x, ent[2], bias, True, want_col=False))
+                                                  lambda: ops.conv1_first_fwd(x, rows, bias, True, want_col=False))
                 else:
                     # conv1_1 as im2col (K = 27 -> 32) + the 1x1 MFMA convolution
                     col = ops.im2col_first(x)
                     T[op["y"]] = self._timed("fwd " + op["p"], ops.igemm_tile(g, 0, self.bf16, self.x3) if self.prof is not None else "", flops1,
-                                             lambda: ops.conv2d_fwd(col, ent[2], bias, g, True, bf16=self.bf16))
+                                             lambda: ops.conv2d_fwd(col, rows, bias, g, True, bf16=self.bf16))
                 T["x_col"] = col
                 aux[op["y"]] = g
             elif kind in ("conv", "head"):
@@ -688,7 +686,7 @@ class _Engine:
             if path.cast16:
                 # a head on an f32 tensor outside the bf16 trunk (c_7 on fc7's output): one cast, then the LDS-DMA kernel
                 xin = T[L.x + ":b16"] = ops.cast_bf16(xin)
-            wf16, _ = self._bf16_weights(L, P)
+            wf16 = self._filter("b16", L, P).fwd
             if not L.head:
                 return self._timed(label, "conv3x3_bf16_kernel", ops.conv_flops(g), lambda: ops.conv3x3_bf16(xin, wf16, bias, L.co, L.relu))
             # a head's rows go to the scatter as f32 with its leading dimension
@@ -699,7 +697,7 @@ class _Engine:
             # boundary of the bf16 trunk (pool5 -> fc6): the kernels below take f32 tensors; a copy another reader made is reused
             xin = T[L.x + ":f32"] = T.get(L.x + ":f32") if T.get(L.x + ":f32") is not None else ops.cast_f32(xin)
         if path.kind == "wino":
-            uf, _ = self._wino_weights(L, P, adj=path.adj)
+            uf = self._filter("wino_adj" if path.adj else "wino", L, P).fwd
             pl, keep, wb = path.pool, path.keep, path.bits
             pre = aux.pop("preplanes:" + L.x, None)
             if pre is not None:
@@ -734,12 +732,12 @@ class _Engine:
                 aux["bits:" + L.key] = res[2]
             return res[0] if keep else res
         if path.kind == "x31":
-            w3f, _ = self._x31_weights(L, P)
+            w3f = self._filter("x31", L, P).fwd
             return self._timed(label, "gemm_planes_x3_kernel (1x1)", ops.conv_flops(g), lambda: ops.conv1x1_fwd_x3(xin, w3f, bias, g, L.relu))
-        wf, _ = self._layouts(L, P, False)
+        w = self._filter("layout", L, P)          # (bf16 mode: plane 0 of the limbs feeds the halo-tile kernel)
         return self._timed(label, ops.igemm_tile(g, 0, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
-                           lambda: ops.conv2d_fwd_x3(xin, wf, bias, g, L.relu, ld=L.co_pad) if self.x3 else
-                           ops.conv2d_fwd(xin, wf, bias, g, L.relu, ld=L.co_pad, bf16=self.bf16, w3=self._planes(L.key, False)))
+                           lambda: ops.conv2d_fwd_x3(xin, w.fwd_limbs, bias, g, L.relu, ld=L.co_pad) if self.x3 else
+                           ops.conv2d_fwd(xin, w.fwd, bias, g, L.relu, ld=L.co_pad, bf16=self.bf16, w3=w.fwd_limbs if self.bf16 else None))
 
     def _wgrad_gemm_async(self, main, Y, kept, part, g, ldy, assign):
         """Second half of a Winograd weight gradient on the weight-gradient stream: waits for what `main` has enqueued so far (the dy
@@ -828,7 +826,7 @@ class _Engine:
                 if need_w:
                     L.hand(grads, *self._timed("wgrad " + name, "wgrad3x3_bf16_kernel", ops.conv_flops(g),
                                                lambda: ops.conv3x3_wgrad_bf16t(xin, dy, g, L.ld16, True, **gout())))
-                _, wb16 = self._bf16_weights(L, P)
+                wb16 = self._filter("b16", L, P).bwd
 
                 def dgrad16(dx, acc, mask):
                     if f32_dx and (acc or mask is not None or dx is not None):
@@ -877,7 +875,7 @@ class _Engine:
                 else:
                     Y, _ = dy_planes()
                 del kept
-                _, uadj = self._wino_weights(L, P, adj=True)
+                uadj = self._filter("wino_adj", L, P).bwd
                 bits = aux.pop("bits:" + name, None)
                 below = self._conv_of.get(L.x) if self.adjoint_chain else None
                 gb = aux.get(L.x) if below is not None else None
@@ -928,7 +926,7 @@ class _Engine:
                 if path.adj:
                     raise RuntimeError(f"{name}: its filter planes are laid out for the adjoint data gradient, which needs the forward's kept planes "
                                        "(the engine's keep_planes / dual_dy / adjoint_dgrad switches must not change between a forward and its backward)")
-                _, ub = self._wino_weights(L, P)
+                ub = self._filter("wino", L, P).bwd
                 bits = aux.pop("bits:" + name, None) if (dyp is not None or full or isinstance(T[L.x], _Elided)) else None
 
                 def dgrad_rot(dx, acc, mask):
@@ -944,25 +942,26 @@ class _Engine:
                                                                lambda: dgrad_rot(dx, acc, mask)))
                 return
             if path.kind == "x31" and not to_bf16:
-                _, w3b = self._x31_weights(L, P)
+                w3b = self._filter("x31", L, P).bwd
                 deliver(L.x, lambda dx, acc, mask: self._timed(
                     "dgrad " + name, "gemm_planes_x3_kernel (1x1)", ops.conv_flops(g),
                     lambda: ops.conv1x1_dgrad_x3(dy, w3b, g, dx, mask, acc)))
                 return
-            _, wb = self._layouts(L, P, True)
+            w = self._filter("layout", L, P, need_bwd=True)
+            w3 = w.bwd_limbs if self.bf16 else None
             if to_bf16:
                 def boundary(dx, acc, mask):
                     if acc or mask is not None or dx is not None:
                         raise RuntimeError("the bf16 trunk's boundary tensor must have one consumer and no ReLU of its own")
                     d32 = self._timed("dgrad " + name, ops.igemm_tile(g, 1, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
-                                      lambda: ops.conv2d_dgrad(dy, wb, g, None, None, False, bf16=self.bf16, w3=self._planes(name, True)))
+                                      lambda: ops.conv2d_dgrad(dy, w.bwd, g, None, None, False, bf16=self.bf16, w3=w3))
                     return ops.cast_bf16(d32)
                 deliver(L.x, boundary)
                 return
             deliver(L.x, lambda dx, acc, mask: self._timed(
                 "dgrad " + name, ops.igemm_tile(g, 1, self.bf16, self.x3) if self.prof is not None else "", ops.conv_flops(g),
-                lambda: ops.conv2d_dgrad_x3(dy, wb, g, dx, mask, acc) if self.x3 else
-                ops.conv2d_dgrad(dy, wb, g, dx, mask, acc, bf16=self.bf16, w3=self._planes(name, True))))
+                lambda: ops.conv2d_dgrad_x3(dy, w.bwd_limbs, g, dx, mask, acc) if self.x3 else
+                ops.conv2d_dgrad(dy, w.bwd, g, dx, mask, acc, bf16=self.bf16, w3=w3)))
 
         for op in reversed(self.ops):
             kind = op["op"]
@@ -1232,7 +1231,7 @@ class GraphedForward:
         s = self._stream
         # The copy's layouts go into a cache of their own, never into the engine's: entries keyed on (data_ptr, _version) of the
         # copy would outlive it there, and a later copy allocated at the same addresses (version 0 again) would hit them.
-        shared, eng._wcache = eng._wcache, {}
+        shared, eng._wcache = eng._wcache, _FilterCache()
         try:
             s.wait_stream(torch.cuda.current_stream(self.x.device))
             with torch.no_grad(), torch.cuda.stream(s):       # warm-up: weight layouts, workspaces, allocator pools
@@ -1242,7 +1241,7 @@ class GraphedForward:
             self.graph = torch.cuda.CUDAGraph()
             with ops.capture_workspaces() as ws, torch.no_grad(), torch.cuda.graph(self.graph, stream=s):
                 self.loc, self.conf, _ = eng.forward(self.x, P, save=False)
-            layouts = [t for ent in eng._wcache.values() for t in ent if torch.is_tensor(t)]
+            layouts = eng._wcache.tensors()
         finally:
             eng._wcache = shared
         self._held = (P, ws, layouts)          # what the replay reads besides its own pool: the parameter copy, its layouts, the workspaces

@@ -642,8 +642,8 @@ class GraphedTrainStep:
             with ops.capture_workspaces() as ws, torch.no_grad(), torch.cuda.graph(g, stream=s):
                 self.losses, self.obj, self.cls = self._body(with_sgd=single)
             self.graph = g
-            table = eng._wtable if eng.uses_weight_table() else None          # (otherwise a table of an earlier setting, not read)
-            self._held = (ws, table, [t for ent in eng._wcache.values() for t in ent if torch.is_tensor(t)])
+            table = eng._wcache.fill if eng.uses_weight_table() else None     # (otherwise a table of an earlier setting, not read)
+            self._held = (ws, table, eng._wcache.tensors())
             self.kernel_nodes = _graph_kernel_nodes(g)
             if single:
                 tr.steps -= 1                                 # apply_sgd's bookkeeping ran once during capture without a step being executed

@@ -113,11 +113,17 @@ def wino_flops(g: ConvGeom):
 
 
 # ---- weights ---------------------------------------------------------------------------
+def layout_filter_alloc(ci: int, taps: int, co_pad: int, device, bwd: bool = False) -> torch.Tensor:
+    """Destination of a filter in the direct kernels' layout: OHWI (co_pad, taps, ci) or, bwd, IHWO (ci, taps, co_pad), f32.  The
+    transforms write every element, the rows past the filter's own as zeros."""
+    return torch.empty((ci, taps, co_pad) if bwd else (co_pad, taps, ci), device=device, dtype=torch.float32)
+
+
 def weight_ohwi(w_oihw: torch.Tensor, co_pad: Optional[int] = None) -> torch.Tensor:
     _req(w_oihw, "weight")
     co, ci, r, s = w_oihw.shape
     co_pad = co if co_pad is None else co_pad
-    out = torch.empty((co_pad, r * s, ci), device=w_oihw.device, dtype=torch.float32)
+    out = layout_filter_alloc(ci, r * s, co_pad, w_oihw.device)
     check(_lib.load().ssd_weight_oihw_to_ohwi(w_oihw.data_ptr(), out.data_ptr(), co, ci, r, s, co_pad, _stream()), "weight_ohwi")
     return out
 
@@ -126,7 +132,7 @@ def weight_ihwo(w_oihw: torch.Tensor, co_pad: Optional[int] = None) -> torch.Ten
     _req(w_oihw, "weight")
     co, ci, r, s = w_oihw.shape
     co_pad = pad32(co) if co_pad is None else co_pad
-    out = torch.empty((ci, r * s, co_pad), device=w_oihw.device, dtype=torch.float32)
+    out = layout_filter_alloc(ci, r * s, co_pad, w_oihw.device, bwd=True)
     check(_lib.load().ssd_weight_oihw_to_ihwo(w_oihw.data_ptr(), out.data_ptr(), co, ci, r, s, co_pad, _stream()), "weight_ihwo")
     return out
 
@@ -309,6 +315,22 @@ def conv3x3_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
 
 def pad64(c: int) -> int:
     return (c + 63) // 64 * 64
+
+
+def bf16_filter_alloc(co: int, ci: int, device, bwd: bool = False) -> torch.Tensor:
+    """Destination of a 3x3 filter for csrc/conv_bf16.hip: OHWI (co, 9, ci) or, bwd, IHWO (ci, 9, pad64(co)) zero-filled, bf16."""
+    if bwd:
+        return torch.zeros((ci, 9, pad64(co)), device=device, dtype=torch.bfloat16)
+    return torch.empty((co, 9, ci), device=device, dtype=torch.bfloat16)
+
+
+def weights_bf16(w_oihw: torch.Tensor):
+    """(Co,Ci,3,3) f32 -> the bf16 OHWI and IHWO copies of `bf16_filter_alloc` (per-layer form of the kind-3 weight job)."""
+    co, ci = int(w_oihw.shape[0]), int(w_oihw.shape[1])
+    wf, wb = bf16_filter_alloc(co, ci, w_oihw.device), bf16_filter_alloc(co, ci, w_oihw.device, bwd=True)
+    wf.copy_(w_oihw.permute(0, 2, 3, 1).reshape(co, 9, ci))
+    wb[:, :, :co] = w_oihw.permute(1, 2, 3, 0).reshape(ci, 9, co)
+    return wf, wb
 
 
 def cast_bf16(x: torch.Tensor) -> torch.Tensor:
@@ -665,11 +687,17 @@ def dropout_mask(n: int, p: float, seed: int, site: int, device) -> torch.Tensor
     return out.bool()
 
 
+def first_rows_alloc(co: int, device) -> torch.Tensor:
+    """Destination of conv1_1's filter rows: (co, 1, 32) f32, zero-filled (27 taps, padded to the GEMM's K = 32)."""
+    return torch.zeros((co, 1, 32), device=device, dtype=torch.float32)
+
+
 def first_weight_rows(w_oihw: torch.Tensor) -> torch.Tensor:
     """(Co,3,3,3) OIHW -> (Co,1,32): rows ordered like im2col_first's columns, zero padded."""
     co = w_oihw.shape[0]
-    rows = w_oihw.detach().permute(0, 2, 3, 1).reshape(co, 27)              # [co][(r,s),c]
-    return torch.nn.functional.pad(rows, (0, 5)).reshape(co, 1, 32).contiguous()
+    out = first_rows_alloc(co, w_oihw.device)
+    out.view(co, 32)[:, :27] = w_oihw.detach().permute(0, 2, 3, 1).reshape(co, 27)      # [co][(r,s),c]
+    return out
 
 
 def first_weight_grad(dw_rows: torch.Tensor) -> torch.Tensor:

@@ -344,12 +344,12 @@ def f64_rounding_pinned_grads(params, decisions, neg_select, pinned, case=None, 
 
 def bf16_tensor_heads(net):
     """the heads the engine's last training forward ran on the bf16-tensor kernels (weight-table entries `b16`)"""
-    return {p for p, kind, _, _ in net._engine._wtable[2] if kind == "b16" and p.startswith("c_")}
+    return {p for p, kind in net._engine._wcache.kinds().items() if kind == "b16" and p.startswith("c_")}
 
 
 def weight_kinds(net):
     """{layer: x31 | wino_adj | wino | layout | b16 | first} of the engine's last training forward (its weight table)"""
-    return {p: kind for p, kind, _, _ in net._engine._wtable[2]}
+    return net._engine._wcache.kinds()
 
 
 def oracle_self_decisions(params, x, boxes, classes, variant=300, bf16=False):

@@ -1210,6 +1210,49 @@ def test_forward_records_the_path_the_weight_table_planned(golden_net, conv_dtyp
     assert {path.kind for _, _, _, path in plan} == ({"wino", "direct"} if conv_dtype == "f32" else {"b16", "direct"})
 
 
+@pytest.mark.parametrize("conv_dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("variant,bs", [(300, 32), (512, 2)])       # batch 32: fc7 and seq8.0 are `x31` layers in the f32 mode
+def test_weight_table_and_per_layer_lookup_fill_the_cache_alike(variant, bs, conv_dtype):
+    """The engine's two ways of filling its filter cache, from the same random filters and without a forward pass: one launch of the
+    batched weight table (`_prepare_weights_batched`, what a training forward does) against the per-layer builders behind the lookup
+    (`_filter`, what an eval forward does).  Same keys, same shapes and dtypes, and every forward and backward layout equal bit for
+    bit, padding included: each side either allocates it as zeros or writes zeros there (`ssd_weights_prepare` writes the rows
+    past a filter's own in kinds 1 and 3 and the columns past co in kind 0; limb-plane buffers are zero-filled by their allocators
+    on both sides).  A per-layer `layout` record also keeps its OIHW source, which a table record has no use for; neither side has
+    limb planes of a `layout` record in these modes."""
+    from objectdetection_ssd_amd import Model
+    eng = Model._Engine(variant)
+    eng.bf16 = conv_dtype == "bf16"
+    gen = torch.Generator(device=DEV).manual_seed(variant + bs)
+    P = {n: torch.zeros(1, device=DEV) for n in eng.names}          # biases and the L2-norm scale: only their addresses are read
+    plan = [(eng._first, "first")] + [(L, eng._table_kind(path)) for _, L, _, path in eng._plan(bs, variant, variant)]
+    for L, _ in plan:
+        ci, k = L.conv[0], L.conv[1]
+        for n, rows in zip(L.weights, (L.rows0, L.co - L.rows0)):
+            P[n] = torch.randn((rows, ci, k, k), device=DEV, generator=gen) * 0.05
+    x = torch.zeros(1, 3, variant, variant, device=DEV).expand(bs, 3, variant, variant)
+    eng._prepare_weights_batched(x, P)
+    by_table, eng._wcache = eng._wcache, Model._FilterCache()
+    for L, what in plan:
+        eng._filter(what, L, P, need_bwd=True)
+    torch.cuda.synchronize()
+    assert list(by_table) == list(eng._wcache) and len(by_table) == len(plan)
+    want = {"first", "wino", "layout"} | ({"x31"} if bs == 32 else set()) if conv_dtype == "f32" else {"first", "b16", "layout"}
+    assert {slot for slot, _ in by_table} == want
+
+    def bits(t):
+        return t.view(torch.int16) if t.dtype == torch.bfloat16 else t
+    for at, a in by_table.items():
+        b = eng._wcache[at]
+        assert a.sig == b.sig, at
+        for ta, tb in ((a.fwd, b.fwd), (a.bwd, b.bwd)):
+            assert (ta is None) == (tb is None), at
+            if ta is not None:
+                assert ta.shape == tb.shape and ta.dtype == tb.dtype and torch.equal(bits(ta), bits(tb)), at
+        assert a.fwd_limbs is b.fwd_limbs is a.bwd_limbs is b.bwd_limbs is a.oihw is None, at
+        assert (b.oihw is not None) == (at[0] == "layout"), at
+
+
 def test_ops_refuse_tensors_of_another_device_than_the_current_one():
     from objectdetection_ssd_amd import ops
     if torch.cuda.device_count() < 2:

@@ -113,8 +113,8 @@ def test_graphed_train_step_survives_eager_work_on_its_own_net(conv_dtype, two_s
     streams = [gstep._stream] + ([eng._side_stream, eng._wgrad_stream] if two_streams else [])
     ws = _ws_refs(streams)
     assert ws, "no workspace cached for the capture's streams"
-    table = weakref.ref(eng._wtable[1])
-    kept = [weakref.ref(t) for t in eng._wtable[1].keep]
+    table = weakref.ref(eng._wcache.fill.table)
+    kept = [weakref.ref(t) for t in eng._wcache.fill.table.keep]
 
     with torch.no_grad():                                      # 1: eval forward at the larger batch
         nets[1](_batch(50, BIG)[0])
@@ -127,7 +127,7 @@ def test_graphed_train_step_survives_eager_work_on_its_own_net(conv_dtype, two_s
 
     if two_streams:
         assert _replaced(ws), "no side-stream workspace was regrown: the test no longer exercises the hazard"
-    assert eng._wtable[1] is not table(), "the weight table was not replaced: the test no longer exercises the hazard"
+    assert eng._wcache.fill.table is not table(), "the weight table was not replaced: the test no longer exercises the hazard"
     gc.collect()
     dead = [k for k, r in ws.items() if r() is None]
     assert not dead, f"workspaces the graph replays with were freed: {dead}"
