@@ -71,6 +71,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=20)        # train.py:29
     ap.add_argument("--fused-sgd", action="store_true", help="objectdetection_ssd_amd.optim.SGD in place of torch.optim.SGD (same results)")
+    ap.add_argument("--optimizer", choices=("sgd", "adamw"), default="sgd",
+                    help="adamw: objectdetection_ssd_amd.optim.AdamW (weight decay 1e-2) on the same flat buffers and device words as the "
+                         "fused SGD step; takes --grad-clip, --schedule and --ema-decay as SGD does")
     ap.add_argument("--grad-clip", type=float, default=None, metavar="FLOAT",
                     help="clip the global gradient 2-norm to FLOAT inside the fused optimizer step and skip non-finite steps (implies "
                          "--fused-sgd; what torch.nn.utils.clip_grad_norm_ before optimizer.step() does, without leaving the device)")
@@ -108,8 +111,12 @@ def main():
         from objectdetection_ssd_amd.optim import SGD
     else:
         SGD = torch.optim.SGD
-    optimizer = SGD(params=[{"params": biases, "lr": 2 * lr}, {"params": not_biases}], lr=lr, momentum=0.9,
-                    weight_decay=5e-4, **opt_kw)              # train.py:53-55
+    groups = [{"params": biases, "lr": 2 * lr}, {"params": not_biases}]
+    if a.optimizer == "adamw":
+        from objectdetection_ssd_amd.optim import AdamW
+        optimizer = AdamW(params=groups, lr=lr, weight_decay=1e-2, **opt_kw)
+    else:
+        optimizer = SGD(params=groups, lr=lr, momentum=0.9, weight_decay=5e-4, **opt_kw)      # train.py:53-55
     cnn.train()
     t0 = time.time()
     feed = batches(a.steps, a.batch, device) if a.decode is None else jpeg_batches(a.steps, a.batch, a.decode)

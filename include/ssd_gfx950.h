@@ -782,6 +782,43 @@ int ssd_sgd_momentum_sched(float* param, const float* grad, float* momentum_buf,
                            const int* skip_dev, void* stream);
 int ssd_swap_f32(float* a, float* b, size_t n, void* stream);
 
+/* ---- fused Adam / AdamW step on the same flat ranges and the same device words (learning rate, EMA weight, clip scale, skip flag) as
+ * ssd_sgd_momentum_sched.  Compiled without floating-point contraction; every fused multiply-add below is an explicit one.
+ *
+ * Adam state: a block of its own (the schedule block above is unchanged) of three 8-byte words, 8-byte aligned, that the caller
+ * initialises once to {1.0, 1.0, 0}:
+ *   state[0] pow1 (f64): beta1^t as a running product;   state[1] pow2 (f64): beta2^t as a running product;
+ *   state[2] low 4 bytes step (int32): Adam steps actually taken, t; high 4 bytes spare (zero).
+ *
+ * ssd_adam_advance: one workgroup.  *skip_dev != 0 (skip_dev may be NULL): writes nothing.  Otherwise step = t + 1, pow1 = pow1 * beta1,
+ * pow2 = pow2 * beta2: one IEEE f64 multiply each per step, so the block after t steps is what t multiplications starting from 1.0 give
+ * on any IEEE machine -- no pow() is involved, and a checkpointed counter restores the block bit for bit.
+ *
+ * ssd_adam_step, per element of n-element ranges, all f32, after ssd_adam_advance has run for this step (fma = one rounding):
+ *   rate = lr_dev ? (double)*lr_dev : lr                                           (f64)
+ *   g  = grad * *grad_scale_dev                                                    (only when grad_scale_dev is given)
+ *   decoupled == 0 (Adam, L2):   g = fma(wd, p, g)                                 (weight_decay != 0; wd = (float)weight_decay)
+ *   decoupled != 0 (AdamW):      p = p * (float)(1 - rate * weight_decay)          (weight_decay != 0; the factor formed in f64)
+ *   m  = fma((float)(1 - beta1), g - m, m)
+ *   v  = fma((float)(1 - beta2) * g, g, v * (float)beta2)
+ *   den = sqrt(v) / (float)sqrt(1 - pow2) + (float)eps
+ *   p  = p + ((float)(-(rate / (1 - pow1))) * m) / den
+ * 1 - beta, the bias corrections, the division and the square root of the step size are f64 and rounded to f32 once each (one
+ * division and one square root per thread, none per element); sqrt and / per element are correctly rounded f32.  That is
+ * torch.optim.Adam / AdamW (foreach=False) with bit-equal exp_avg and exp_avg_sq; how far p is from torch's after one step is recorded
+ * in tests/golden/adam_ref_distance.json.  ema != NULL: then the three operations of ssd_sgd_momentum_sched on the new p.
+ * *skip_dev != 0: nothing at all is written.  Vector / scalar choice and grid as ssd_sgd_momentum_sched; gradient, moments and EMA
+ * move through non-temporal 16-byte accesses, the parameters through plain ones.
+ *
+ * Both only enqueue on `stream` (graph-capturable).  Refusals, in this order: SSD_ERR_NULL for a missing state, param, grad, exp_avg or
+ * exp_avg_sq and for ema given without ema_w_dev; SSD_ERR_BAD_SHAPE for a beta outside [0, 1), a negative (or NaN) eps or weight_decay,
+ * and a negative lr when lr_dev is NULL; SSD_ERR_ALIGN for a state that is not 8-byte aligned or any other pointer that is not 4-byte
+ * aligned; then n == 0 is SSD_OK. */
+int ssd_adam_advance(void* state, double beta1, double beta2, const int* skip_dev, void* stream);
+int ssd_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, size_t n, double lr, const float* lr_dev,
+                  const float* ema_w_dev, const void* state, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                  const float* grad_scale_dev, const int* skip_dev, void* stream);
+
 /* ---- BatchNorm2d in training mode, Dropout / Dropout2d (SSD_resnet34 train mode: Model.py:24,56-70,72-126 and
  * torchvision's BasicBlock).  Tensors are [M][ld] f32 rows whose first C columns are the channels (M = N*H*W), C % 4 == 0,
  * ld % 4 == 0, rows 16-byte aligned.  Reductions use fixed-order slab partials (no atomics): results are bitwise reproducible.

@@ -220,6 +220,8 @@ SIGNATURES = {
     "ssd_sgd_schedule_advance": (_I, [_P, _P, _I, _I, C.c_double, _I, _P, _P]),
     "ssd_sgd_momentum_sched": (_I, [_P, _P, _P, _P, _Z, _P, _P, _F, _F, _P, _I, _P, _P]),
     "ssd_swap_f32": (_I, [_P, _P, _Z, _P]),
+    "ssd_adam_advance": (_I, [_P, C.c_double, C.c_double, _P, _P]),
+    "ssd_adam_step": (_I, [_P, _P, _P, _P, _P, _Z, C.c_double, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P]),
     "ssd_bn_workspace": (_Z, [_Z, _I]),
     "ssd_bn_train_stats": (_I, [_P, _I, _Z, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_bn_apply": (_I, [_P, _I, _Z, _I, _P, _P, _P, _I, _P, _P, _I, _I, _F, _U64, _I, _I, _P, _I, _P]),

@@ -16,7 +16,8 @@ decay applies to both groups, as torch.optim.SGD does there).
 The flat buffers are one `optim.FlatStore` over weights-then-biases whose gradient buffer
 carries the count slot as a tail; the order inside a step (clip norm, finalise, schedule
 advance) and the choice of the SGD wrapper are `optim.FusedStepMixin._step_controls` and
-`optim.launch_sgd`, shared with `optim.SGD`.
+`optim.launch_sgd`, shared with `optim.SGD`.  `optimizer="adam" | "adamw"` runs `optim.Adam`'s update rule over the same two
+segments instead (`_apply_adam`, `optim.AdamStateMixin`); the class keeps its name.
 """
 from __future__ import annotations
 
@@ -28,10 +29,10 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .optim import FlatLayout, FlatStore, FusedStepMixin, launch_sgd
+from .optim import AdamStateMixin, FlatLayout, FlatStore, FusedStepMixin, check_adam_settings, launch_sgd
 
 
-class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
+class FlatSGDDataParallel(AdamStateMixin, FusedStepMixin, torch.optim.Optimizer):
     """The data-parallel optimizer of the step.  It IS a `torch.optim.Optimizer` with the two parameter groups of reference
     train.py:53-55 in the same order (`param_groups[0]` = biases at 2x lr, `param_groups[1]` = the rest), so the caller's
     `StepLR(optimizer, ...)` (train.py:57), `for g in optimizer.param_groups: g['lr'] = lr` (train_function.py:29-30),
@@ -43,7 +44,7 @@ class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
                  bias_lr_mult: float = 2.0, process_group=None, overlap: Optional[bool] = None, bucket_bytes: int = 16 << 20,
                  grad_dtype: torch.dtype = torch.float32, time_exchange: bool = False,
                  max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False, schedule=None, ema_decay=None,
-                 ema_warmup: bool = True):
+                 ema_warmup: bool = True, *, optimizer: str = "sgd", betas=(0.9, 0.999), eps: float = 1e-8):
         """overlap: start the all-reduce of a slice of the flat gradient buffer as soon as the backward has produced all of it
         (asynchronous collectives on the process group's stream, `bucket_bytes` per slice), instead of one all-reduce after the
         backward.  Same sums, same result (bitwise: tests/test_ddp_gloo.py at world 2 / 4 / 8).  None (default) = overlapped whenever
@@ -69,7 +70,17 @@ class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
         counter, and an exponential moving average of the weights (`flat_ema`, the layout of `flat_param`) updated inside the two SGD
         launches; one more single-workgroup launch per step (`optim.SchedEmaMixin`).  The groups' 'lr' stay the base rates.  Every rank
         holds the same schedule state: the skip word that gates it is computed behind the all-reduce.  `current_lr`, `step_count` and
-        `ema_weight` are device views; `ema_parameters()` / `ema_weights()` reach the average."""
+        `ema_weight` are device views; `ema_parameters()` / `ema_weights()` reach the average.
+
+        optimizer = "sgd" (default: every launch, argument and bit as described above) | "adam" | "adamw", with `betas` and `eps`:
+        the update rule of `optim.Adam` / `optim.AdamW` over the same two segments -- one single-workgroup launch that advances the
+        Adam state block (ONE step counter and pair of running products for the whole optimizer, `optim.AdamStateMixin`) and two
+        Adam launches; `momentum` is then not used.  The first moments live in `flat_mom`, the second in `flat_sq`; the groups have
+        torch.optim.AdamW's keys and `state[p]` its `step` / `exp_avg` / `exp_avg_sq` entries."""
+        if optimizer not in ("sgd", "adam", "adamw"):
+            raise ValueError(f"optimizer must be 'sgd', 'adam' or 'adamw', got {optimizer!r}")
+        self.optimizer_kind = optimizer
+        self._init_adam()
         self._init_clip(max_grad_norm, norm_type, skip_nonfinite)
         self._init_sched(schedule, ema_decay, ema_warmup)
         self.model = model
@@ -89,17 +100,25 @@ class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
         self.names = self.w_names + self.b_names
         self.params: List[torch.nn.Parameter] = [named[n] for n in self.names]
         n_wn = len(self.w_names)
-        super().__init__([{"params": self.params[n_wn:], "lr": lr * bias_lr_mult}, {"params": self.params[:n_wn]}],
-                         dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False))
+        if optimizer == "sgd":
+            defaults = dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False)
+        else:
+            check_adam_settings("FlatSGDDataParallel", lr, betas, eps, weight_decay, False, False, False)
+            defaults = dict(lr=lr, betas=(betas[0], betas[1]), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                            foreach=None, capturable=False, differentiable=False, fused=None,
+                            decoupled_weight_decay=optimizer == "adamw")
+        super().__init__([{"params": self.params[n_wn:], "lr": lr * bias_lr_mult}, {"params": self.params[:n_wn]}], defaults)
         dev = self.params[0].device      # flat buffers live where the model lives (the SGD kernel itself is GPU-only)
         layout = FlatLayout(self.params)
         self._sizes, self._slots, self._offs = layout.sizes, layout.slots, layout.offsets
         self.n_w = layout.offsets[n_wn]
         self.n = layout.total
         # one store over weights-then-biases; the parameters now live in `flat_param`, and `flat_grad` is [grads | n_pos | pad]
-        self._store = store = FlatStore(self.params, layout, tail=1 + (-(self.n + 1)) % 64)
-        self.flat_param, self.flat_grad, self.flat_mom = store.param, store.grad, store.mom
-        self.grad_views, self.mom_views = store.grad_views, store.mom_views
+        adam = optimizer != "sgd"
+        self._store = store = FlatStore(self.params, layout, tail=1 + (-(self.n + 1)) % 64,
+                                        mom_key="exp_avg" if adam else "momentum_buffer", sq_key="exp_avg_sq" if adam else None)
+        self.flat_param, self.flat_grad, self.flat_mom, self.flat_sq = store.param, store.grad, store.mom, store.sq
+        self.grad_views, self.mom_views, self.sq_views = store.grad_views, store.mom_views, store.sq_views
         self.inv_npos = torch.ones(1, device=dev, dtype=torch.float32)
         self._has_momentum = False       # False: the next step starts the momentum buffer from the gradient, as torch.optim.SGD does
         self.steps = 0
@@ -128,6 +147,7 @@ class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
         self._finalizer = weakref.finalize(self, FlatSGDDataParallel._detach, eng_ref, self._token)
         self.flat_grad16 = (torch.zeros(self.n_w, device=dev, dtype=torch.bfloat16) if grad_dtype == torch.bfloat16 else None)
         self._clip_prepare()
+        self._adam_prepare()
         if self._sched_on():
             self._sched_buffers(dev)     # (the EMA waits for the first step: the parameters may still be broadcast or loaded)
         # -- overlapped exchange: contiguous slices of the weight segment, filled from the back of the network first ------------
@@ -216,8 +236,16 @@ class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
         Accepts this optimizer's own state dicts and those of a train.py-style optimizer over the same model (re-indexed by
         parameter name: `_from_reference_layout`)."""
         state_dict = self._from_reference_layout(state_dict)
+        adam = self.optimizer_kind != "sgd"
+        if adam:
+            steps = {float(st["step"]) for st in state_dict["state"].values() if "step" in st}
+            if len(steps) > 1 or any(t != int(t) or t < 0 for t in steps):
+                raise ValueError(f"FlatSGDDataParallel.load_state_dict: the parameters' step counts {sorted(steps)} disagree or are no "
+                                 "counts; the Adam step counter here is one per optimizer")
         super().load_state_dict(state_dict)
-        mom = [self.state.get(p, {}).get("momentum_buffer") is not None for p in self.params]
+        key = self._store.mom_key
+        mom = [self.state.get(p, {}).get(key) is not None and (not adam or self.state[p].get("exp_avg_sq") is not None)
+               for p in self.params]
         if any(mom) and not all(mom):
             raise ValueError("FlatSGDDataParallel.load_state_dict: momentum buffers for only some of the parameters")
         ema = [self.state.get(p, {}).get("ema") is not None for p in self.params]
@@ -227,6 +255,10 @@ class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
         if not self._has_momentum:
             with torch.no_grad():
                 self.flat_mom.zero_()
+                if adam:
+                    self.flat_sq.zero_()
+        if adam:
+            self._adam_restore(int(steps.pop()) if steps and self._has_momentum else 0, *self._adam_betas(self.param_groups))
         self._store.adopt(self.state)        # (an EMA the restored state has no averages for stays: its views are attached again)
         self.steps = int(state_dict.get("flat_steps", self.steps)) if isinstance(state_dict, dict) else self.steps
         self._sched_unstamp()
@@ -234,6 +266,10 @@ class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
     def state_dict(self):
         """torch's layout plus `flat_steps`; with the schedule or the EMA on, every group also carries `sched_step`, the device step
         counter (reading it is the one synchronisation), and `state[p]['ema']` travels with the momentum buffers."""
+        if self.optimizer_kind != "sgd" and self._has_momentum:
+            t = self._adam_step_host()             # torch's per-parameter `step`, here the optimizer's one counter
+            for p in self.params:
+                self.state[p]["step"] = torch.tensor(float(t), dtype=torch.float32)
         sd = super().state_dict()
         sd["flat_steps"] = self.steps
         return self._sched_stamp(sd)
@@ -433,7 +469,42 @@ class FlatSGDDataParallel(FusedStepMixin, torch.optim.Optimizer):
             self._store.start_ema(self.state)
         return True
 
+    def _adam_prepare(self) -> bool:
+        """An Adam trainer: make sure the Adam state block exists (outside any graph capture) -> True."""
+        if self.optimizer_kind == "sgd":
+            return False
+        self._adam_buffers(self.flat_param.device)
+        return True
+
+    def _apply_adam(self) -> None:
+        """`apply_sgd` of an Adam trainer: the shared controls, the Adam advance (held by the skip word only under the guard, like
+        the schedule advance), then the weight and the bias segment."""
+        gb, gw = self.param_groups
+        for g in (gb, gw):
+            check_adam_settings("FlatSGDDataParallel", g["lr"], g["betas"], g["eps"], g["weight_decay"], g.get("amsgrad", False),
+                                g.get("maximize", False), g.get("differentiable", False))
+        beta1, beta2 = self._adam_betas(self.param_groups)
+        self._clip_prepare()
+        self._adam_prepare()
+        sched = self._sched_prepare()
+        scale, skip, lr_words, ema_w = self._step_controls([self.flat_grad[:self.n]], self.inv_npos)
+        ops.adam_advance_(self._adam_state, beta1, beta2, skip if self.skip_nonfinite else None)
+        ema = self.flat_ema if self.ema_decay is not None else None
+        for gi, g, seg in ((1, gw, slice(0, self.n_w)), (0, gb, slice(self.n_w, self.n))):       # weights, then biases
+            ops.adam_step_(self.flat_param[seg], self.flat_grad[seg], self.flat_mom[seg], self.flat_sq[seg],
+                           None if ema is None else ema[seg], float(g["lr"]), lr_words[gi:gi + 1] if sched else None, ema_w,
+                           self._adam_state, beta1, beta2, float(g["eps"]), float(g["weight_decay"]),
+                           bool(g.get("decoupled_weight_decay", False)), scale, skip)
+        if not self._has_momentum:
+            for p, mv, sv in zip(self.params, self.mom_views, self.sq_views):
+                self.state[p].update(step=torch.tensor(0.0, dtype=torch.float32), exp_avg=mv, exp_avg_sq=sv)
+            self._has_momentum = True    # (here: torch.optim.AdamW's state entries are attached; `state_dict()` fills `step`)
+        self.steps += 1
+        self.model._engine._wcache.clear()
+
     def apply_sgd(self) -> None:
+        if self.optimizer_kind != "sgd":
+            return self._apply_adam()
         first = not self._has_momentum
         gb, gw = self.param_groups
         for g in (gb, gw):
@@ -494,7 +565,8 @@ class GraphedTrainStep:
     The first `warmup` calls run the step eagerly (they are ordinary training steps: allocator pools, workspaces, weight tables and the
     momentum buffers come into being), the next call captures and replays; while a group has a nonzero momentum whose buffer does not
     exist yet the step stays eager (the first SGD step starts the buffer from the gradient, a different launch), with momentum 0 the
-    capture follows the warm-up.  With more than one rank the gradient exchange is ONE f32 all-reduce issued after the graph (a
+    capture follows the warm-up, and so it does for an Adam trainer (`optimizer="adam" | "adamw"`: zero moments are Adam's own start, the
+    Adam advance and the two Adam launches are nodes of the graph at one rank).  With more than one rank the gradient exchange is ONE f32 all-reduce issued after the graph (a
     collective started from inside the backward cannot be part of a replay), followed by the two SGD launches;
     `FlatSGDDataParallel(overlap=...)` is switched off for the life of this object, and a trainer built with `grad_dtype=torch.bfloat16`
     is refused at more than one rank (`ValueError`) rather than sending f32.
@@ -503,7 +575,7 @@ class GraphedTrainStep:
     `apply_sgd` and so part of the captured step at one rank: a skipped replayed step leaves parameters and momentum untouched and
     bumps `trainer.skipped_steps` with no host involvement.  With more ranks they run eagerly behind the all-reduce, as the SGD does.
 
-    What forces a re-capture: a change of lr / momentum / weight decay of either group (StepLR), of the trainer's clip settings, of its
+    What forces a re-capture: a change of lr / momentum / weight decay / betas / eps of either group (StepLR), of the optimizer kind, of the trainer's clip settings, of its
     schedule object or EMA settings, of the world size, of the engine's
     stream placement (`overlap_tail`, `defer_tail_wgrad`), or of any engine setting in `_Engine.schedule_key()` (dtype mode, Winograd
     and its thresholds, the fused and adjoint forms).  Under an `optim.LRSchedule` the groups' lr are the BASE rates, which no longer
@@ -605,8 +677,8 @@ class GraphedTrainStep:
     def _signature(self):
         tr = self.trainer
         eng = self.net._engine
-        return tuple((g["lr"], g["momentum"], g["weight_decay"]) for g in tr.param_groups) + (
-            tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + tr._clip_settings() + tr._sched_settings() + eng.schedule_key()
+        return tuple((g["lr"], g.get("momentum"), g["weight_decay"], g.get("betas"), g.get("eps")) for g in tr.param_groups) + (
+            tr.optimizer_kind, tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + tr._clip_settings() + tr._sched_settings() + eng.schedule_key()
 
     def _eager(self, x, classes, boxes):
         from . import Losses
@@ -654,12 +726,14 @@ class GraphedTrainStep:
     def __call__(self, x, classes, boxes):
         tr = self.trainer
         self._calls += 1
-        if self._calls <= self.warmup or not (tr._has_momentum or all(g["momentum"] == 0 for g in tr.param_groups)):
+        started = tr.optimizer_kind != "sgd" or tr._has_momentum or all(g["momentum"] == 0 for g in tr.param_groups)
+        if self._calls <= self.warmup or not started:      # (Adam's moments start at zero: no first launch of another form to wait for)
             return self._eager(x, classes, boxes)
         if self._static is None:
             self._make_static(x)
         tr._clip_prepare()                # (the clip's small buffers come into being here, never inside a capture)
         tr._sched_prepare()               # (and the schedule block, the table of rates and the EMA buffer)
+        tr._adam_prepare()                # (and the Adam state block)
         self._load_batch(x, classes, boxes)
         if self.graph is None or self._sig != self._signature():
             self._capture()

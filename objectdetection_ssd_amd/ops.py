@@ -1062,6 +1062,60 @@ def swap_f32_(a, b):
     check(_lib.load().ssd_swap_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), "swap_f32")
 
 
+ADAM_STATE_WORDS = 3           # pow1, pow2 (f64), then step (int32) in the low half of the third 8-byte word: include/ssd_gfx950.h
+
+
+def adam_state(device, step: int = 0, pow1: float = 1.0, pow2: float = 1.0) -> torch.Tensor:
+    """A new Adam state block (f64[ADAM_STATE_WORDS]); `adam_state_step` is the int32 view of its counter."""
+    state = torch.tensor([pow1, pow2, 0.0], dtype=torch.float64)
+    state.view(torch.int32)[4] = int(step)
+    return state.to(device)
+
+
+def adam_state_step(state) -> torch.Tensor:
+    """0-dim int32 view of the block's step counter."""
+    return state.view(torch.int32)[4]
+
+
+def adam_advance_(state, beta1, beta2, skip=None):
+    """One step of the Adam state block: step + 1, pow1 * beta1, pow2 * beta2 (one f64 multiply each).  skip: optional int32 device
+    flag; when it is set nothing is written."""
+    _req(state, "state", torch.float64)
+    if state.numel() < ADAM_STATE_WORDS:
+        raise ValueError("adam_advance_: state holds 3 f64 words")
+    if skip is not None:
+        _req(skip, "skip", torch.int32)
+    check(_lib.load().ssd_adam_advance(state.data_ptr(), float(beta1), float(beta2), _ptr(skip), _stream()), "adam_advance")
+
+
+def adam_step_(param, grad, exp_avg, exp_avg_sq, ema, lr, lr_dev, ema_w_dev, state, beta1, beta2, eps, weight_decay, decoupled,
+               grad_scale=None, skip=None):
+    """One fused Adam (decoupled False: L2 weight decay) or AdamW (True) launch over equally long flat slices, at the host rate `lr`
+    (f64) or, given `lr_dev`, at that f32 device word; the bias corrections come from `state`, which `adam_advance_` has advanced for
+    this step.  Given `ema`, it moves towards the new parameters by the device weight `ema_w_dev` in the same pass; when the device
+    flag `skip` is set nothing is written."""
+    _req(param, "param"); _req(grad, "grad"); _req(exp_avg, "exp_avg"); _req(exp_avg_sq, "exp_avg_sq"); _req(state, "state", torch.float64)
+    n = param.numel()
+    if grad.numel() != n or exp_avg.numel() != n or exp_avg_sq.numel() != n or state.numel() < ADAM_STATE_WORDS:
+        raise ValueError("adam sizes")
+    if lr_dev is not None:
+        _req(lr_dev, "lr_dev")
+        if lr_dev.numel() < 1:
+            raise ValueError("adam sizes")
+    if ema is not None:
+        _req(ema, "ema"); _req(ema_w_dev, "ema_w_dev")
+        if ema.numel() != n or ema_w_dev.numel() < 1:
+            raise ValueError("adam sizes")
+    if grad_scale is not None:
+        _req(grad_scale, "grad_scale")
+    if skip is not None:
+        _req(skip, "skip", torch.int32)
+    check(_lib.load().ssd_adam_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), _ptr(ema), n, float(lr),
+                                    _ptr(lr_dev), _ptr(ema_w_dev) if ema is not None else None, state.data_ptr(), float(beta1),
+                                    float(beta2), float(eps), float(weight_decay), int(bool(decoupled)), _ptr(grad_scale), _ptr(skip),
+                                    _stream()), "adam_step")
+
+
 def map_eval(det_boxes, det_classes, det_scores, det_start, gt_boxes, gt_classes, gt_start, recall_levels, n_classes=20):
     """Concatenated detections / ground truth (see include/ssd_gfx950.h ssd_map_eval) -> (table (n_classes, n_levels)
     float64, tp (D,) uint8, counts (2, n_classes) int32).  recall_levels: host sequence of floats."""

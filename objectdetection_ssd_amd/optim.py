@@ -13,7 +13,7 @@ The kernel reproduces torch's rounding sequence, so the parameters after k steps
 
 This module is also where the pieces that `SGD` shares with `ddp.FlatSGDDataParallel` exist once: `FlatLayout` (the slot rule of a
 flat buffer), `FlatStore` (the flat parameter / gradient / momentum / EMA buffers of one layout, their views and the EMA's life
-cycle; `SGD` keeps one per parameter group, the trainer one over all its parameters), `FusedStepMixin._step_controls` (the order
+cycle; `SGD` / `Adam` keep one per parameter group, the trainer one over all its parameters), `FusedStepMixin._step_controls` (the order
 inside a step: clip norm and finalise, ONE schedule advance, and the device words the SGD launches then read) and `launch_sgd`
 (the choice between the plain, guarded and scheduled SGD wrappers).  What differs stays with each optimizer: how gradients reach the
 flat buffer, which ranges are launched, and the momentum bookkeeping.
@@ -28,6 +28,10 @@ finalise launch and the guarded form of the same SGD kernel, and nothing comes b
 A per-iteration learning-rate schedule (`LRSchedule`: warm-up, multistep, cosine, polynomial) and an exponential moving average of
 the weights (`ema_decay`) live on the device too (`SchedEmaMixin`): the rate is a device word the SGD launch reads, a device step
 counter indexes a table of rates built on the host, and the average is updated in the pass SGD makes anyway.
+
+`Adam` and `AdamW` are torch's optimizers of those names on the same stores, controls and launch order (`FlatGroupOptimizer` is what
+the three share): `ssd_adam_step` per run, the first moments in the stores' `mom` buffers, the second in `sq`, and ONE device step
+counter with the running products beta1^t, beta2^t per optimizer (`AdamStateMixin`), where torch counts per parameter.
 """
 from __future__ import annotations
 
@@ -329,15 +333,21 @@ class FlatLayout:
 
 class FlatStore:
     """The flat `param`, `grad`, `mom` and (once asked for) `ema` buffers of one `FlatLayout`, and their per-parameter views.  The
-    parameters are seated in `param` (`p.data` become its views); `grad` has `tail` more words behind the last slot."""
+    parameters are seated in `param` (`p.data` become its views); `grad` has `tail` more words behind the last slot.  `mom` is SGD's
+    momentum buffer or Adam's `exp_avg`; a store built with `sq_key` also has `sq`, Adam's `exp_avg_sq`."""
 
-    def __init__(self, params, layout: FlatLayout, tail: int = 0) -> None:
+    def __init__(self, params, layout: FlatLayout, tail: int = 0, mom_key: str = "momentum_buffer", sq_key=None) -> None:
         dev = params[0].device
         self.params, self.layout = list(params), layout
+        self.mom_key, self.sq_key = mom_key, sq_key                # the `state[p]` entries that `mom` and `sq` are the storage of
         self.param = torch.zeros(layout.total, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(layout.total + tail, device=dev, dtype=torch.float32)
         self.mom = torch.zeros(layout.total, device=dev, dtype=torch.float32)
         self.grad_views, self.mom_views = layout.views(self.grad), layout.views(self.mom)
+        self.sq = self.sq_views = None                             # Adam's second moment: only a store given `sq_key` has one
+        if sq_key is not None:
+            self.sq = torch.zeros(layout.total, device=dev, dtype=torch.float32)
+            self.sq_views = layout.views(self.sq)
         self.ema = self.ema_views = None                           # the weight EMA, with the parameters' layout (`make_ema`)
         self.ema_live = False                                      # a step has updated it, or a checkpoint brought it
         with torch.no_grad():
@@ -351,13 +361,17 @@ class FlatStore:
 
     def adopt(self, state) -> None:
         """Take over what a checkpoint (or the store these parameters lived in before) left in the optimizer's `state`: momentum
-        buffers are copied into `mom` and replaced by its views, and so are the averages, if there are any."""
+        buffers (or Adam's moments) are copied into `mom` (and `sq`) and replaced by their views, and so are the averages, if there
+        are any."""
         with torch.no_grad():
-            for p, mv in zip(self.params, self.mom_views):
-                have = state.get(p, {}).get("momentum_buffer")
-                if have is not None:
-                    mv.copy_(have.to(mv.device, torch.float32).reshape(mv.shape))
-                    state[p]["momentum_buffer"] = mv
+            for key, views in ((self.mom_key, self.mom_views), (self.sq_key, self.sq_views)):
+                if key is None:
+                    continue
+                for p, mv in zip(self.params, views):
+                    have = state.get(p, {}).get(key)
+                    if have is not None:
+                        mv.copy_(have.to(mv.device, torch.float32).reshape(mv.shape))
+                        state[p][key] = mv
         emas = [state.get(p, {}).get("ema") for p in self.params]
         if self.ema is not None or any(e is not None for e in emas):
             self.make_ema(state, emas)
@@ -385,28 +399,77 @@ class FlatStore:
         self.ema_live = True
 
 
-class SGD(FusedStepMixin, torch.optim.Optimizer):
-    def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
-                 nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None,
-                 max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False, schedule=None, ema_decay=None,
-                 ema_warmup: bool = True):
-        """max_grad_norm: clip the GLOBAL norm (`norm_type` 2 or inf) of every gradient of every group to it, as
-        `torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm, norm_type)` before `step()` does.  skip_nonfinite: a step whose
-        gradient norm is Inf or NaN changes neither parameters nor momentum and counts into `skipped_steps`.
+class AdamStateMixin:
+    """The Adam state block of `optim.Adam` / `optim.AdamW` and of `ddp.FlatSGDDataParallel(optimizer="adam" | "adamw")`: ONE step
+    counter and ONE pair of running products beta1^t, beta2^t per optimizer, on the device (include/ssd_gfx950.h, ssd_adam_advance).
+    `adam_steps` is a view of the counter and never synchronises."""
 
-        schedule: an `LRSchedule`; step t runs group g at float32(group['lr'] * schedule.factors[t]) read from a device table, the
-        groups' 'lr' stay the base rates.  ema_decay (in (0, 1)): keep an exponential moving average of every parameter,
-        e += (1 - d_t) * (p - e) after each step, d_t = min(ema_decay, (1 + t) / (10 + t)) with `ema_warmup`, else ema_decay;
-        `state[p]['ema']`, `ema_parameters()` and `ema_weights()` reach it.  A parameter takes part in the steps it has a gradient in."""
+    def _init_adam(self) -> None:
+        self._adam_state = None           # f64[3]: pow1, pow2, step
+        self._adam_start = (0, 1.0, 1.0)  # what a restored checkpoint starts the block from, until it exists
+
+    @staticmethod
+    def _adam_betas(groups):
+        """The one pair of betas of all groups: the running products are per optimizer, as the counter is."""
+        betas = {(float(g["betas"][0]), float(g["betas"][1])) for g in groups}
+        if len(betas) != 1:
+            raise ValueError(f"Adam: every parameter group must have the same betas (one step counter and one pair of running "
+                             f"products per optimizer), got {sorted(betas)}")
+        b1, b2 = next(iter(betas))
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"Adam: betas must be in [0, 1), got {(b1, b2)}")
+        return b1, b2
+
+    def _adam_buffers(self, dev) -> None:
+        """The block, made outside any capture."""
+        if self._adam_state is None or self._adam_state.device != dev:
+            if self._adam_state is not None:
+                words = self._adam_state.cpu()
+                self._adam_start = (int(words.view(torch.int32)[4]), float(words[0]), float(words[1]))
+            self._adam_state = ops.adam_state(dev, *self._adam_start)
+
+    def _adam_restore(self, t: int, beta1: float, beta2: float) -> None:
+        """A checkpoint's step count: the products are rebuilt by the t multiplications the device would have done (Python floats
+        are IEEE f64), and written INTO the block when it exists, so a captured step keeps reading the right memory."""
+        pow1 = pow2 = 1.0
+        for _ in range(int(t)):
+            pow1, pow2 = pow1 * beta1, pow2 * beta2
+        self._adam_start = (int(t), pow1, pow2)
+        if self._adam_state is not None:
+            self._adam_state.copy_(ops.adam_state("cpu", *self._adam_start))
+
+    def _adam_step_host(self) -> int:
+        """The counter, read back: the one synchronisation (checkpoints)."""
+        return int(ops.adam_state_step(self._adam_state).item()) if self._adam_state is not None else int(self._adam_start[0])
+
+    @property
+    def adam_steps(self):
+        """0-dim int32 device tensor: Adam steps actually taken (skipped steps do not count); None before the first step."""
+        return None if self._adam_state is None else ops.adam_state_step(self._adam_state)
+
+
+def check_adam_settings(name, lr, betas, eps, weight_decay, amsgrad, maximize, differentiable) -> None:
+    if amsgrad or maximize or differentiable:
+        raise ValueError(f"{name}: amsgrad / maximize / differentiable are not implemented")
+    if isinstance(lr, torch.Tensor) or not lr >= 0.0:
+        raise ValueError(f"{name}: lr must be a non-negative number, got {lr!r}")
+    if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+        raise ValueError(f"{name}: betas must be two numbers in [0, 1), got {betas!r}")
+    if not eps >= 0.0 or not weight_decay >= 0.0:
+        raise ValueError(f"{name}: eps and weight_decay must be non-negative")
+
+
+class FlatGroupOptimizer(FusedStepMixin, torch.optim.Optimizer):
+    """What `SGD`, `Adam` and `AdamW` share: one `FlatStore` per parameter group, seated the first time a step (or the EMA's
+    accessors) sees the group, the EMA's accessors, and how a step turns the groups' gradients into launch ranges (`_gather`) and
+    the device words the launches read (`_controls`).  A subclass names the `state[p]` entries its store's `mom` / `sq` buffers
+    are (`_MOM_KEY`, `_SQ_KEY`) and writes `step()`."""
+
+    _MOM_KEY, _SQ_KEY = "momentum_buffer", None
+
+    def __init__(self, params, defaults, max_grad_norm, norm_type, skip_nonfinite, schedule, ema_decay, ema_warmup) -> None:
         self._init_clip(max_grad_norm, norm_type, skip_nonfinite)
         self._init_sched(schedule, ema_decay, ema_warmup)
-        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
-            raise ValueError("SGD: lr, momentum and weight_decay must be non-negative")
-        if dampening != 0.0 or nesterov or maximize or differentiable:
-            raise ValueError("SGD: dampening / nesterov / maximize / differentiable are not part of the reference's step "
-                             "(train.py:53-55) and are not implemented")
-        defaults = dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False, maximize=False,
-                        foreach=foreach, differentiable=False, fused=fused)
         super().__init__(params, defaults)
         self._buffers: List[FlatStore | None] = [None] * len(self.param_groups)       # one store per parameter group
 
@@ -414,16 +477,6 @@ class SGD(FusedStepMixin, torch.optim.Optimizer):
         super().add_param_group(param_group)
         if hasattr(self, "_buffers"):
             self._buffers.append(None)
-
-    def state_dict(self):
-        """torch's layout; with the schedule or the EMA on, every group also carries `sched_step`, the device step counter (reading it
-        is the one synchronisation), and `state[p]['ema']` travels with the momentum buffers."""
-        return self._sched_stamp(super().state_dict())
-
-    def load_state_dict(self, state_dict) -> None:
-        super().load_state_dict(state_dict)
-        self._buffers = [None] * len(self.param_groups)           # restored momentum and EMA buffers are re-seated at the next step
-        self._sched_unstamp()
 
     def _seat_all(self) -> None:
         for gi, group in enumerate(self.param_groups):
@@ -463,37 +516,30 @@ class SGD(FusedStepMixin, torch.optim.Optimizer):
         if buf is None or not buf.seated(params):                 # first step, or the caller moved / replaced the tensors
             for p in params:
                 if p.dtype != torch.float32 or p.device.type != "cuda" or not p.is_contiguous():
-                    raise ValueError("SGD: parameters must be contiguous float32 tensors on the GPU")
-            buf = self._buffers[gi] = FlatStore(params, FlatLayout(params))
-            buf.adopt(self.state)                                 # restored momentum and EMA buffers
+                    raise ValueError(f"{type(self).__name__}: parameters must be contiguous float32 tensors on the GPU")
+            buf = self._buffers[gi] = FlatStore(params, FlatLayout(params), mom_key=self._MOM_KEY, sq_key=self._SQ_KEY)
+            buf.adopt(self.state)                                 # restored momentum / moment and EMA buffers
         return buf
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        clip, sched = self._clip_on(), self._sched_on()
-        pending = []                                              # every group's runs: the norm covers them all, then ONE advance
+    def _gather(self, fresh_of=None):
+        """-> [(gi, group, store, runs)] for every group with a gradient, the gradients copied into the stores' flat buffers.
+        Parameters without a gradient are skipped, as torch skips them: maximal runs [lo, hi, fresh] of neighbouring parameters in
+        the same situation are one launch (the whole group, in the reference's loop); `fresh_of(group, p)` tells the situations
+        apart (SGD: the momentum buffer starts at this step), None: there is one."""
+        pending = []
         for gi, group in enumerate(self.param_groups):
-            if group["dampening"] != 0 or group["nesterov"] or group.get("maximize", False):
-                raise ValueError("SGD: dampening / nesterov / maximize are not implemented")
             params = group["params"]
             if not params:
                 continue
             buf = self._group_buffers(gi, params)
-            lr, mom, wd = float(group["lr"]), float(group["momentum"]), float(group["weight_decay"])
-            # torch skips parameters without a gradient and starts a momentum buffer at the first gradient it sees: maximal runs of
-            # neighbouring parameters in the same situation are one launch (the whole group, in the reference's loop)
             runs, cur = [], None
             for i, p in enumerate(params):
                 if p.grad is None:
                     cur = None
                     continue
                 if p.grad.is_sparse:
-                    raise ValueError("SGD: sparse gradients are not supported")
-                fresh = mom != 0.0 and self.state[p].get("momentum_buffer") is None
+                    raise ValueError(f"{type(self).__name__}: sparse gradients are not supported")
+                fresh = bool(fresh_of(group, p)) if fresh_of is not None else False
                 if cur is not None and cur[2] == fresh:
                     cur[1] = i + 1
                 else:
@@ -503,17 +549,72 @@ class SGD(FusedStepMixin, torch.optim.Optimizer):
             if not have:
                 continue
             torch._foreach_copy_([buf.grad_views[i] for i in have], [params[i].grad for i in have])
-            pending.append((gi, buf, runs, lr, mom, wd))
+            pending.append((gi, group, buf, runs))
+        return pending
+
+    def _controls(self, pending):
+        """ONE norm over the runs the launches cover (slots of parameters without a gradient hold stale data and are in no run),
+        then ONE schedule advance -> `_step_controls`' device words."""
+        ranges = [buf.grad[buf.layout.span(lo, hi)] for _, _, buf, runs in pending for lo, hi, _ in runs]
+        if self._clip_on():
+            self._clip_buffers(ranges[0].device, sum(ops.grad_norm_slots(r.numel()) for r in ranges))
+        if self._sched_on():
+            self._sched_buffers(ranges[0].device)
+        return self._step_controls(ranges)
+
+
+class SGD(FlatGroupOptimizer):
+    def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+                 nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None,
+                 max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False, schedule=None, ema_decay=None,
+                 ema_warmup: bool = True):
+        """max_grad_norm: clip the GLOBAL norm (`norm_type` 2 or inf) of every gradient of every group to it, as
+        `torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm, norm_type)` before `step()` does.  skip_nonfinite: a step whose
+        gradient norm is Inf or NaN changes neither parameters nor momentum and counts into `skipped_steps`.
+
+        schedule: an `LRSchedule`; step t runs group g at float32(group['lr'] * schedule.factors[t]) read from a device table, the
+        groups' 'lr' stay the base rates.  ema_decay (in (0, 1)): keep an exponential moving average of every parameter,
+        e += (1 - d_t) * (p - e) after each step, d_t = min(ema_decay, (1 + t) / (10 + t)) with `ema_warmup`, else ema_decay;
+        `state[p]['ema']`, `ema_parameters()` and `ema_weights()` reach it.  A parameter takes part in the steps it has a gradient in."""
+        check_clip_settings(max_grad_norm, norm_type, skip_nonfinite)
+        check_sched_settings(schedule, ema_decay, ema_warmup)
+        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
+            raise ValueError("SGD: lr, momentum and weight_decay must be non-negative")
+        if dampening != 0.0 or nesterov or maximize or differentiable:
+            raise ValueError("SGD: dampening / nesterov / maximize / differentiable are not part of the reference's step "
+                             "(train.py:53-55) and are not implemented")
+        defaults = dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False, maximize=False,
+                        foreach=foreach, differentiable=False, fused=fused)
+        super().__init__(params, defaults, max_grad_norm, norm_type, skip_nonfinite, schedule, ema_decay, ema_warmup)
+
+    def state_dict(self):
+        """torch's layout; with the schedule or the EMA on, every group also carries `sched_step`, the device step counter (reading it
+        is the one synchronisation), and `state[p]['ema']` travels with the momentum buffers."""
+        return self._sched_stamp(super().state_dict())
+
+    def load_state_dict(self, state_dict) -> None:
+        super().load_state_dict(state_dict)
+        self._buffers = [None] * len(self.param_groups)           # restored momentum and EMA buffers are re-seated at the next step
+        self._sched_unstamp()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        sched = self._sched_on()
+        self._clip_on()
+        for group in self.param_groups:
+            if group["dampening"] != 0 or group["nesterov"] or group.get("maximize", False):
+                raise ValueError("SGD: dampening / nesterov / maximize are not implemented")
+        # torch starts a momentum buffer at the first gradient it sees: such parameters are launches of their own
+        pending = self._gather(lambda group, p: group["momentum"] != 0 and self.state[p].get("momentum_buffer") is None)
         if not pending:
             return loss
-        # ONE norm over the runs the SGD launches cover: slots of parameters without a gradient hold stale data and are in no run
-        ranges = [buf.grad[buf.layout.span(lo, hi)] for _, buf, runs, *_ in pending for lo, hi, _ in runs]
-        if clip:
-            self._clip_buffers(ranges[0].device, sum(ops.grad_norm_slots(r.numel()) for r in ranges))
-        if sched:
-            self._sched_buffers(ranges[0].device)
-        grad_scale, skip, lr_words, ema_w = self._step_controls(ranges)
-        for gi, buf, runs, lr, mom, wd in pending:
+        grad_scale, skip, lr_words, ema_w = self._controls(pending)
+        for gi, group, buf, runs in pending:
+            lr, mom, wd = float(group["lr"]), float(group["momentum"]), float(group["weight_decay"])
             if self.ema_decay is not None:
                 buf.start_ema(self.state)
             for lo, hi, fresh in runs:
@@ -529,3 +630,113 @@ class SGD(FusedStepMixin, torch.optim.Optimizer):
                         self.state[p]["momentum_buffer"] = buf.mom_views[i]
                     torch.autograd.graph.increment_version(p)     # written outside autograd: invalidate re-laid weight caches
         return loss
+
+
+class Adam(AdamStateMixin, FlatGroupOptimizer):
+    """`torch.optim.Adam` (L2 weight decay; `decoupled_weight_decay=True` makes it AdamW) on the flat stores and the step sequence
+    of `optim.SGD`: `ssd_adam_step` (include/ssd_gfx950.h) once per run of neighbouring parameters with a gradient, the first
+    moments in the stores' `mom` buffers, the second in `sq`.  Same constructor and param-group keys as torch's, same
+    `state[p] = {'step', 'exp_avg', 'exp_avg_sq'}` entries, so checkpoints move between the two; `exp_avg` and `exp_avg_sq`
+    follow torch's rounding sequence bit for bit (foreach=False), the parameter follows the sequence documented in the header.
+
+    The one deliberate departure from torch: the step counter is ONE device word per optimizer, not one per parameter.  A parameter
+    without a gradient is left out of that step's launches and its moments stay untouched, as in torch, but when it takes part again
+    its bias correction follows the optimizer's counter, where torch's would follow the number of steps that parameter itself has
+    taken.  For the same reason every group has the same betas, and `load_state_dict` refuses per-parameter steps that disagree.
+    `state[p]['step']` is brought up to date by `state_dict()`, which reads the counter back (the one synchronisation).
+
+    max_grad_norm / norm_type / skip_nonfinite / schedule / ema_decay / ema_warmup: exactly as in `optim.SGD`; a skipped step
+    advances neither counter.  Without a schedule and without the EMA the step size comes from the f64 `group['lr']`, as torch's
+    does; with either it comes from the f32 device word of the schedule block."""
+
+    _MOM_KEY, _SQ_KEY = "exp_avg", "exp_avg_sq"
+    _DECOUPLED = False
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 amsgrad: bool = False, *, foreach=None, maximize: bool = False, capturable: bool = False,
+                 differentiable: bool = False, fused=None, decoupled_weight_decay: bool = False, max_grad_norm=None, norm_type=2.0,
+                 skip_nonfinite: bool = False, schedule=None, ema_decay=None, ema_warmup: bool = True):
+        name = type(self).__name__
+        check_clip_settings(max_grad_norm, norm_type, skip_nonfinite)
+        check_sched_settings(schedule, ema_decay, ema_warmup)
+        check_adam_settings(name, lr, betas, eps, weight_decay, amsgrad, maximize, differentiable)
+        self._init_adam()
+        defaults = dict(lr=lr, betas=(betas[0], betas[1]), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                        foreach=foreach, capturable=capturable, differentiable=False, fused=fused,
+                        decoupled_weight_decay=bool(decoupled_weight_decay) or self._DECOUPLED)
+        super().__init__(params, defaults, max_grad_norm, norm_type, skip_nonfinite, schedule, ema_decay, ema_warmup)
+
+    def state_dict(self):
+        """torch's layout: `state[p] = {'step' (0-dim f32, the optimizer's counter), 'exp_avg', 'exp_avg_sq'}` plus `'ema'` when
+        there is one, torch's param-group keys, and `sched_step` with the schedule or the EMA on, as `optim.SGD` carries it."""
+        t = self._adam_step_host()
+        for st in self.state.values():
+            if "exp_avg" in st:
+                st["step"] = torch.tensor(float(t), dtype=torch.float32)
+        return self._sched_stamp(super().state_dict())
+
+    def load_state_dict(self, state_dict) -> None:
+        """Both moments are re-seated into the stores at the next step; the running products are rebuilt from the step count by the
+        multiplications the device would have done, so a resumed run continues bit for bit."""
+        steps = {float(st["step"]) for st in state_dict["state"].values() if "step" in st}
+        if len(steps) > 1:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: the parameters' step counts disagree ({sorted(steps)}); the "
+                             "step counter here is one per optimizer")
+        t = steps.pop() if steps else 0.0
+        if t != int(t) or t < 0:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: step count {t!r}")
+        super().load_state_dict(state_dict)
+        self._buffers = [None] * len(self.param_groups)
+        self._sched_unstamp()
+        self._adam_restore(int(t), *self._adam_betas(self.param_groups))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        sched = self._sched_on()
+        self._clip_on()
+        for group in self.param_groups:
+            check_adam_settings(type(self).__name__, group["lr"], group["betas"], group["eps"], group["weight_decay"],
+                                group.get("amsgrad", False), group.get("maximize", False), group.get("differentiable", False))
+        beta1, beta2 = self._adam_betas(self.param_groups)
+        pending = self._gather()
+        if not pending:
+            return loss
+        grad_scale, skip, lr_words, ema_w = self._controls(pending)
+        self._adam_buffers(pending[0][2].param.device)
+        ops.adam_advance_(self._adam_state, beta1, beta2, skip if self.skip_nonfinite else None)
+        for gi, group, buf, runs in pending:
+            if self.ema_decay is not None:
+                buf.start_ema(self.state)
+            for lo, hi, _ in runs:
+                span = buf.layout.span(lo, hi)
+                ops.adam_step_(buf.param[span], buf.grad[span], buf.mom[span], buf.sq[span],
+                               buf.ema[span] if self.ema_decay is not None else None, float(group["lr"]),
+                               lr_words[gi:gi + 1] if sched else None, ema_w, self._adam_state, beta1, beta2, float(group["eps"]),
+                               float(group["weight_decay"]), bool(group.get("decoupled_weight_decay", self._DECOUPLED)), grad_scale, skip)
+                for i in range(lo, hi):
+                    p = buf.params[i]
+                    st = self.state[p]
+                    if "exp_avg" not in st:                       # torch's entries; zero moments are Adam's own start
+                        st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                        st["exp_avg"], st["exp_avg_sq"] = buf.mom_views[i], buf.sq_views[i]
+                    torch.autograd.graph.increment_version(p)     # written outside autograd: invalidate re-laid weight caches
+        return loss
+
+
+class AdamW(Adam):
+    """`torch.optim.AdamW`: `optim.Adam` with decoupled weight decay, p <- p * float32(1 - lr * weight_decay) before the step."""
+
+    _DECOUPLED = True
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 amsgrad: bool = False, *, maximize: bool = False, foreach=None, capturable: bool = False,
+                 differentiable: bool = False, fused=None, max_grad_norm=None, norm_type=2.0, skip_nonfinite: bool = False,
+                 schedule=None, ema_decay=None, ema_warmup: bool = True):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=True, max_grad_norm=max_grad_norm,
+                         norm_type=norm_type, skip_nonfinite=skip_nonfinite, schedule=schedule, ema_decay=ema_decay,
+                         ema_warmup=ema_warmup)
