@@ -2,7 +2,7 @@
 
     python examples/train_synthetic.py [--steps 20] [--batch 20] [--fused-sgd] [--grad-clip 10.0]
                                        [--schedule none|multistep|cosine] [--warmup-steps 5] [--ema-decay 0.999]
-                                       [--decode host|device]
+                                       [--decode host|device] [--ignore-difficult]
 
 With the reference checked out next to this repo, the same three lines (`install_dropin()`, then
 `from train_function import train_model`) run its own `train_model` unchanged -- see INTEGRATION.md.
@@ -23,7 +23,7 @@ from Losses import ssd            # noqa: E402  (reference import style)
 from Model import SSD_300         # noqa: E402
 
 
-def batches(n, bs, dev, seed=0):
+def batches(n, bs, dev, seed=0, ignore_difficult=False):
     rng = np.random.default_rng(seed)
     g = torch.Generator().manual_seed(seed)
     for _ in range(n):
@@ -35,10 +35,15 @@ def batches(n, bs, dev, seed=0):
             w, h = rng.uniform(.08, .6, k), rng.uniform(.08, .6, k)
             boxes.append(torch.tensor(np.stack([x1, y1, np.minimum(x1 + w, 1), np.minimum(y1 + h, 1)], 1), dtype=torch.float32))
             classes.append(torch.tensor(rng.integers(0, 20, k), dtype=torch.float32))
-        yield x, classes, boxes
+        if not ignore_difficult:
+            yield x, classes, boxes, None
+            continue
+        # every second object after an image's first counts as `difficult`: out of the ground truth, into the ignore list
+        hard = [torch.arange(len(b)) % 2 == 1 for b in boxes]
+        yield x, [c[~h] for c, h in zip(classes, hard)], [b[~h] for b, h in zip(boxes, hard)], [b[h] for b, h in zip(boxes, hard)]
 
 
-def jpeg_batches(n, bs, decode, seed=0):
+def jpeg_batches(n, bs, decode, seed=0, ignore_difficult=False):
     """The reference's input side (train.py:29): synthetic JPEG files on disk, `MultiImageMultiBBoxDataset` + `collate_fn` in two
     DataLoader workers.  decode="host": PIL decodes in the workers and pixels travel; decode="device": the files' bytes travel and
     `inputs.to(device)` decodes them on the GPU (a progressive file among them takes the PIL path inside the same batch)."""
@@ -59,10 +64,14 @@ def jpeg_batches(n, bs, decode, seed=0):
         x1, y1 = rng.uniform(0, 300, k), rng.uniform(0, 225, k)
         boxes.append(np.stack([x1, y1, x1 + rng.uniform(40, 190, k), y1 + rng.uniform(40, 140, k)], 1).tolist())
         labels.append([class_to_label[int(c)] for c in rng.integers(0, 20, k)])
-    ds = MultiImageMultiBBoxDataset(paths, boxes, labels, [[0] * len(b) for b in boxes], list(range(len(paths))), decode=decode)
+    # --ignore-difficult: every second object after an image's first is `difficult`; keep_difficult="ignore" leaves those out of the
+    # ground truth (as the default False does) and hands them back, carried through the same augmentation, as a fifth list
+    difficult = [[int(ignore_difficult and j % 2 == 1) for j in range(len(b))] for b in boxes]
+    ds = MultiImageMultiBBoxDataset(paths, boxes, labels, difficult, list(range(len(paths))),
+                                    keep_difficult="ignore" if ignore_difficult else False, decode=decode)
     dl = torch.utils.data.DataLoader(ds, batch_size=bs, shuffle=True, num_workers=2, collate_fn=collate_fn)
-    for inputs, classes, bboxes, _ in dl:
-        yield inputs, classes, bboxes
+    for inputs, classes, bboxes, _, *ignore in dl:
+        yield inputs, classes, bboxes, (ignore[0] if ignore else None)
     tmp.cleanup()
 
 
@@ -86,6 +95,9 @@ def main():
     ap.add_argument("--decode", choices=("host", "device"), default=None,
                     help="feed the loop from synthetic JPEG files through Dataset / DataLoader workers instead of random tensors: "
                          "'host' decodes with PIL in the workers, 'device' ships the compressed bytes and decodes on the GPU")
+    ap.add_argument("--ignore-difficult", action="store_true",
+                    help="mark some objects `difficult` and train with them as ignore regions (Losses.ssd(ignore_bboxs=...)): the priors "
+                         "over them are neither positives nor mined as hard negatives")
     a = ap.parse_args()
     opt_kw = {}
     if a.schedule != "none" or a.warmup_steps or a.ema_decay is not None:
@@ -119,15 +131,19 @@ def main():
         optimizer = SGD(params=groups, lr=lr, momentum=0.9, weight_decay=5e-4, **opt_kw)      # train.py:53-55
     cnn.train()
     t0 = time.time()
-    feed = batches(a.steps, a.batch, device) if a.decode is None else jpeg_batches(a.steps, a.batch, a.decode)
-    for count, (inputs, classes, bboxes) in enumerate(feed):
+    feed = (batches(a.steps, a.batch, device, ignore_difficult=a.ignore_difficult) if a.decode is None else
+            jpeg_batches(a.steps, a.batch, a.decode, ignore_difficult=a.ignore_difficult))
+    for count, (inputs, classes, bboxes, ignore) in enumerate(feed):
         raw = inputs
         inputs = inputs.to(device)                            # a RawBatch: upload, JPEG decode, photometric, resize + normalise
         classes = [c.to(device) for c in classes]
         bboxes = [b.to(device) for b in bboxes]
         optimizer.zero_grad()
         outputs = cnn(inputs)
-        loss1, loss2 = ssd(outputs, classes, bboxes)
+        if ignore is None:
+            loss1, loss2 = ssd(outputs, classes, bboxes)
+        else:
+            loss1, loss2 = ssd(outputs, classes, bboxes, ignore_bboxs=ignore)
         loss = loss1 + loss2
         loss.backward()
         optimizer.step()
@@ -138,6 +154,9 @@ def main():
                         f"  skipped {optimizer.skipped_steps.item()}")
             if "schedule" in opt_kw or "ema_decay" in opt_kw:
                 norm += f"  lr {optimizer.current_lr[1].item():.3g}  ema_w {optimizer.ema_weight.item():.3g}"
+            if ignore is not None:                            # reading it is this loop's sync
+                import Losses
+                norm += f"  ignored priors {int(Losses.last_match['ignored'].sum())} ({sum(len(b) for b in ignore)} boxes)"
             if getattr(raw, "decode_status", None) is not None:   # reading it is this loop's sync
                 norm += f"  decoded on the device {int((raw.decode_status == 0).sum())}/{len(raw)}"
             print(f"it {count:3d}  l1 {loss1.item():.4f}  l2 {loss2.item():.4f}{norm}  {time.time() - t0:.1f}s")

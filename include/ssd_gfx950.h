@@ -467,6 +467,32 @@ int ssd_multibox_loss(const float* loc, const float* conf, const float* gt_boxes
                       int norm_mode, float* losses, int32_t* obj, int32_t* cls, float* dloc, float* dconf,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- MultiBox loss with ignore regions (VOC `difficult` objects, COCO crowd regions) ----------
+ * ssd_multibox_loss's arguments, meaning and status codes, plus:
+ *   ign_boxes (n_ign,4) xyxy f32, fractional like gt_boxes; may be NULL when n_ign == 0.
+ *   ign_start (bs+1) int32 ON THE DEVICE: prefix offsets into ign_boxes (data, as img_start is: a captured call replays any
+ *             split of the boxes over the images, an image may have none).  n_ign = total number of ignore boxes, >= 0.
+ *   ignore_threshold, overlap_mode: a prior that is NOT positive is ignored when some ignore box of its image overlaps it by
+ *             >= ignore_threshold.  overlap_mode 0: IoU (the matching's f32 op sequence); 1: intersection / the prior's own
+ *             unclipped area (the crowd rule of the COCO protocol with the prior in the detection's place).  A NaN overlap
+ *             ignores nothing.
+ *   ign (bs,P) uint8 output: 1 for an ignored prior.
+ * Matching takes no notice of ignore boxes: a positive prior (threshold or forced match) stays positive.  An ignored prior is
+ * treated in the hard-negative mining as the positives are (mining value 0; ranking, quota min(ratio * n_pos, P) and the
+ * lower-index-first tie rule are unchanged) and receives no gradient: its dconf and dloc rows are exactly zero, also when the
+ * quota reaches into the zero values.  With no ignore box in any image every output equals ssd_multibox_loss's bit for bit.
+ * Always the three-launch form: ssd_tune_set_loss_form does not reach this entry (the four-launch cross-check form has no
+ * ignore path).  The workspace is ssd_multibox_loss's.
+ * Errors: SSD_ERR_NULL (a null pointer; ign_boxes null with n_ign > 0), SSD_ERR_BAD_SHAPE (the shape rules above, n_ign < 0,
+ * overlap_mode not 0 / 1), SSD_ERR_ALIGN (ign_boxes not 16-byte aligned, besides the rules above), SSD_ERR_WORKSPACE. */
+size_t ssd_multibox_loss_ignore_workspace(int bs, int P, int n_gt, int n_ign);
+int ssd_multibox_loss_ignore(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                             const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh,
+                             const float* priors_xyxy, int P, int n_classes, float iou_threshold, int neg_pos_ratio,
+                             int norm_mode, const float* ign_boxes, const int32_t* ign_start, int n_ign,
+                             float ignore_threshold, int overlap_mode, float* losses, int32_t* obj, int32_t* cls,
+                             uint8_t* ign, float* dloc, float* dconf, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- decode + per-class NMS + top-k (Losses.py:11-98 inference; Util.py:86-96) ----------
  * l_ (P,4), c_ (P,n_classes) of ONE image, n_classes = conf width C, 2..256 (background = C-1 is never a detection).
  * Outputs (capacity top_k): boxes (top_k,4) xyxy scaled by (img_w,img_h,img_w,img_h), classes int64 (0..C-2), probs f32,

@@ -132,6 +132,30 @@ def plan_transform(width: int, height: int, boxes: torch.Tensor, labels: torch.T
     return GeomPlan(height, width, canvas, crop, flip, photo), boxes, labels
 
 
+def map_regions(plan: GeomPlan, boxes: torch.Tensor) -> torch.Tensor:
+    """Pixel xyxy boxes that are NOT ground truth (ignore regions: VOC `difficult` objects, COCO crowd regions) carried through a
+    drawn plan, with the f32 operations `plan_transform` applies to the ground truth: shift by the canvas placement; intersect with
+    the crop window and translate to it (a region is kept by what is left of it, not by its centre: half an unlabelled object in
+    the crop is still an unlabelled object); drop what is left with no area; mirror with the reference's flip arithmetic
+    (Util.py:732-749).  No random draw: the plan, and so every other item of the sample, is that of the ground truth alone."""
+    boxes = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4).clone()
+    ch, cw, top, left = plan.canvas
+    boxes = boxes + torch.FloatTensor([left, top, left, top]).unsqueeze(0)
+    ct, cl, crop_h, crop_w = plan.crop
+    if (ct, cl, crop_h, crop_w) != (0, 0, ch, cw):
+        cb = torch.FloatTensor([cl, ct, cl + crop_w, ct + crop_h])
+        boxes[:, :2] = torch.max(boxes[:, :2], cb[:2])
+        boxes[:, :2] -= cb[:2]
+        boxes[:, 2:] = torch.min(boxes[:, 2:], cb[2:])
+        boxes[:, 2:] -= cb[:2]
+    boxes = boxes[(boxes[:, 2] > boxes[:, 0]) & (boxes[:, 3] > boxes[:, 1])]
+    if plan.flip:
+        x0 = crop_w - boxes[:, 0] - 1
+        x2 = crop_w - boxes[:, 2] - 1
+        boxes = torch.stack((x2, boxes[:, 1], x0, boxes[:, 3]), dim=1)
+    return boxes
+
+
 class RawBatch:
     """A batch as it leaves a DataLoader worker: the images' 8-bit pixels packed into ONE CPU uint8 tensor plus each image's
     geometry / photometric plan -- plain host data, picklable, no GPU touched (reference train.py:29,40 runs `collate_fn`
@@ -304,7 +328,10 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
     """Reference Dataset.py:7-39 with the same constructor.  `__getitem__` returns the RAW 8-bit image and its
     geometry plan instead of a normalised tensor: `(RawImage, classes, standardized_bbox, index)` -- host work only, as it
     runs in DataLoader workers; `collate_fn` packs a batch's RawImages into a `RawBatch` whose `.to(device)` (the caller's
-    own line train_function.py:61, main process) makes the normalised device tensor."""
+    own line train_function.py:61, main process) makes the normalised device tensor.
+    keep_difficult: False (the reference's default: difficult objects are dropped), True (kept as ground truth), or "ignore":
+    dropped from the ground truth as with False -- same draws, same four items -- and returned as a fifth item `ignore_bbox`
+    (m, 4), carried through the sample's plan by `map_regions` and standardised like the boxes, for `Losses.ssd(ignore_bboxs=...)`."""
 
     def __init__(self, all_images, all_multi_bboxes, all_multi_labels, all_difficulties, all_indices, isTest=False,
                  keep_difficult=False, decode="host"):
@@ -332,14 +359,21 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
             image = RawImage.of(Image.open(self.images_list[index]).convert("RGB"))
         c = torch.Tensor([label_to_class[i] for i in self.multi_labels_list[index]])
         bboxes = torch.Tensor(self.multi_bbox_list[index])
-        if self.keep_difficult is False:
+        ignore = None
+        as_ignore = isinstance(self.keep_difficult, str) and self.keep_difficult == "ignore"
+        if self.keep_difficult is False or as_ignore:
             keep = self.all_difficulties[index] == 0
+            if as_ignore:
+                ignore = bboxes[~keep]
             bboxes, c = bboxes[keep], c[keep]
         if self.isTest is False:
             image, bboxes, c = transform(image, bboxes, c)            # Dataset.py:33
         w, h = image.size                                             # Dataset.py:35
         standardized_bbox = bboxes / torch.FloatTensor([w, h, w, h]).unsqueeze(0)
-        return image, c, standardized_bbox, self.all_indices[index]
+        if ignore is None:
+            return image, c, standardized_bbox, self.all_indices[index]
+        ignore_bbox = map_regions(image.plan, ignore) / torch.FloatTensor([w, h, w, h]).unsqueeze(0)
+        return image, c, standardized_bbox, self.all_indices[index], ignore_bbox
 
 
 @dataclass
@@ -528,12 +562,15 @@ class EncodedImage:
 def collate_fn(batch):
     """Reference Dataset.py:41-53: (images, classes, boxes, indices) of a list of samples.  Host work only (it runs in the
     DataLoader's workers): RawImage entries are packed into one `RawBatch`; already-normalised tensors are stacked like the
-    reference does."""
+    reference does.  Samples of `keep_difficult="ignore"` carry a fifth item: their ignore boxes come back as a fifth list."""
     images, classes, boxes, indices = [], [], [], []
     for b in batch:
         images.append(b[0]); classes.append(b[1]); boxes.append(b[2]); indices.append(b[3])
+    ignore = [b[4] for b in batch] if batch and len(batch[0]) == 5 else None
     if images and isinstance(images[0], (RawImage, EncodedImage)):
         x = pack_batch([r.pixels if isinstance(r, RawImage) else r for r in images], [r.plan for r in images])
     else:
         x = torch.stack(images, dim=0)
+    if ignore is not None:
+        return x, classes, boxes, indices, ignore
     return x, classes, boxes, indices

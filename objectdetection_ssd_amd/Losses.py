@@ -46,21 +46,26 @@ def _priors_on(dev: torch.device, n_priors: int = 8732):
 
 class _MultiBoxLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, loc, conf, gt, gt_cls, img_start, norm_mode):
+    def forward(ctx, loc, conf, gt, gt_cls, img_start, norm_mode, ignore=None):
         pri, pri_xyxy = _priors_on(loc.device, loc.shape[1])
         want = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        kw = {}
+        if ignore is not None:                           # (boxes, starts, threshold, overlap): the entry with ignore regions
+            kw = dict(ignore_boxes=ignore[0], ignore_start=ignore[1], ignore_threshold=ignore[2], ignore_overlap=ignore[3])
         out = ops.multibox_loss(loc.detach().contiguous(), conf.detach().contiguous(), gt, gt_cls, img_start, pri, pri_xyxy,
-                                IOU_THRESHOLD, NEG_POS_RATIO, norm_mode, want_grads=want)
+                                IOU_THRESHOLD, NEG_POS_RATIO, norm_mode, want_grads=want, **kw)
         ctx.dloc, ctx.dconf = out["dloc"], out["dconf"]
         global last_match
         last_match = dict(obj=out["obj"], cls=out["cls"], n_pos=out["losses"][2])
+        if ignore is not None:
+            last_match["ignored"] = out["ign"]
         losses = out["losses"]
         return losses[0].clone(), losses[1].clone(), losses[2].clone()
 
     @staticmethod
     def backward(ctx, g_loc, g_conf, _g_npos):
         # loc_loss depends on loc only, conf_loss on conf only
-        return ctx.dloc * g_loc, ctx.dconf * g_conf, None, None, None, None
+        return ctx.dloc * g_loc, ctx.dconf * g_conf, None, None, None, None, None
 
 
 def _image_starts(start, dev: torch.device) -> torch.Tensor:
@@ -88,13 +93,34 @@ def _pack_targets(tr_classes: Sequence[torch.Tensor], tr_bboxs: Sequence[torch.T
     return gt, cls, _image_starts(start, dev)
 
 
-def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = False):
+def _pack_ignore(ignore_bboxs, dev: torch.device):
+    """(boxes (n_ign, 4) f32, starts (bs + 1,) int32) on `dev` from a list of (m_i, 4) tensors, one per image, m_i >= 0."""
+    parts = [torch.as_tensor(b, dtype=torch.float32).reshape(-1, 4) for b in ignore_bboxs]
+    start = [0]
+    for b in parts:
+        start.append(start[-1] + int(b.shape[0]))
+    if start[-1] == 0:
+        boxes = torch.zeros((0, 4), dtype=torch.float32, device=dev)
+    else:
+        boxes = torch.cat([b.to(dev) for b in parts]).contiguous()
+    return boxes, _image_starts(start, dev)
+
+
+def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = False, ignore_bboxs=None, ignore_threshold: float = 0.5,
+        ignore_overlap: str = "iou"):
     """outputs = (loc (bs,8732,4), conf (bs,8732,C)); tr_classes: list of (n_i,) float tensors with values
     0..C-2 (C = conf.shape[-1] = foreground classes + background, 21 for VOC; background = C-1); tr_bboxs: list of
     (n_i,4) xyxy fractional boxes.  Returns (loc_loss, conf_loss) as 0-dim tensors
     that support `+`, `.item()` and `.backward()` (train_function.py:82-94).
     with_n_pos: also return this call's number of positive priors (0-dim device tensor) -- the data-parallel step
-    (ddp.py) takes it from here, not from the module global `last_match`, so two models / threads cannot mix theirs up."""
+    (ddp.py) takes it from here, not from the module global `last_match`, so two models / threads cannot mix theirs up.
+    ignore_bboxs: a list of (m_i,4) fractional xyxy boxes per image, m_i >= 0 (VOC `difficult` objects, COCO crowd regions).  A
+    prior that is not positive and overlaps one of its image's ignore boxes by >= ignore_threshold -- ignore_overlap "iou", or "ioa" =
+    intersection over the prior's area, the crowd rule -- is neither mined as a hard negative nor given a gradient; matching is
+    unchanged.  `last_match` then has "ignored" (bs,P) uint8."""
+    ops.ignore_overlap_mode(ignore_overlap)
+    if ignore_bboxs is not None and len(ignore_bboxs) != len(tr_bboxs):
+        raise ValueError(f"ssd(): ignore_bboxs has {len(ignore_bboxs)} entries for {len(tr_bboxs)} images")
     loc, conf = outputs
     if loc.dim() != 3 or conf.dim() != 3 or loc.shape[0] != len(tr_bboxs) or loc.shape[1] not in (ancs_xywh.shape[0], 24564):
         raise ValueError(f"ssd(): outputs {tuple(loc.shape)}, {tuple(conf.shape)} do not match {len(tr_bboxs)} images "
@@ -102,7 +128,10 @@ def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = Fa
     gt, cls, img_start = _pack_targets(tr_classes, tr_bboxs, loc.device)
     if not loc.is_cuda:
         raise RuntimeError("ssd() runs on the gfx950 HIP kernels only (no CPU fallback): outputs must be device tensors")
-    l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode)
+    ignore = None
+    if ignore_bboxs is not None:
+        ignore = _pack_ignore(ignore_bboxs, loc.device) + (float(ignore_threshold), ignore_overlap)
+    l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode, ignore)
     if with_n_pos:
         return l_loc, l_conf, n_pos.detach()
     return l_loc, l_conf

@@ -30,6 +30,13 @@
 //                                64 x C dconf floats leave as ONE flat coalesced stream (consecutive threads, consecutive floats)
 // L2 (one workgroup per image, radix select) does not depend on C and is shared.  C <= 64 keeps L1 / L3 as they are.
 //
+// Ignore regions (ssd_multibox_loss_ignore: VOC `difficult` objects, COCO crowd regions).  L1, L1w and L2 are templates on IGN; the
+// IGN = false instances are the kernels above, unchanged.  With IGN, L1 / L1w stage the image's ignore boxes beside its GT boxes (the
+// first SG in LDS, more from memory) and write one byte per prior: some ignore box overlaps it by >= the threshold (IoU, or
+// intersection over the prior's own area).  L2, which alone knows the positives (forced matches), keeps the byte for non-positives only,
+// gives those priors the mining value 0 where the positives get theirs (the reference's cce1[pos] = 0 becomes cce1[pos | ign] = 0)
+// and leaves their selection bit clear: L3 / L3w, which read nothing but cls and sel, then skip them -- the same kernels for both entries.
+//
 // Class labels index conf rows: every kernel reads them through class_index(), which keeps any value (negative, >= C - 1, NaN)
 // inside the row.  Labels outside 0 .. C-2 are the caller's error and give unspecified losses, but no access outside the tensors.
 //
@@ -292,6 +299,49 @@ struct ImageArgs {
 
 constexpr int SG = 128;        // GT boxes of an image kept in LDS (more are read from memory: correct, slower)
 
+// Ignore regions of the batch: boxes [ign_start[i], ign_start[i + 1]) belong to image i; ign[bs][P] is the output byte per prior.
+struct IgnArgs {
+    const float* boxes; const int32_t* start; uint8_t* ign;
+    float thr; int mode;                              // mode 0: IoU, 1: intersection over the prior's area
+};
+
+// L1 / L1w with IGN: the first SG ignore boxes of image i into LDS (before the block's barrier)
+__device__ __forceinline__ void stage_ignore(const IgnArgs& g, int i, int tid, f32x4* si_box, float* si_area) {
+    const int s = g.start[i], e = g.start[i + 1];
+    const int ns = e - s < SG ? e - s : SG;
+    for (int t = tid; t < ns; t += 256) {
+        const f32x4 g4 = *reinterpret_cast<const f32x4*>(g.boxes + (size_t)(s + t) * 4);
+        si_box[t] = g4;
+        si_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
+    }
+}
+
+// does some ignore box of image i overlap prior b by >= thr?  The IoU is iou_xyxy's op sequence with the ignore box in the GT box's
+// place; mode 1 divides the same intersection by the prior's own (unclipped) area.  A NaN overlap compares false.
+__device__ __forceinline__ bool ignore_hit(const IgnArgs& g, const f32x4* si_box, const float* si_area, int i, const f32x4 b) {
+    const int s = g.start[i], e = g.start[i + 1];
+    const float area_b = (b[2] - b[0]) * (b[3] - b[1]);
+    bool hit = false;
+    for (int k = s; k < e; ++k) {
+        f32x4 g4;
+        float area_a;
+        if (k - s < SG) {
+            g4 = si_box[k - s];
+            area_a = si_area[k - s];
+        } else {
+            g4 = *reinterpret_cast<const f32x4*>(g.boxes + (size_t)k * 4);
+            area_a = (g4[2] - g4[0]) * (g4[3] - g4[1]);
+        }
+        const float lx = fmaxf(g4[0], b[0]), ly = fmaxf(g4[1], b[1]);
+        const float hx = fminf(g4[2], b[2]), hy = fminf(g4[3], b[3]);
+        const float dx = fmaxf(hx - lx, 0.f), dy = fmaxf(hy - ly, 0.f);
+        const float inter = dx * dy;
+        const float v = g.mode == 0 ? inter / ((area_a + area_b) - inter) : inter / area_b;
+        hit = hit || v >= g.thr;
+    }
+    return hit;
+}
+
 // L1 / L1w: IoU of prior p (lane of a wave owning 64 consecutive priors) against the image's boxes [s, e) -> the prior's best box
 // (first index on ties) in (best, idx); and, per box, the wave's best prior into partv / parti[k][slot]
 __device__ __forceinline__ void match_wave(const ImageArgs& a, const f32x4* sg_box, const float* sg_area, int s, int e, int p, bool live,
@@ -354,11 +404,14 @@ __device__ __forceinline__ float col_wave(const float v[4], int c) {         // 
 }
 
 // L1: grid (ceil(P / 256), bs), 256 threads; a wave owns 64 consecutive priors of image blockIdx.y
-__global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a) {
+template <bool IGN>
+__global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a, const IgnArgs g) {
     extern __shared__ __attribute__((aligned(16))) float stage_all[];       // [4][64 * C] conf rows
     __shared__ f32x4 sg_box[SG];
     __shared__ float sg_area[SG];
     __shared__ int sg_cls[SG];
+    __shared__ f32x4 si_box[IGN ? SG : 1];
+    __shared__ float si_area[IGN ? SG : 1];
     const int i = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = a.img_start[i], e = a.img_start[i + 1];
     const int P = a.P, C = a.C;
@@ -369,6 +422,7 @@ __global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a) {
         sg_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
         sg_cls[t] = class_index(a.gt_cls[s + t], C);
     }
+    if (IGN) stage_ignore(g, i, tid, si_box, si_area);
     const int pb = blockIdx.x * 256 + wave * 64;          // this wave's first prior
     const int rows = P - pb < 64 ? P - pb : 64;           // (<= 0: a wave past the end; it still reports "nothing" for every box)
     float* const st = stage_all + (size_t)wave * 64 * C;
@@ -396,14 +450,18 @@ __global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a) {
         a.cebg[ip] = -((x[c] - m) - logf(se));
         a.bestv[ip] = best;
         a.obj[ip] = idx;
+        if (IGN) g.ign[ip] = ignore_hit(g, si_box, si_area, i, *reinterpret_cast<const f32x4*>(a.pri_xyxy + (size_t)p * 4)) ? 1 : 0;
     }
 }
 
 // L1w (64 < C <= 256): L1 without the row staging; grid (ceil(P / 256), bs), 256 threads, a wave per 64 consecutive priors
-__global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a) {
+template <bool IGN>
+__global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a, const IgnArgs g) {
     __shared__ f32x4 sg_box[SG];
     __shared__ float sg_area[SG];
     __shared__ int sg_cls[SG];
+    __shared__ f32x4 si_box[IGN ? SG : 1];
+    __shared__ float si_area[IGN ? SG : 1];
     const int i = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = a.img_start[i], e = a.img_start[i + 1];
     const int P = a.P, C = a.C;
@@ -414,6 +472,7 @@ __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a)
         sg_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
         sg_cls[t] = class_index(a.gt_cls[s + t], C);
     }
+    if (IGN) stage_ignore(g, i, tid, si_box, si_area);
     __syncthreads();
     const int pb = blockIdx.x * 256 + wave * 64;
     const int rows = P - pb < 64 ? P - pb : 64;
@@ -449,13 +508,16 @@ __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a)
         a.cebg[ip] = ce;
         a.bestv[ip] = best;
         a.obj[ip] = idx;
+        if (IGN) g.ign[ip] = ignore_hit(g, si_box, si_area, i, *reinterpret_cast<const f32x4*>(a.pri_xyxy + (size_t)p * 4)) ? 1 : 0;
     }
 }
 
-// L2: one workgroup of 1024 threads per image
-__global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a) {
+// L2: one workgroup of 1024 threads per image.  IGN: the bytes L1 wrote stay set for non-positives only; those get the mining value 0
+// like the positives and never a selection bit (one bit per prior in LDS behind vals carries that to the last pass).
+template <bool IGN>
+__global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a, const IgnArgs g) {
     constexpr int NW = 16, NT = 1024;
-    extern __shared__ __attribute__((aligned(16))) uint32_t vals[];            // [P] negative CE bits of this image
+    extern __shared__ __attribute__((aligned(16))) uint32_t vals[];            // [P] negative CE bits of this image (IGN: + [ceil(P / 32)] ignored bits)
     __shared__ float fred[3][NW];
     __shared__ int ired[NW];
     __shared__ int hist[256];
@@ -470,6 +532,9 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a) {
         sg_cls[t] = class_index(a.gt_cls[s + t], C);
         sg_box[t] = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
     }
+    uint32_t* const ibits = vals + P;
+    if (IGN)
+        for (int t = tid; t < (P + 31) / 32; t += NT) ibits[t] = 0u;           // (the barrier below orders this before the atomicOr's)
     // ---- best prior of each box: a wave per box over the NPW per-wave results of L1 ----
     for (int k = s + wave; k < e; k += NW) {
         float v = 0.f;
@@ -500,6 +565,7 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a) {
     for (int p0 = tid; p0 < P; p0 += UP * NT) {
         float bv[UP], cev[UP];
         int ob[UP];
+        uint8_t ig[UP];
         f32x4 lc[UP], prr[UP];
 #pragma unroll
         for (int u = 0; u < UP; ++u) {
@@ -508,6 +574,7 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a) {
             bv[u] = a.bestv[ip];
             ob[u] = a.obj[ip];
             cev[u] = a.cebg[ip];
+            ig[u] = IGN ? g.ign[ip] : (uint8_t)0;
             lc[u] = *reinterpret_cast<const f32x4*>(a.loc + ip * 4);
             prr[u] = *reinterpret_cast<const f32x4*>(a.pri + (size_t)(p < P ? p : 0) * 4);
         }
@@ -551,6 +618,14 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a) {
                     }
                     const f32x4 l = lc[u];
                     my_l1 += (fabsf(l[0] - g[0]) + fabsf(l[1] - g[1])) + (fabsf(l[2] - g[2]) + fabsf(l[3] - g[3]));
+                }
+                if (IGN) {
+                    const bool ignored = !pos && ig[u] != 0;
+                    if (ignored) {
+                        nv = 0.f;
+                        atomicOr(&ibits[p >> 5], 1u << (p & 31));
+                    }
+                    if (pos && ig[u] != 0) g.ign[ip] = 0;       // a positive stays positive inside an ignore box
                 }
                 vals[p] = __float_as_uint(nv > 0.f ? nv : 0.f);      // also maps -0.0 and NaN to +0.0
             }
@@ -662,6 +737,7 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a) {
         uint8_t sl = 0;
         if (u > T) sl = 1;
         else if (u == T) { sl = rank < remaining ? 1 : 0; ++rank; }
+        if (IGN && ((ibits[p >> 5] >> (p & 31)) & 1u)) sl = 0;             // (after the rank: the tie rule counts them as it always did)
         a.sel[(size_t)i * P + p] = sl;
     }
     if (tid == 0) {
@@ -847,11 +923,64 @@ extern "C" size_t ssd_multibox_loss_workspace(int bs, int P, int n_gt) {
     return carve(nullptr, bs, P, n_gt).bytes;
 }
 
-extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
-                                 const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh,
-                                 const float* priors_xyxy, int P, int n_classes, float iou_threshold, int neg_pos_ratio,
-                                 int norm_mode, float* losses, int32_t* obj, int32_t* cls, float* dloc, float* dconf,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+
+// L1 (or L1w) and L2 of the three-launch form; IGN = false is what ssd_multibox_loss has always launched
+template <bool IGN>
+int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, hipStream_t st) {
+    const bool wide_rows = ia.C > 64;               // L1w / L3w: nothing staged per class
+    const size_t l1_lds = wide_rows ? 0 : (size_t)4 * 64 * ia.C * 4;
+    const size_t l2_lds = (size_t)ia.P * 4 + (IGN ? (size_t)ssd_cdiv(ia.P, 32) * 4 : 0);
+    static std::atomic<unsigned long long> raised_l12{0};     // one bit per device (common.h); one word per instance of this template
+    int dev;
+    if ((l1_lds > 48 * 1024 || l2_lds > 48 * 1024) && ssd_attr_needed(raised_l12, dev)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(loss_prior_kernel<IGN>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
+                hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(loss_image_kernel<IGN>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
+                hipSuccess)
+            return SSD_ERR_LAUNCH;
+        ssd_attr_done(raised_l12, dev);
+    }
+    if (wide_rows)
+        hipLaunchKernelGGL(loss_prior_wide_kernel<IGN>, dim3(NB, bs), dim3(256), 0, st, ia, ga);
+    else
+        hipLaunchKernelGGL(loss_prior_kernel<IGN>, dim3(NB, bs), dim3(256), l1_lds, st, ia, ga);
+    SSD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(loss_image_kernel<IGN>, dim3(bs), dim3(1024), l2_lds, st, ia, ga);
+    SSD_CHECK_LAUNCH();
+    return SSD_OK;
+}
+
+// L3 (or L3w): shared by both entries
+int launch_finalize(const FinalArgs& fa, hipStream_t st) {
+    const int NB = ssd_cdiv(fa.P, LB);
+    const bool grads = fa.dloc != nullptr;
+    if (fa.C > 64) {
+        hipLaunchKernelGGL(finalize_wide_kernel, grads ? dim3(ssd_cdiv(fa.P, RW), fa.bs) : dim3(1, 1), dim3(LB), 0, st, fa);
+        SSD_CHECK_LAUNCH();
+        return SSD_OK;
+    }
+    const size_t fin_lds = grads ? (size_t)LB * fa.C * 4 : 0;
+    if (fin_lds > 48 * 1024) {
+        static std::atomic<unsigned long long> raised_fin{0};
+        int dev;
+        if (ssd_attr_needed(raised_fin, dev)) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
+                hipSuccess)
+                return SSD_ERR_LAUNCH;
+            ssd_attr_done(raised_fin, dev);
+        }
+    }
+    hipLaunchKernelGGL(finalize_kernel, grads ? dim3(NB, fa.bs) : dim3(1, 1), dim3(LB), fin_lds, st, fa);
+    SSD_CHECK_LAUNCH();
+    return SSD_OK;
+}
+
+// argument checks common to ssd_multibox_loss and ssd_multibox_loss_ignore
+int check_loss_args(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes, const int32_t* img_start, int bs,
+                    int n_gt, const float* priors_cxcywh, const float* priors_xyxy, int P, int n_classes, int neg_pos_ratio, int norm_mode,
+                    const float* losses, const int32_t* obj, const int32_t* cls, const float* dloc, const float* dconf,
+                    const void* workspace, size_t workspace_bytes) {
     if (!loc || !conf || !gt_boxes || !gt_classes || !img_start || !priors_cxcywh || !priors_xyxy || !losses || !obj ||
         !cls || !workspace)
         return SSD_ERR_NULL;
@@ -863,32 +992,28 @@ extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const floa
         !ssd_aligned16(workspace))
         return SSD_ERR_ALIGN;
     if (workspace_bytes < ssd_multibox_loss_workspace(bs, P, n_gt)) return SSD_ERR_WORKSPACE;
+    return SSD_OK;
+}
+
+}  // namespace
+
+extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                                 const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh,
+                                 const float* priors_xyxy, int P, int n_classes, float iou_threshold, int neg_pos_ratio,
+                                 int norm_mode, float* losses, int32_t* obj, int32_t* cls, float* dloc, float* dconf,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    const int bad = check_loss_args(loc, conf, gt_boxes, gt_classes, img_start, bs, n_gt, priors_cxcywh, priors_xyxy, P, n_classes,
+                                    neg_pos_ratio, norm_mode, losses, obj, cls, dloc, dconf, workspace, workspace_bytes);
+    if (bad != SSD_OK) return bad;
     hipStream_t st = (hipStream_t)stream;
     const LossWs w = carve(workspace, bs, P, n_gt);
     const int NB = ssd_cdiv(P, LB);
-    const bool wide_rows = n_classes > 64;          // L1w / L3w: nothing staged per class
     if (g_loss_form != 0) {
         // L1 wide (a wave per 64 priors), L2 one workgroup per image
-        const size_t l1_lds = wide_rows ? 0 : (size_t)4 * 64 * n_classes * 4, l2_lds = (size_t)P * 4;
-        static std::atomic<unsigned long long> raised_l12{0};     // one bit per device (common.h)
-        int dev;
-        if ((l1_lds > 48 * 1024 || l2_lds > 48 * 1024) && ssd_attr_needed(raised_l12, dev)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(loss_prior_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
-                    hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(loss_image_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
-                    hipSuccess)
-                return SSD_ERR_LAUNCH;
-            ssd_attr_done(raised_l12, dev);
-        }
         ImageArgs ia{loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, w.partv, w.parti, w.bestv, w.neg,
                      w.best_prior, obj, cls, w.sel, w.stats, P, n_classes, neg_pos_ratio, NB * 4, iou_threshold};
-        if (wide_rows)
-            hipLaunchKernelGGL(loss_prior_wide_kernel, dim3(NB, bs), dim3(256), 0, st, ia);
-        else
-            hipLaunchKernelGGL(loss_prior_kernel, dim3(NB, bs), dim3(256), l1_lds, st, ia);
-        SSD_CHECK_LAUNCH();
-        hipLaunchKernelGGL(loss_image_kernel, dim3(bs), dim3(1024), l2_lds, st, ia);
-        SSD_CHECK_LAUNCH();
+        const int rc = launch_prior_image<false>(ia, IgnArgs{nullptr, nullptr, nullptr, 0.f, 0}, bs, NB, st);
+        if (rc != SSD_OK) return rc;
     } else {
         hipLaunchKernelGGL(best_prior_per_gt_kernel, dim3(n_gt), dim3(256), 0, st, gt_boxes, priors_xyxy, P, w.best_prior);
         SSD_CHECK_LAUNCH();
@@ -910,25 +1035,38 @@ extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const floa
         hipLaunchKernelGGL(hard_negative_kernel, dim3(bs), dim3(HB), hn_lds, st, w.neg, w.part, w.sel, w.stats, P, NB, neg_pos_ratio);
         SSD_CHECK_LAUNCH();
     }
-    FinalArgs fa{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode};
-    const bool grads = dloc != nullptr;
-    if (wide_rows) {
-        hipLaunchKernelGGL(finalize_wide_kernel, grads ? dim3(ssd_cdiv(P, RW), bs) : dim3(1, 1), dim3(LB), 0, st, fa);
-        SSD_CHECK_LAUNCH();
-        return SSD_OK;
-    }
-    const size_t fin_lds = grads ? (size_t)LB * n_classes * 4 : 0;
-    if (fin_lds > 48 * 1024) {
-        static std::atomic<unsigned long long> raised_fin{0};
-        int dev;
-        if (ssd_attr_needed(raised_fin, dev)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
-                hipSuccess)
-                return SSD_ERR_LAUNCH;
-            ssd_attr_done(raised_fin, dev);
-        }
-    }
-    hipLaunchKernelGGL(finalize_kernel, grads ? dim3(NB, bs) : dim3(1, 1), dim3(LB), fin_lds, st, fa);
-    SSD_CHECK_LAUNCH();
-    return SSD_OK;
+    return launch_finalize(FinalArgs{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode},
+                           st);
+}
+
+// The loss with ignore regions; always the three-launch form (ssd_tune_set_loss_form does not reach it).  The workspace is the one of
+// ssd_multibox_loss: the ignore byte per prior is the caller's `ign`, nothing else is kept per ignore box.
+extern "C" size_t ssd_multibox_loss_ignore_workspace(int bs, int P, int n_gt, int n_ign) {
+    if (n_ign < 0) return 0;
+    return ssd_multibox_loss_workspace(bs, P, n_gt);
+}
+
+extern "C" int ssd_multibox_loss_ignore(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                                        const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh,
+                                        const float* priors_xyxy, int P, int n_classes, float iou_threshold, int neg_pos_ratio,
+                                        int norm_mode, const float* ign_boxes, const int32_t* ign_start, int n_ign,
+                                        float ignore_threshold, int overlap_mode, float* losses, int32_t* obj, int32_t* cls,
+                                        uint8_t* ign, float* dloc, float* dconf, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!ign_start || !ign || (n_ign > 0 && !ign_boxes)) return SSD_ERR_NULL;
+    const int bad = check_loss_args(loc, conf, gt_boxes, gt_classes, img_start, bs, n_gt, priors_cxcywh, priors_xyxy, P, n_classes,
+                                    neg_pos_ratio, norm_mode, losses, obj, cls, dloc, dconf, workspace, workspace_bytes);
+    if (bad == SSD_ERR_NULL) return bad;               // the header's order: null, shape, alignment, workspace
+    if (n_ign < 0 || (overlap_mode != 0 && overlap_mode != 1)) return SSD_ERR_BAD_SHAPE;
+    if (bad == SSD_ERR_BAD_SHAPE || bad == SSD_ERR_ALIGN) return bad;
+    if (n_ign > 0 && !ssd_aligned16(ign_boxes)) return SSD_ERR_ALIGN;
+    if (bad != SSD_OK) return bad;
+    hipStream_t st = (hipStream_t)stream;
+    const LossWs w = carve(workspace, bs, P, n_gt);
+    const int NB = ssd_cdiv(P, LB);
+    ImageArgs ia{loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, w.partv, w.parti, w.bestv, w.neg,
+                 w.best_prior, obj, cls, w.sel, w.stats, P, n_classes, neg_pos_ratio, NB * 4, iou_threshold};
+    const int rc = launch_prior_image<true>(ia, IgnArgs{ign_boxes, ign_start, ign, ignore_threshold, overlap_mode}, bs, NB, st);
+    if (rc != SSD_OK) return rc;
+    return launch_finalize(FinalArgs{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode},
+                           st);
 }

@@ -593,15 +593,27 @@ class GraphedTrainStep:
     Measured interleaved with the eager step on one device (tools/ab_graph.py, batch 32, f32): eager 20.41 ms, replay with two branches
     20.57, replay on one chain 21.03 -- the step is GPU-bound, so the replay buys HOST time (5.1 -> 0.3 ms per step), not device time.
 
-    `__call__(x, classes, boxes)` -> (loc_sum, conf_sum, n_pos): 0-dim views of a static device tensor holding this rank's
+    max_ignore_per_image (default 0: this object behaves and captures exactly as without it): with a capacity above 0 the step takes
+    ignore regions (`Losses.ssd(ignore_bboxs=...)`: VOC `difficult` objects, COCO crowd regions) as a fourth argument, a list of (m_i, 4)
+    boxes per image or None.  They live in static buffers of capacity x batch rows, staged like the ground truth, their per-image
+    offsets are data, and the captured loss is the entry with ignore regions: any split of at most that many boxes over the images,
+    none at all included, replays without a re-capture.  `ignore_threshold` / `ignore_overlap` (attributes, 0.5 / "iou") are baked
+    in; changing one re-captures.
+
+    `__call__(x, classes, boxes, ignore=None)` -> (loc_sum, conf_sum, n_pos): 0-dim views of a static device tensor holding this rank's
     un-normalised loss sums and positive count (`Losses.ssd(..., norm_mode=1, with_n_pos=True)`), overwritten by the next call."""
 
-    def __init__(self, net, trainer: FlatSGDDataParallel, max_boxes_per_image: int = 8, warmup: int = 2, two_streams: bool = True):
+    def __init__(self, net, trainer: FlatSGDDataParallel, max_boxes_per_image: int = 8, warmup: int = 2, two_streams: bool = True,
+                 max_ignore_per_image: int = 0):
         if trainer.grad_dtype == torch.bfloat16 and trainer.world > 1:       # (before anything below touches the trainer or the net)
             raise ValueError("GraphedTrainStep exchanges the f32 gradient buffer in one all-reduce behind the replay: a trainer built with "
                              "grad_dtype=torch.bfloat16 would silently send f32 -- build it with the f32 default, or step it eagerly")
         self.net, self.trainer = net, trainer
         self.max_per_image, self.warmup = int(max_boxes_per_image), int(warmup)
+        if int(max_ignore_per_image) < 0:
+            raise ValueError("max_ignore_per_image must be >= 0")
+        self.max_ignore_per_image = int(max_ignore_per_image)
+        self.ignore_threshold, self.ignore_overlap = 0.5, "iou"
         self.two_streams = bool(two_streams)
         self.graph = None
         self._sig = None
@@ -623,8 +635,21 @@ class GraphedTrainStep:
         # pinned staging for ground truth that arrives on the host, four steps deep (the host may run that far ahead of the device)
         self._ring = [dict(gt=torch.zeros((cap, 4)).pin_memory(), cls=torch.zeros((cap,)).pin_memory(),
                            start=torch.zeros((bs + 1,), dtype=torch.int32).pin_memory(), done=None) for _ in range(4)]
+        if self.max_ignore_per_image > 0:
+            icap = bs * self.max_ignore_per_image
+            self._static.update(ign=torch.zeros((icap, 4), device=dev), ign_start=torch.zeros((bs + 1,), device=dev, dtype=torch.int32))
+            for slot in self._ring:
+                slot.update(ign=torch.zeros((icap, 4)).pin_memory(), ign_start=torch.zeros((bs + 1,), dtype=torch.int32).pin_memory())
 
-    def _load_batch(self, x, classes, boxes):
+    def _ignore_lists(self, ignore, bs: int):
+        """the call's ignore argument as one (m_i, 4) f32 tensor per image (None: no box anywhere)"""
+        if ignore is None:
+            return [torch.zeros((0, 4))] * bs
+        if len(ignore) != bs:
+            raise ValueError(f"ignore has {len(ignore)} entries for {bs} images")
+        return [torch.as_tensor(b, dtype=torch.float32).reshape(-1, 4) for b in ignore]
+
+    def _load_batch(self, x, classes, boxes, ignore=None):
         S = self._static
         if tuple(x.shape) != tuple(S["x"].shape) or x.dtype != S["x"].dtype:
             raise ValueError(f"graph step built for images {tuple(S['x'].shape)}, got {tuple(x.shape)}")
@@ -634,6 +659,12 @@ class GraphedTrainStep:
         n = sum(counts)
         if n > S["gt"].shape[0]:
             raise ValueError(f"{n} ground-truth boxes in the batch, the graph step holds {S['gt'].shape[0]} (max_boxes_per_image)")
+        if self.max_ignore_per_image > 0:
+            ign = self._ignore_lists(ignore, x.shape[0])
+            icounts = [int(b.shape[0]) for b in ign]
+            m = sum(icounts)
+            if m > S["ign"].shape[0]:
+                raise ValueError(f"{m} ignore boxes in the batch, the graph step holds {S['ign'].shape[0]} (max_ignore_per_image)")
         S["x"].copy_(x, non_blocking=True)
         slot = self._ring[self._ring_pos]
         self._ring_pos = (self._ring_pos + 1) % len(self._ring)
@@ -651,6 +682,17 @@ class GraphedTrainStep:
             S["gt"][:n].copy_(slot["gt"][:n], non_blocking=True)
             S["cls"][:n].copy_(slot["cls"][:n], non_blocking=True)
         S["start"].copy_(st, non_blocking=True)
+        if self.max_ignore_per_image > 0:
+            ist = slot["ign_start"]
+            ist[0] = 0
+            torch.cumsum(torch.tensor(icounts, dtype=torch.int32), 0, out=ist[1:])
+            if m:
+                if all(b.is_cuda for b in ign if b.shape[0]):
+                    torch.cat([b for b in ign if b.shape[0]], out=S["ign"][:m])
+                else:
+                    torch.cat([b.cpu() for b in ign], out=slot["ign"][:m])
+                    S["ign"][:m].copy_(slot["ign"][:m], non_blocking=True)
+            S["ign_start"].copy_(ist, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         slot["done"] = ev
@@ -663,8 +705,12 @@ class GraphedTrainStep:
         P = net._forward_params()
         loc, conf, saved = eng.forward(S["x"], P, save=True)
         pri, pri_xyxy = Losses._priors_on(loc.device, loc.shape[1])
+        kw = {}
+        if self.max_ignore_per_image > 0:
+            kw = dict(ignore_boxes=S["ign"], ignore_start=S["ign_start"], ignore_threshold=self.ignore_threshold,
+                      ignore_overlap=self.ignore_overlap)
         out = ops.multibox_loss(loc, conf, S["gt"], S["cls"], S["start"], pri, pri_xyxy, Losses.IOU_THRESHOLD, Losses.NEG_POS_RATIO, 1,
-                                want_grads=True)
+                                want_grads=True, **kw)
         need = {n: bool(P[n].requires_grad) for n in eng.names}
         eng.backward(saved, out["dloc"], out["dconf"], P, need)
         tr.flat_grad[tr.n:tr.n + 1].copy_(out["losses"][2:3])
@@ -678,14 +724,19 @@ class GraphedTrainStep:
         tr = self.trainer
         eng = self.net._engine
         return tuple((g["lr"], g.get("momentum"), g["weight_decay"], g.get("betas"), g.get("eps")) for g in tr.param_groups) + (
-            tr.optimizer_kind, tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + tr._clip_settings() + tr._sched_settings() + eng.schedule_key()
+            tr.optimizer_kind, tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + tr._clip_settings() + tr._sched_settings() + eng.schedule_key() + (
+            (self.ignore_threshold, self.ignore_overlap) if self.max_ignore_per_image > 0 else ())
 
-    def _eager(self, x, classes, boxes):
+    def _eager(self, x, classes, boxes, ignore=None):
         from . import Losses
         tr = self.trainer
         tr.zero_grad()
         loc, conf = self.net(x)
-        l1, l2, n_pos = Losses.ssd((loc, conf), classes, boxes, norm_mode=1, with_n_pos=True)
+        kw = {}
+        if self.max_ignore_per_image > 0:
+            kw = dict(ignore_bboxs=self._ignore_lists(ignore, x.shape[0]), ignore_threshold=self.ignore_threshold,
+                      ignore_overlap=self.ignore_overlap)
+        l1, l2, n_pos = Losses.ssd((loc, conf), classes, boxes, norm_mode=1, with_n_pos=True, **kw)
         (l1 + l2).backward()
         tr.reduce_and_step(n_pos)
         return l1.detach(), l2.detach(), n_pos
@@ -723,18 +774,20 @@ class GraphedTrainStep:
             eng.overlap_tail = keep_tail
         self._sig = self._signature()
 
-    def __call__(self, x, classes, boxes):
+    def __call__(self, x, classes, boxes, ignore=None):
+        if ignore is not None and self.max_ignore_per_image == 0:
+            raise ValueError("this graph step was built without room for ignore boxes: pass max_ignore_per_image > 0")
         tr = self.trainer
         self._calls += 1
         started = tr.optimizer_kind != "sgd" or tr._has_momentum or all(g["momentum"] == 0 for g in tr.param_groups)
         if self._calls <= self.warmup or not started:      # (Adam's moments start at zero: no first launch of another form to wait for)
-            return self._eager(x, classes, boxes)
+            return self._eager(x, classes, boxes, ignore)
         if self._static is None:
             self._make_static(x)
         tr._clip_prepare()                # (the clip's small buffers come into being here, never inside a capture)
         tr._sched_prepare()               # (and the schedule block, the table of rates and the EMA buffer)
         tr._adam_prepare()                # (and the Adam state block)
-        self._load_batch(x, classes, boxes)
+        self._load_batch(x, classes, boxes, ignore)
         if self.graph is None or self._sig != self._signature():
             self._capture()
         self.graph.replay()

@@ -858,9 +858,28 @@ def heads_gather(dloc: torch.Tensor, dconf: torch.Tensor, ld: int, n: int, hw: i
 
 
 # ---- loss / decode ----------------------------------------------------------------------------
+IGNORE_OVERLAPS = {"iou": 0, "ioa": 1}
+
+
+def ignore_overlap_mode(overlap):
+    """0 / 1 for "iou" / "ioa" (the `overlap_mode` of the C ABI); ValueError for anything else."""
+    try:
+        return IGNORE_OVERLAPS[overlap]
+    except (KeyError, TypeError):
+        raise ValueError(f"ignore_overlap must be 'iou' or 'ioa', not {overlap!r}") from None
+
+
 def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, iou_threshold=0.5,
-                  neg_pos_ratio=3, norm_mode=0, want_grads=True):
-    """-> dict(losses (3,), obj (bs,P) i32, cls (bs,P) i32, dloc, dconf)."""
+                  neg_pos_ratio=3, norm_mode=0, want_grads=True, ignore_boxes=None, ignore_start=None, ignore_threshold=0.5,
+                  ignore_overlap="iou"):
+    """-> dict(losses (3,), obj (bs,P) i32, cls (bs,P) i32, dloc, dconf).
+    ignore_boxes (n_ign, 4) fractional xyxy with ignore_start (bs + 1,) int32 prefix offsets (both on the device; n_ign may be 0):
+    the loss with ignore regions (`ssd_multibox_loss_ignore`) -- a prior that is not positive and overlaps an ignore box of its
+    image by >= ignore_threshold ("iou", or "ioa" = intersection over the prior's area) is neither mined nor given a gradient; the
+    dict then has "ign" (bs,P) uint8 too.  None: the plain entry."""
+    mode = ignore_overlap_mode(ignore_overlap)
+    if (ignore_boxes is None) != (ignore_start is None):
+        raise ValueError("multibox_loss: ignore_boxes and ignore_start go together")
     _req(loc, "loc"); _req(conf, "conf"); _req(gt_boxes, "gt_boxes"); _req(gt_classes, "gt_classes")
     _req(img_start, "img_start", torch.int32); _req(priors_cxcywh, "priors"); _req(priors_xyxy, "priors_xyxy")
     bs, p, ncls = conf.shape
@@ -876,6 +895,21 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
     cls = torch.empty((bs, p), device=dev, dtype=torch.int32)
     dloc = torch.empty_like(loc) if want_grads else None
     dconf = torch.empty_like(conf) if want_grads else None
+    if ignore_boxes is not None:
+        _req(ignore_boxes, "ignore_boxes"); _req(ignore_start, "ignore_start", torch.int32)
+        n_ign = ignore_boxes.shape[0]
+        if tuple(ignore_boxes.shape) != (n_ign, 4) or ignore_start.numel() != bs + 1:
+            raise ValueError("multibox_loss ignore shapes")
+        ws = workspace(lib.ssd_multibox_loss_ignore_workspace(bs, p, n_gt, n_ign), loc.device, "loss")
+        ign = torch.empty((bs, p), device=dev, dtype=torch.uint8)
+        check(lib.ssd_multibox_loss_ignore(loc.data_ptr(), conf.data_ptr(), gt_boxes.data_ptr(), gt_classes.data_ptr(),
+                                           img_start.data_ptr(), bs, n_gt, priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, ncls,
+                                           float(iou_threshold), int(neg_pos_ratio), int(norm_mode),
+                                           ignore_boxes.data_ptr() if n_ign else None, ignore_start.data_ptr(), n_ign,
+                                           float(ignore_threshold), mode, losses.data_ptr(), obj.data_ptr(), cls.data_ptr(),
+                                           ign.data_ptr(), _ptr(dloc), _ptr(dconf), ws.data_ptr(), ws.numel(), _stream()),
+              "multibox_loss_ignore")
+        return dict(losses=losses, obj=obj, cls=cls, dloc=dloc, dconf=dconf, ign=ign)
     check(lib.ssd_multibox_loss(loc.data_ptr(), conf.data_ptr(), gt_boxes.data_ptr(), gt_classes.data_ptr(), img_start.data_ptr(),
                                 bs, n_gt, priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, ncls, float(iou_threshold),
                                 int(neg_pos_ratio), int(norm_mode), losses.data_ptr(), obj.data_ptr(), cls.data_ptr(),
