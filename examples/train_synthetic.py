@@ -43,10 +43,11 @@ def batches(n, bs, dev, seed=0, ignore_difficult=False):
         yield x, [c[~h] for c, h in zip(classes, hard)], [b[~h] for b, h in zip(boxes, hard)], [b[h] for b, h in zip(boxes, hard)]
 
 
-def jpeg_batches(n, bs, decode, seed=0, ignore_difficult=False):
+def jpeg_batches(n, bs, decode, seed=0, ignore_difficult=False, mosaic=0.0):
     """The reference's input side (train.py:29): synthetic JPEG files on disk, `MultiImageMultiBBoxDataset` + `collate_fn` in two
     DataLoader workers.  decode="host": PIL decodes in the workers and pixels travel; decode="device": the files' bytes travel and
-    `inputs.to(device)` decodes them on the GPU (a progressive file among them takes the PIL path inside the same batch)."""
+    `inputs.to(device)` decodes them on the GPU (a progressive file among them takes the PIL path inside the same batch).
+    mosaic > 0: that share of the samples is composed of four files each, resized into the quadrants around a random centre."""
     import tempfile
     from PIL import Image
     from Dataset import MultiImageMultiBBoxDataset, collate_fn
@@ -68,7 +69,7 @@ def jpeg_batches(n, bs, decode, seed=0, ignore_difficult=False):
     # ground truth (as the default False does) and hands them back, carried through the same augmentation, as a fifth list
     difficult = [[int(ignore_difficult and j % 2 == 1) for j in range(len(b))] for b in boxes]
     ds = MultiImageMultiBBoxDataset(paths, boxes, labels, difficult, list(range(len(paths))),
-                                    keep_difficult="ignore" if ignore_difficult else False, decode=decode)
+                                    keep_difficult="ignore" if ignore_difficult else False, decode=decode, mosaic=mosaic)
     dl = torch.utils.data.DataLoader(ds, batch_size=bs, shuffle=True, num_workers=2, collate_fn=collate_fn)
     for inputs, classes, bboxes, _, *ignore in dl:
         yield inputs, classes, bboxes, (ignore[0] if ignore else None)
@@ -98,7 +99,12 @@ def main():
     ap.add_argument("--ignore-difficult", action="store_true",
                     help="mark some objects `difficult` and train with them as ignore regions (Losses.ssd(ignore_bboxs=...)): the priors "
                          "over them are neither positives nor mined as hard negatives")
+    ap.add_argument("--mosaic", type=float, default=0.0, metavar="P",
+                    help="compose a sample with probability P of four files, each resized into one quadrant around a random centre "
+                         "(mosaic augmentation; feeds from files: implies --decode host unless --decode is given)")
     a = ap.parse_args()
+    if a.mosaic > 0 and a.decode is None:
+        a.decode = "host"
     opt_kw = {}
     if a.schedule != "none" or a.warmup_steps or a.ema_decay is not None:
         from objectdetection_ssd_amd.optim import LRSchedule
@@ -132,7 +138,7 @@ def main():
     cnn.train()
     t0 = time.time()
     feed = (batches(a.steps, a.batch, device, ignore_difficult=a.ignore_difficult) if a.decode is None else
-            jpeg_batches(a.steps, a.batch, a.decode, ignore_difficult=a.ignore_difficult))
+            jpeg_batches(a.steps, a.batch, a.decode, ignore_difficult=a.ignore_difficult, mosaic=a.mosaic))
     for count, (inputs, classes, bboxes, ignore) in enumerate(feed):
         raw = inputs
         inputs = inputs.to(device)                            # a RawBatch: upload, JPEG decode, photometric, resize + normalise

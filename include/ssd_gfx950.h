@@ -659,6 +659,31 @@ size_t ssd_preprocess_workspace(const ssd_image_desc* descs_host, int B, int out
 int ssd_preprocess_u8(const uint8_t* arena, const ssd_image_desc* descs_dev, const ssd_image_desc* descs_host, int B,
                       int out_h, int out_w, const float* mean3_host, const float* std3_host, const uint8_t* filler3_host,
                       float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
+/* The same resize / normalise pass into destination RECTANGLES: T tiles compose B output images (mosaic augmentation: four sources
+ * per training image, each resized into one quadrant; a plain image is one full-frame tile).  Tile t is what ssd_preprocess_u8
+ * computes for `src` at the output size (dst_h, dst_w) -- coefficients from crop_w / dst_w and crop_h / dst_h, so a tile never
+ * samples another tile's source -- written to out[out_image][c][dst_top + oy][dst_left + ox].  The tiles of every output image
+ * must cover it exactly once, so every output element is written once and nothing is cleared first.
+ *   reserved[] carries where the tile's scratch lies in the workspace, in the packed order of the tile list:
+ *     reserved[0] = sum of (dst_w + dst_h) over the tiles before t            (its first coefficient row)
+ *     reserved[1] = sum of ceil(crop_h * dst_w * 3 / 256) over the tiles before t   (its intermediate rows, in 256-byte units)
+ *     reserved[2] = 0
+ *   The workspace query reads the geometry only; ssd_preprocess_tiles_u8 refuses descriptors whose reserved[] differ.
+ * Refused before anything is enqueued, the first that applies: SSD_ERR_NULL (a NULL pointer); SSD_ERR_BAD_SHAPE (T, B, out_h or
+ * out_w <= 0, T or B above 65535; out_image outside 0 .. B-1; dst_h or dst_w < 1 or a rectangle that leaves the output; anything
+ * ssd_preprocess_u8 refuses of `src`, its tap bound -- a crop more than 31 times its rectangle, per axis -- taken against
+ * dst_h / dst_w; tiles of one image that overlap, leave a gap, or an image without a tile; reserved[] not as above);
+ * SSD_ERR_ALIGN (workspace not 16-byte aligned); SSD_ERR_WORKSPACE.  The query returns 0 for what would be refused for shape. */
+typedef struct ssd_tile_desc {
+    ssd_image_desc src;            /* source image, canvas, crop window, flip: as for ssd_preprocess_u8 */
+    int32_t out_image;             /* 0 .. B-1 */
+    int32_t dst_top, dst_left, dst_h, dst_w;   /* rectangle of the out_h x out_w output it fills */
+    int32_t reserved[3];
+} ssd_tile_desc;
+size_t ssd_preprocess_tiles_workspace(const ssd_tile_desc* tiles_host, int T, int B, int out_h, int out_w);
+int ssd_preprocess_tiles_u8(const uint8_t* arena, const ssd_tile_desc* tiles_dev, const ssd_tile_desc* tiles_host, int T, int B,
+                            int out_h, int out_w, const float* mean3_host, const float* std3_host, const uint8_t* filler3_host,
+                            float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- baseline JPEG decode into the arena's pixel slots, ahead of the two calls above: what
  * PIL.Image.open(f).convert("RGB") returns (libjpeg's default path), bit for bit -- Huffman decode, dequantise + the "islow"

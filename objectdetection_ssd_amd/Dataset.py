@@ -11,6 +11,10 @@ images travel as raw 8-bit pixels; one kernel set (csrc/preprocess.hip) then pro
 reference, pinned on its own function) and applied by csrc/photometric.hip.  Its arithmetic is torchvision's PIL back end,
 i.e. Pillow's ImageEnhance / blend / HSV conversions, reproduced bit for bit against Pillow; torchvision itself is absent,
 so its four thin wrappers are restated from their documented behaviour (see oracle/ssd_oracle.py).
+
+Beyond the reference: mosaic augmentation (`MultiImageMultiBBoxDataset(mosaic=...)`, `MosaicImage`).  A training image is composed of
+four sources, each with its own plan, resized into the quadrants around a drawn centre; the batch then carries a tile list and the
+same kernel set writes every source into its rectangle (`ssd_preprocess_tiles_u8`).
 """
 from __future__ import annotations
 
@@ -74,15 +78,16 @@ def _iou_1xn(crop: torch.Tensor, boxes: torch.Tensor) -> torch.Tensor:
 
 
 def plan_transform(width: int, height: int, boxes: torch.Tensor, labels: torch.Tensor, photometric: bool = True,
-                   rng=random):
+                   rng=random, expand: bool = True):
     """The draws and box arithmetic of reference Util.py:566-607 `transform` for an image of the given size.
-    Returns (GeomPlan, new_boxes, new_labels); boxes are pixel xyxy float32 like the reference's."""
+    Returns (GeomPlan, new_boxes, new_labels); boxes are pixel xyxy float32 like the reference's.
+    expand=False (mosaic tiles: the mosaic is the zoom-out) leaves out the expand coin and its three draws: the canvas is the source."""
     boxes = boxes.clone().float()
     labels = labels.clone()
     photo = plan_photometric(rng) if photometric else ()
     h, w = height, width
     canvas = (h, w, 0, 0)
-    if rng.random() < .5:                      # expand, Util.py:610-645
+    if expand and rng.random() < .5:           # expand, Util.py:610-645
         scale = rng.uniform(1, 4)
         new_h, new_w = int(scale * h), int(scale * w)
         left = rng.randint(0, new_w - w)
@@ -165,12 +170,17 @@ class RawBatch:
 
     def __init__(self, arena: torch.Tensor, offsets: Sequence[int], plans: Sequence[GeomPlan], size: Tuple[int, int] = (300, 300),
                  headers: Optional[Sequence[Optional["JpegHeader"]]] = None, host_offsets: Optional[Sequence[int]] = None,
-                 device_bytes: Optional[int] = None):
+                 device_bytes: Optional[int] = None, tiles: Optional[Sequence[Tuple[int, int, int, int, int, int]]] = None):
         if arena.dtype != torch.uint8 or arena.dim() != 1 or arena.is_cuda:
             raise ValueError("RawBatch: arena must be a 1-D CPU uint8 tensor")
         if len(offsets) != len(plans) or not plans:
             raise ValueError("RawBatch: one offset and one plan per image, at least one image")
         self.arena, self.offsets, self.plans, self.out_hw = arena, list(offsets), list(plans), tuple(size)
+        # A batch with a `MosaicImage` in it: offsets / plans / headers are per SOURCE image (four of a mosaic, one of a plain entry) and
+        # tiles[k] = (source, out_image, top, left, h, w) is the rectangle of output image `out_image` that source fills, resized to
+        # (h, w); a plain entry is one full-frame tile.  None: one source per output image, the whole frame (every batch without a mosaic).
+        self.tiles = None if tiles is None else [tuple(int(v) for v in t) for t in tiles]
+        self.n_images = len(self.plans) if tiles is None else 1 + max(t[1] for t in self.tiles)
         # A batch that holds JPEG streams (pack_batch): headers[i] is the image's JpegHeader, or None for one that came as pixels.
         # `offsets` are then the pixel slots of the DEVICE arena of `device_bytes` bytes; the host arena holds only what exists --
         # the pixels of the host-decoded images, then the entropy-coded data of the others -- at host_offsets[i].
@@ -184,18 +194,19 @@ class RawBatch:
     # what train_function.py reads from `inputs` (`.shape[0]`, `.size(0)`) also works before `.to(device)`
     @property
     def shape(self) -> torch.Size:
-        return torch.Size((len(self.plans), 3) + self.out_hw)
+        return torch.Size((self.n_images, 3) + self.out_hw)
 
     def size(self, dim: Optional[int] = None):
         return self.shape if dim is None else self.shape[dim]
 
     def __len__(self) -> int:
-        return len(self.plans)
+        return self.n_images
 
     def pin_memory(self) -> "RawBatch":          # DataLoader(pin_memory=True) calls this in its pinning thread (main process)
         if self.headers is None:
-            return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw)
-        return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw, self.headers, self.host_offsets, self.device_bytes)
+            return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw, tiles=self.tiles)
+        return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw, self.headers, self.host_offsets, self.device_bytes,
+                        self.tiles)
 
     def cuda(self, device=None) -> torch.Tensor:
         return self.to(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
@@ -225,7 +236,13 @@ class RawBatch:
                         photo[i].alpha[k] = float(factor)
                         photo[i].hue_delta[k] = (int(factor * 255) & 0xFF) if kind == 3 else 0
                 ops.photometric_u8(arena, descs, photo)
-            return ops.preprocess_u8(arena, descs, self.out_hw, MEAN, STD, FILLER_U8)
+            if self.tiles is None:
+                return ops.preprocess_u8(arena, descs, self.out_hw, MEAN, STD, FILLER_U8)
+            tiles = (_lib.TileDesc * len(self.tiles))()
+            for t, (src, image, top, left, h, w) in zip(tiles, self.tiles):
+                t.src = descs[src]
+                t.out_image, t.dst_top, t.dst_left, t.dst_h, t.dst_w = image, top, left, h, w
+            return ops.preprocess_tiles_u8(arena, tiles, self.n_images, self.out_hw, MEAN, STD, FILLER_U8)
 
     def _upload_and_decode(self, host: torch.Tensor, device) -> torch.Tensor:
         """The device arena of a batch with JPEG streams: upload what exists, then decode every stream into its pixel slot
@@ -258,7 +275,11 @@ class RawBatch:
 def pack_batch(images: Sequence, plans: Optional[Sequence[GeomPlan]] = None, size: Tuple[int, int] = (300, 300)) -> RawBatch:
     """images: HWC uint8 RGB arrays / tensors / PIL images of any sizes -> RawBatch (host only; safe in a DataLoader worker).
     An entry may also be an `EncodedImage`, or the `bytes` of an image file: a baseline JPEG `parse_jpeg` accepts stays
-    compressed and is decoded on the device by `.to(device)`; any other file is decoded here with PIL."""
+    compressed and is decoded on the device by `.to(device)`; any other file is decoded here with PIL.
+    An entry may be a `MosaicImage` too (its `out_hw` must be `size`; `plans[i]` is not read: its sources carry theirs): every source
+    gets a pixel slot, the batch a tile list (`RawBatch.tiles`), and a plain entry beside it is one full-frame tile."""
+    if any(isinstance(im, MosaicImage) for im in images):
+        return _pack_tiles(images, plans, size)
     items = []                                   # per image: pixels (ndarray) or an EncodedImage
     for im in images:
         if isinstance(im, (bytes, bytearray, memoryview)):
@@ -275,9 +296,10 @@ def pack_batch(images: Sequence, plans: Optional[Sequence[GeomPlan]] = None, siz
     if not items:
         raise ValueError("empty batch")
     hw = [(a.header.height, a.header.width) if isinstance(a, EncodedImage) else a.shape[:2] for a in items]
-    plans = [identity_plan(h, w) for h, w in hw] if plans is None else list(plans)
+    plans = [None] * len(items) if plans is None else list(plans)
     if len(plans) != len(items):
         raise ValueError("one plan per image")
+    plans = [identity_plan(h, w) if p is None else p for p, (h, w) in zip(plans, hw)]
     for p, (h, w) in zip(plans, hw):
         if (p.src_h, p.src_w) != (h, w):
             raise ValueError("plan does not belong to this image")
@@ -314,6 +336,37 @@ def pack_batch(images: Sequence, plans: Optional[Sequence[GeomPlan]] = None, siz
                     total + stream_bytes)
 
 
+TILE_MAX_SCALE = 31                          # csrc/preprocess.hip: at most 63 taps = 2 * ceil(crop / rectangle) + 1, per axis
+
+
+def _pack_tiles(images: Sequence, plans: Optional[Sequence[Optional[GeomPlan]]], size: Tuple[int, int]) -> RawBatch:
+    """`pack_batch` of a batch that holds a `MosaicImage`: the sources of all entries packed as a plain batch, and the tile list."""
+    if plans is not None and len(plans) != len(images):
+        raise ValueError("one plan per image")
+    sources, src_plans, tiles = [], [], []
+    for i, im in enumerate(images):
+        if isinstance(im, MosaicImage):
+            if tuple(im.out_hw) != tuple(size):
+                raise ValueError(f"MosaicImage composed for {tuple(im.out_hw)} in a batch of size {tuple(size)}")
+            for src, (top, left, h, w) in zip(im.sources, im.rects):
+                tiles.append((len(sources), i, top, left, h, w))
+                sources.append(src.pixels if isinstance(src, RawImage) else src)
+                src_plans.append(src.plan)
+        else:
+            tiles.append((len(sources), i, 0, 0, size[0], size[1]))
+            sources.append(im)
+            src_plans.append(None if plans is None else plans[i])
+    rb = pack_batch(sources, src_plans, size)
+    for src, i, _, _, h, w in tiles:
+        ch, cw = rb.plans[src].crop[2:]
+        if ch > TILE_MAX_SCALE * h or cw > TILE_MAX_SCALE * w:
+            raise ValueError(f"image {i}: a {ch} x {cw} crop into a {h} x {w} rectangle is beyond the resize's bound of "
+                             f"{TILE_MAX_SCALE} source pixels per output pixel (63 taps)")
+    if rb.headers is None:
+        return RawBatch(rb.arena, rb.offsets, rb.plans, size, tiles=tiles)
+    return RawBatch(rb.arena, rb.offsets, rb.plans, size, rb.headers, rb.host_offsets, rb.device_bytes, tiles)
+
+
 def preprocess_batch(images: Sequence, plans: Optional[Sequence[GeomPlan]] = None, size: Tuple[int, int] = (300, 300),
                      device=None) -> torch.Tensor:
     """images: HWC uint8 RGB arrays / tensors / PIL images of any sizes -> (B,3,H,W) float32 on the GPU
@@ -331,10 +384,13 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
     own line train_function.py:61, main process) makes the normalised device tensor.
     keep_difficult: False (the reference's default: difficult objects are dropped), True (kept as ground truth), or "ignore":
     dropped from the ground truth as with False -- same draws, same four items -- and returned as a fifth item `ignore_bbox`
-    (m, 4), carried through the sample's plan by `map_regions` and standardised like the boxes, for `Losses.ssd(ignore_bboxs=...)`."""
+    (m, 4), carried through the sample's plan by `map_regions` and standardised like the boxes, for `Losses.ssd(ignore_bboxs=...)`.
+    mosaic (pass it and its companions by keyword; `decode` stays the last parameter): the probability that a training sample is a
+    `MosaicImage` of four files (see `_mosaic`).  The default 0.0 makes not one extra draw: the samples are exactly those without it."""
 
     def __init__(self, all_images, all_multi_bboxes, all_multi_labels, all_difficulties, all_indices, isTest=False,
-                 keep_difficult=False, decode="host"):
+                 keep_difficult=False, mosaic: float = 0.0, mosaic_center=(0.25, 0.75), mosaic_min_box: float = 2.0,
+                 mosaic_size=(300, 300), decode="host"):
         if decode not in ("host", "device"):
             raise ValueError("decode must be 'host' (PIL in the worker) or 'device' (baseline JPEG streams decoded on the GPU)")
         self.decode = decode
@@ -345,13 +401,24 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
         self.all_difficulties = [torch.tensor(i) for i in all_difficulties]
         self.keep_difficult = keep_difficult
         self.all_indices = all_indices
+        # mosaic (training samples only): with probability `mosaic` a sample is composed of itself and three random partners around a
+        # centre drawn in mosaic_center = (lo, hi) fractions of the mosaic_size = (H, W) frame; 0.0 draws nothing and changes nothing
+        self.mosaic, self.mosaic_center, self.mosaic_min_box = float(mosaic), tuple(mosaic_center), float(mosaic_min_box)
+        self.mosaic_size = tuple(int(v) for v in mosaic_size)
+        lo, hi = self.mosaic_center
+        if not 0.0 <= self.mosaic <= 1.0:
+            raise ValueError("mosaic is a probability")
+        if not 0 < lo <= hi < 1:
+            raise ValueError("mosaic_center: 0 < lo <= hi < 1")
+        if any(int(lo * n) < 1 or int(hi * n) > n - 1 for n in self.mosaic_size):
+            raise ValueError("mosaic_center leaves a tile of mosaic_size without a pixel")
 
     def __len__(self):
         return len(self.images_list)
 
-    def __getitem__(self, index):
+    def _load(self, index):
+        """(RawImage or EncodedImage, classes, boxes, ignore boxes or None) of one file, before any draw"""
         from PIL import Image
-        from .Util import transform
         if self.decode == "device":               # the file's bytes; anything but a baseline JPEG in scope is decoded here, as below
             with open(self.images_list[index], "rb") as f:
                 image = EncodedImage.of(f.read())
@@ -366,6 +433,13 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
             if as_ignore:
                 ignore = bboxes[~keep]
             bboxes, c = bboxes[keep], c[keep]
+        return image, c, bboxes, ignore
+
+    def __getitem__(self, index):
+        from .Util import transform
+        if self.isTest is False and self.mosaic > 0.0 and random.random() < self.mosaic:
+            return self._mosaic(index)
+        image, c, bboxes, ignore = self._load(index)
         if self.isTest is False:
             image, bboxes, c = transform(image, bboxes, c)            # Dataset.py:33
         w, h = image.size                                             # Dataset.py:35
@@ -374,6 +448,48 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
             return image, c, standardized_bbox, self.all_indices[index]
         ignore_bbox = map_regions(image.plan, ignore) / torch.FloatTensor([w, h, w, h]).unsqueeze(0)
         return image, c, standardized_bbox, self.all_indices[index], ignore_bbox
+
+    def _mosaic(self, index):
+        """The sample `index` as a mosaic.  Draws, in this order: three partners, `randrange(len(self))` each; the centre,
+        cx = randint(int(lo*W), int(hi*W)) and cy likewise with H; then for the sample itself and the partners -- the tiles top-left,
+        top-right, bottom-left, bottom-right -- the plan of `plan_transform(expand=False)`, the photometric draw included.  A tile's
+        boxes, in its plan's crop frame, are divided by the crop size, clamped to [0, 1] and carried into their rectangle; of all tiles'
+        boxes those at least `mosaic_min_box` output pixels wide and high are kept (the largest one if none is: `Losses.ssd` needs a
+        box per image).  Ignore boxes go through `map_regions` and the same mapping; only those without area are dropped."""
+        H, W = self.mosaic_size
+        lo, hi = self.mosaic_center
+        members = [index] + [random.randrange(len(self)) for _ in range(3)]
+        cx = random.randint(int(lo * W), int(hi * W))
+        cy = random.randint(int(lo * H), int(hi * H))
+        rects = ((0, 0, cy, cx), (0, cx, cy, W - cx), (cy, 0, H - cy, cx), (cy, cx, H - cy, W - cx))
+        frame = torch.FloatTensor([W, H, W, H])
+        sources, boxes, classes, ignores = [], [], [], []
+        for i, (top, left, h, w) in zip(members, rects):
+            image, c, bboxes, ignore = self._load(i)
+            if isinstance(image, EncodedImage):
+                plan, bboxes, c = plan_transform(image.header.width, image.header.height, bboxes, c, expand=False)
+                sources.append(EncodedImage(image.data, image.header, plan))
+            else:
+                plan, bboxes, c = plan_transform(image.pixels.shape[1], image.pixels.shape[0], bboxes, c, expand=False)
+                sources.append(RawImage(image.pixels, plan))
+            cw, ch = plan.size
+
+            def carry(b):
+                s = torch.clamp(b / torch.FloatTensor([cw, ch, cw, ch]), 0, 1)
+                return (s * torch.FloatTensor([w, h, w, h]) + torch.FloatTensor([left, top, left, top])) / frame
+            boxes.append(carry(bboxes)); classes.append(c)
+            if ignore is not None:
+                ignores.append(carry(map_regions(plan, ignore)))
+        boxes, classes = torch.cat(boxes), torch.cat(classes)
+        keep = ((boxes[:, 2] - boxes[:, 0]) * W >= self.mosaic_min_box) & ((boxes[:, 3] - boxes[:, 1]) * H >= self.mosaic_min_box)
+        if not keep.any():
+            keep[torch.argmax((boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1]))] = True
+        image = MosaicImage(tuple(sources), rects, (H, W))
+        if not ignores:
+            return image, classes[keep], boxes[keep], self.all_indices[index]
+        ignores = torch.cat(ignores)
+        ignores = ignores[(ignores[:, 2] > ignores[:, 0]) & (ignores[:, 3] > ignores[:, 1])]
+        return image, classes[keep], boxes[keep], self.all_indices[index], ignores
 
 
 @dataclass
@@ -537,6 +653,20 @@ def parse_jpeg(data: bytes) -> Optional[JpegHeader]:
 
 
 @dataclass
+class MosaicImage:
+    """A training image composed of four sources (Bochkovskiy et al. 2020, section 3.3): sources[k] -- a `RawImage` or `EncodedImage`
+    with the plan drawn for it -- is resized into rects[k] = (top, left, h, w) of an out_hw = (H, W) frame; the four rectangles, in the
+    order top-left, top-right, bottom-left, bottom-right, meet at the drawn centre and tile the frame.  `.size` = (W, H)."""
+    sources: Tuple
+    rects: Tuple[Tuple[int, int, int, int], ...]
+    out_hw: Tuple[int, int]
+
+    @property
+    def size(self) -> Tuple[int, int]:
+        return self.out_hw[1], self.out_hw[0]
+
+
+@dataclass
 class EncodedImage:
     """A sibling of `RawImage` for `decode="device"`: the bytes of a baseline JPEG file, its parsed header and the geometry /
     photometric plan drawn for it (a plan needs only the header's width and height).  The pixels first exist on the GPU."""
@@ -562,13 +692,15 @@ class EncodedImage:
 def collate_fn(batch):
     """Reference Dataset.py:41-53: (images, classes, boxes, indices) of a list of samples.  Host work only (it runs in the
     DataLoader's workers): RawImage entries are packed into one `RawBatch`; already-normalised tensors are stacked like the
-    reference does.  Samples of `keep_difficult="ignore"` carry a fifth item: their ignore boxes come back as a fifth list."""
+    reference does.  Samples of `keep_difficult="ignore"` carry a fifth item: their ignore boxes come back as a fifth list.
+    `MosaicImage` entries (a dataset with `mosaic` > 0) may stand beside plain ones: the batch then carries a tile list."""
     images, classes, boxes, indices = [], [], [], []
     for b in batch:
         images.append(b[0]); classes.append(b[1]); boxes.append(b[2]); indices.append(b[3])
     ignore = [b[4] for b in batch] if batch and len(batch[0]) == 5 else None
-    if images and isinstance(images[0], (RawImage, EncodedImage)):
-        x = pack_batch([r.pixels if isinstance(r, RawImage) else r for r in images], [r.plan for r in images])
+    if images and isinstance(images[0], (RawImage, EncodedImage, MosaicImage)):
+        x = pack_batch([r.pixels if isinstance(r, RawImage) else r for r in images],
+                       [None if isinstance(r, MosaicImage) else r.plan for r in images])
     else:
         x = torch.stack(images, dim=0)
     if ignore is not None:

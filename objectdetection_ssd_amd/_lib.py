@@ -26,6 +26,12 @@ class ImageDesc(C.Structure):
         "flip", "reserved")]
 
 
+class TileDesc(C.Structure):
+    """struct ssd_tile_desc"""
+    _fields_ = [("src", ImageDesc)] + [(n, C.c_int32) for n in ("out_image", "dst_top", "dst_left", "dst_h", "dst_w")] + \
+               [("reserved", C.c_int32 * 3)]
+
+
 class WeightJob(C.Structure):
     """struct ssd_weight_job"""
     _fields_ = [("w0", C.c_void_p), ("w1", C.c_void_p), ("out_fwd", C.c_void_p), ("out_bwd", C.c_void_p)] + [(n, C.c_int32) for n in (
@@ -82,6 +88,8 @@ SIGNATURES = {
     "ssd_photometric_u8": (_I, [_P, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "ssd_preprocess_workspace": (_Z, [_P, _I, _I, _I]),
     "ssd_preprocess_u8": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "ssd_preprocess_tiles_workspace": (_Z, [_P, _I, _I, _I, _I]),
+    "ssd_preprocess_tiles_u8": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_jpeg_decode_workspace": (_Z, [_P, _I]),
     "ssd_jpeg_decode_u8": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _P, _P, _Z, _I, _P]),
     "ssd_jpeg_decode_split_workspace": (_Z, [_P, _I, _P, _I, _I]),

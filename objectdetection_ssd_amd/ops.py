@@ -1349,6 +1349,43 @@ def preprocess_u8(arena: torch.Tensor, descs, out_hw=(300, 300), mean=(0.485, 0.
     return out
 
 
+def preprocess_tiles_u8(arena: torch.Tensor, tiles, B: int, out_hw=(300, 300), mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
+                        filler=(123, 116, 103)) -> torch.Tensor:
+    """The resize / normalise pass into destination rectangles (include/ssd_gfx950.h ssd_preprocess_tiles_u8).  arena: uint8 device
+    tensor holding the HWC RGB sources; tiles: ctypes array of _lib.TileDesc (host) whose rectangles cover each of the B output images
+    exactly once; their reserved[] (where each tile's scratch lies in the workspace) are filled here.  -> (B,3,out_h,out_w) float32."""
+    import numpy as np
+    _req(arena, "arena", torch.uint8)
+    T = len(tiles)
+    oh, ow = out_hw
+    # struct ssd_tile_desc as a numpy record; a view: the reserved[] written below are the descriptors' own
+    v = np.frombuffer(tiles, dtype=np.dtype([("src_offset", "<i8")] + [("src_" + n[0] if n[0] == "reserved" else n[0], "<i4") for n in
+                                                                       _lib.ImageDesc._fields_[1:] + _lib.TileDesc._fields_[1:-1]] +
+                                            [("reserved", "<i4", (3,))]))
+    if ((v["src_offset"] < 0) | (v["src_offset"] + v["src_h"].astype(np.int64) * v["src_w"] * 3 > arena.numel())).any():
+        raise ValueError("image descriptor points outside the arena")
+    dst_w, dst_h = np.maximum(v["dst_w"], 0).astype(np.int64), np.maximum(v["dst_h"], 0).astype(np.int64)
+    rows = np.cumsum(dst_w + dst_h)
+    units = np.cumsum((np.maximum(v["crop_h"], 0) * dst_w * 3 + 255) // 256)
+    if rows[-1] >= 1 << 31 or units[-1] >= 1 << 31:
+        raise ValueError("preprocess_tiles_u8: the tiles' scratch rows do not fit 32-bit offsets")
+    v["reserved"][:, 0] = rows - (dst_w + dst_h)
+    v["reserved"][:, 1] = units - (np.maximum(v["crop_h"], 0) * dst_w * 3 + 255) // 256
+    v["reserved"][:, 2] = 0
+    lib = _lib.load()
+    nbytes = lib.ssd_preprocess_tiles_workspace(C.byref(tiles), T, B, oh, ow)
+    if nbytes == 0:
+        raise ValueError("preprocess_tiles_u8: bad geometry (a window outside its canvas, an empty image or rectangle, a crop more than "
+                         "31 times its rectangle, or rectangles that do not cover every output image exactly once)")
+    ws = workspace(nbytes, arena.device, "pre_tiles")
+    tiles_dev = torch.from_numpy(np.frombuffer(bytes(tiles), dtype=np.uint8).copy()).to(arena.device, non_blocking=False)
+    out = torch.empty((B, 3, oh, ow), device=arena.device, dtype=torch.float32)
+    m = (C.c_float * 3)(*mean); s_ = (C.c_float * 3)(*std); f = (C.c_uint8 * 3)(*filler)
+    check(lib.ssd_preprocess_tiles_u8(arena.data_ptr(), tiles_dev.data_ptr(), C.byref(tiles), T, B, oh, ow, C.addressof(m), C.addressof(s_),
+                                      C.addressof(f), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "preprocess_tiles_u8")
+    return out
+
+
 def clock_probe(device) -> torch.Tensor:
     """Enqueue a clock probe on the current stream; returns the (16, 2) int64 tensor it fills (counter, 100 MHz ticks per XCC)."""
     out = torch.zeros((16, 2), device=device, dtype=torch.int64)
