@@ -43,11 +43,12 @@ def batches(n, bs, dev, seed=0, ignore_difficult=False):
         yield x, [c[~h] for c, h in zip(classes, hard)], [b[~h] for b, h in zip(boxes, hard)], [b[h] for b, h in zip(boxes, hard)]
 
 
-def jpeg_batches(n, bs, decode, seed=0, ignore_difficult=False, mosaic=0.0):
+def jpeg_batches(n, bs, decode, seed=0, ignore_difficult=False, mosaic=0.0, affine=0.0):
     """The reference's input side (train.py:29): synthetic JPEG files on disk, `MultiImageMultiBBoxDataset` + `collate_fn` in two
     DataLoader workers.  decode="host": PIL decodes in the workers and pixels travel; decode="device": the files' bytes travel and
     `inputs.to(device)` decodes them on the GPU (a progressive file among them takes the PIL path inside the same batch).
-    mosaic > 0: that share of the samples is composed of four files each, resized into the quadrants around a random centre."""
+    mosaic > 0: that share of the samples is composed of four files each, resized into the quadrants around a random centre.
+    affine > 0: that share of the samples -- plain or mosaic -- is rotated, scaled, sheared and shifted on the device after the resize."""
     import tempfile
     from PIL import Image
     from Dataset import MultiImageMultiBBoxDataset, collate_fn
@@ -69,7 +70,7 @@ def jpeg_batches(n, bs, decode, seed=0, ignore_difficult=False, mosaic=0.0):
     # ground truth (as the default False does) and hands them back, carried through the same augmentation, as a fifth list
     difficult = [[int(ignore_difficult and j % 2 == 1) for j in range(len(b))] for b in boxes]
     ds = MultiImageMultiBBoxDataset(paths, boxes, labels, difficult, list(range(len(paths))),
-                                    keep_difficult="ignore" if ignore_difficult else False, decode=decode, mosaic=mosaic)
+                                    keep_difficult="ignore" if ignore_difficult else False, decode=decode, mosaic=mosaic, affine=affine)
     dl = torch.utils.data.DataLoader(ds, batch_size=bs, shuffle=True, num_workers=2, collate_fn=collate_fn)
     for inputs, classes, bboxes, _, *ignore in dl:
         yield inputs, classes, bboxes, (ignore[0] if ignore else None)
@@ -102,8 +103,11 @@ def main():
     ap.add_argument("--mosaic", type=float, default=0.0, metavar="P",
                     help="compose a sample with probability P of four files, each resized into one quadrant around a random centre "
                          "(mosaic augmentation; feeds from files: implies --decode host unless --decode is given)")
+    ap.add_argument("--affine", type=float, default=0.0, metavar="P",
+                    help="warp a sample with probability P by a random rotation, scale, shear and shift of the 300 x 300 frame (random "
+                         "affine augmentation, after --mosaic where both are given; feeds from files like --mosaic)")
     a = ap.parse_args()
-    if a.mosaic > 0 and a.decode is None:
+    if (a.mosaic > 0 or a.affine > 0) and a.decode is None:
         a.decode = "host"
     opt_kw = {}
     if a.schedule != "none" or a.warmup_steps or a.ema_decay is not None:
@@ -138,10 +142,10 @@ def main():
     cnn.train()
     t0 = time.time()
     feed = (batches(a.steps, a.batch, device, ignore_difficult=a.ignore_difficult) if a.decode is None else
-            jpeg_batches(a.steps, a.batch, a.decode, ignore_difficult=a.ignore_difficult, mosaic=a.mosaic))
+            jpeg_batches(a.steps, a.batch, a.decode, ignore_difficult=a.ignore_difficult, mosaic=a.mosaic, affine=a.affine))
     for count, (inputs, classes, bboxes, ignore) in enumerate(feed):
         raw = inputs
-        inputs = inputs.to(device)                            # a RawBatch: upload, JPEG decode, photometric, resize + normalise
+        inputs = inputs.to(device)                            # a RawBatch: upload, JPEG decode, photometric, resize + normalise, affine warp
         classes = [c.to(device) for c in classes]
         bboxes = [b.to(device) for b in bboxes]
         optimizer.zero_grad()

@@ -684,6 +684,26 @@ size_t ssd_preprocess_tiles_workspace(const ssd_tile_desc* tiles_host, int T, in
 int ssd_preprocess_tiles_u8(const uint8_t* arena, const ssd_tile_desc* tiles_dev, const ssd_tile_desc* tiles_host, int T, int B,
                             int out_h, int out_w, const float* mean3_host, const float* std3_host, const uint8_t* filler3_host,
                             float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
+/* Random affine augmentation of the batch either call above made: out[b] = in[b] warped by the 2x3 matrix m0 .. m5 of image b, which
+ * maps an OUTPUT pixel centre to input coordinates (the inverse of the forward map the host draws).  in / out are (B,3,H,W) float32
+ * and distinct -- a gather, no workspace; mats_dev / mats_host are the same B x 6 float32 coefficients in device / host memory (the
+ * library validates the host copy, the kernel reads the device copy); fill3_host is the NORMALISED filler, per channel
+ * ((float)filler_u8[c] / 255.0f - mean[c]) / std[c] in float32 -- the expression of ssd_preprocess_u8's last pass -- read by value.
+ * Output (ox, oy), all in float32, every operation rounded on its own, in exactly this association:
+ *     fx = (float)ox + 0.5f;  fy = (float)oy + 0.5f
+ *     sx = ((m0*fx + m1*fy) + m2) - 0.5f;   sy = ((m3*fx + m4*fy) + m5) - 0.5f
+ *     live = sx > -1 && sx < (float)W && sy > -1 && sy < (float)H        (float compares: a NaN is not live)
+ *     not live: out[c] = fill[c] for the three channels -- decided BEFORE any float -> int conversion
+ *     x0 = floorf(sx); y0 = floorf(sy); ax = sx - x0; ay = sy - y0
+ *     v00, v01, v10, v11 = in[c] at (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1); a tap outside the image reads fill[c]
+ *     top = v00 + (v01 - v00)*ax;  bot = v10 + (v11 - v10)*ax;  out[c] = top + (bot - top)*ay
+ * So the identity (1,0,0, 0,1,0) is a bit-exact copy, an integer translation an exact shifted copy with filler, a quarter turn of a
+ * square frame an exact permutation, and the result is continuous across the border.
+ * Refused before anything is enqueued, the first that applies: SSD_ERR_NULL (a NULL pointer; `stream` may be NULL);
+ * SSD_ERR_BAD_SHAPE (B, H or W <= 0; B > 65535; H*W >= 2^31; in and out ranges that overlap; a coefficient of mats_host that is
+ * not finite).  Only enqueues on `stream`: no synchronisation. */
+int ssd_affine_warp_f32(const float* in_nchw, float* out_nchw, const float* mats_dev, const float* mats_host, int B, int H, int W,
+                        const float* fill3_host, void* stream);
 
 /* ---- baseline JPEG decode into the arena's pixel slots, ahead of the two calls above: what
  * PIL.Image.open(f).convert("RGB") returns (libjpeg's default path), bit for bit -- Huffman decode, dequantise + the "islow"

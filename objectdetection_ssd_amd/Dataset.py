@@ -14,7 +14,9 @@ so its four thin wrappers are restated from their documented behaviour (see orac
 
 Beyond the reference: mosaic augmentation (`MultiImageMultiBBoxDataset(mosaic=...)`, `MosaicImage`).  A training image is composed of
 four sources, each with its own plan, resized into the quadrants around a drawn centre; the batch then carries a tile list and the
-same kernel set writes every source into its rectangle (`ssd_preprocess_tiles_u8`).
+same kernel set writes every source into its rectangle (`ssd_preprocess_tiles_u8`).  And its usual companion, a random affine warp of
+the formed frame (`affine=...`, `plan_affine`, `affine_boxes`): the host draws the matrix and maps the boxes, the batch carries one matrix
+per warped image (`RawBatch.warps`), and `.to(device)` warps the normalised frames last (csrc/warp.hip, `ssd_affine_warp_f32`).
 """
 from __future__ import annotations
 
@@ -161,6 +163,74 @@ def map_regions(plan: GeomPlan, boxes: torch.Tensor) -> torch.Tensor:
     return boxes
 
 
+def plan_affine(W: int, H: int, rng=random, degrees: float = 10.0, scale=(0.8, 1.25), shear: float = 2.0, translate: float = 0.1):
+    """The six draws of the random affine warp of a W x H frame, in this order: angle = uniform(-degrees, degrees), s = uniform(lo, hi),
+    shx and shy = uniform(-shear, shear) (all angles in degrees), tx = uniform(0.5 - translate, 0.5 + translate) * W and ty likewise
+    with H.  The forward map, in frame pixels and float64, is
+
+        M = T(tx, ty) . Shear(tan shx, tan shy) . s R(angle) . T(-W/2, -H/2)      R = [[cos, -sin], [sin, cos]], Shear = [[1, kx], [ky, 1]]
+
+    evaluated in closed form with scalar arithmetic (A = Shear . sR, then the translation column), and inverted in closed form too.
+    Returns (M, coef): the top two rows of M as six float64 (m00, m01, m02, m10, m11, m12) -- what `affine_boxes` takes -- and the top
+    two rows of M^-1 rounded to float32, the six coefficients of `ops.affine_warp` (output pixel centre -> input coordinates)."""
+    import math
+    lo, hi = scale
+    angle = rng.uniform(-degrees, degrees)
+    s = rng.uniform(lo, hi)
+    shx = rng.uniform(-shear, shear)
+    shy = rng.uniform(-shear, shear)
+    tx = rng.uniform(0.5 - translate, 0.5 + translate) * W
+    ty = rng.uniform(0.5 - translate, 0.5 + translate) * H
+    c, sn = math.cos(math.radians(angle)), math.sin(math.radians(angle))
+    kx, ky = math.tan(math.radians(shx)), math.tan(math.radians(shy))
+    a00, a01 = s * (c + kx * sn), s * (kx * c - sn)
+    a10, a11 = s * (ky * c + sn), s * (c - ky * sn)
+    m02 = tx - (a00 * (W / 2) + a01 * (H / 2))
+    m12 = ty - (a10 * (W / 2) + a11 * (H / 2))
+    det = a00 * a11 - a01 * a10
+    i00, i01, i10, i11 = a11 / det, -a01 / det, -a10 / det, a00 / det
+    inv = (i00, i01, -(i00 * m02 + i01 * m12), i10, i11, -(i10 * m02 + i11 * m12))
+    return (a00, a01, m02, a10, a11, m12), tuple(float(np.float32(v)) for v in inv)
+
+
+def affine_boxes(M, boxes: torch.Tensor, W: int, H: int, min_box: Optional[float] = 2.0, min_visible: float = 0.3):
+    """Standardised xyxy boxes of a W x H frame carried through the forward map M (six float64, see `plan_affine`), in float64: to frame
+    pixels, the four corners through M, their axis-aligned hull, the hull clipped to [0, W] x [0, H], and standardised again as float32.
+    -> (new boxes (n, 4) float32, keep (n,) bool).  A box is kept when its clipped width and height are at least `min_box` pixels and its
+    clipped area at least `min_visible` times the area of its unclipped hull -- and never when nothing of it is left.  min_box=None is
+    the rule of ignore regions: kept by whatever area is left.  The hull of a rotated box is LOOSER than the object it holds (by up to
+    (|sin| + |cos|)^2 in area for a square one): the boxes grow with the angle, which is why the default angle is small."""
+    b = torch.as_tensor(boxes).reshape(-1, 4).numpy().astype(np.float64) * np.array([W, H, W, H], np.float64)
+    m00, m01, m02, m10, m11, m12 = (float(v) for v in M)
+    xs, ys = b[:, [0, 2, 0, 2]], b[:, [1, 1, 3, 3]]                                  # the four corners
+    px = (m00 * xs + m01 * ys) + m02
+    py = (m10 * xs + m11 * ys) + m12
+    hull = np.stack([px.min(1), py.min(1), px.max(1), py.max(1)], 1) if len(b) else np.zeros((0, 4))
+    clip = np.clip(hull, 0.0, np.array([W, H, W, H], np.float64))
+    cw, ch = clip[:, 2] - clip[:, 0], clip[:, 3] - clip[:, 1]
+    keep = (cw > 0) & (ch > 0)
+    if min_box is not None:
+        full = (hull[:, 2] - hull[:, 0]) * (hull[:, 3] - hull[:, 1])
+        keep &= (cw >= min_box) & (ch >= min_box) & (cw * ch >= min_visible * full)
+    new = torch.from_numpy((clip / np.array([W, H, W, H], np.float64)).astype(np.float32))
+    return new, torch.from_numpy(keep)
+
+
+def affine_fill(mean=MEAN, std=STD, filler=FILLER_U8) -> Tuple[float, float, float]:
+    """The filler as the resize's last pass normalises it, in float32: ((float)filler / 255 - mean) / std per channel -- what a tap of
+    `ops.affine_warp` outside the image reads, so a warped frame's border is the colour of an expanded canvas."""
+    return tuple(float((np.float32(f) / np.float32(255.0) - np.float32(m)) / np.float32(s)) for f, m, s in zip(filler, mean, std))
+
+
+def _check_warps(warps: Optional[Sequence], n_images: int) -> Optional[list]:
+    """`RawBatch.warps` of what a caller gave: None where no image is warped, else one slot per output image."""
+    if warps is None or all(w is None for w in warps):
+        return None
+    if len(warps) != n_images or any(w is not None and len(w) != 6 for w in warps):
+        raise ValueError("RawBatch: one warp slot per output image, six coefficients each")
+    return [None if w is None else tuple(float(v) for v in w) for w in warps]
+
+
 class RawBatch:
     """A batch as it leaves a DataLoader worker: the images' 8-bit pixels packed into ONE CPU uint8 tensor plus each image's
     geometry / photometric plan -- plain host data, picklable, no GPU touched (reference train.py:29,40 runs `collate_fn`
@@ -170,7 +240,8 @@ class RawBatch:
 
     def __init__(self, arena: torch.Tensor, offsets: Sequence[int], plans: Sequence[GeomPlan], size: Tuple[int, int] = (300, 300),
                  headers: Optional[Sequence[Optional["JpegHeader"]]] = None, host_offsets: Optional[Sequence[int]] = None,
-                 device_bytes: Optional[int] = None, tiles: Optional[Sequence[Tuple[int, int, int, int, int, int]]] = None):
+                 device_bytes: Optional[int] = None, tiles: Optional[Sequence[Tuple[int, int, int, int, int, int]]] = None,
+                 warps: Optional[Sequence[Optional[Sequence[float]]]] = None):
         if arena.dtype != torch.uint8 or arena.dim() != 1 or arena.is_cuda:
             raise ValueError("RawBatch: arena must be a 1-D CPU uint8 tensor")
         if len(offsets) != len(plans) or not plans:
@@ -181,6 +252,9 @@ class RawBatch:
         # (h, w); a plain entry is one full-frame tile.  None: one source per output image, the whole frame (every batch without a mosaic).
         self.tiles = None if tiles is None else [tuple(int(v) for v in t) for t in tiles]
         self.n_images = len(self.plans) if tiles is None else 1 + max(t[1] for t in self.tiles)
+        # Random affine augmentation: warps[i] is the six float32 coefficients of output image i (`plan_affine`'s second item), or None
+        # for an image that is not warped.  None: no image of the batch is -- the batch never reaches `ops.affine_warp`.
+        self.warps = _check_warps(warps, self.n_images)
         # A batch that holds JPEG streams (pack_batch): headers[i] is the image's JpegHeader, or None for one that came as pixels.
         # `offsets` are then the pixel slots of the DEVICE arena of `device_bytes` bytes; the host arena holds only what exists --
         # the pixels of the host-decoded images, then the entropy-coded data of the others -- at host_offsets[i].
@@ -204,9 +278,9 @@ class RawBatch:
 
     def pin_memory(self) -> "RawBatch":          # DataLoader(pin_memory=True) calls this in its pinning thread (main process)
         if self.headers is None:
-            return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw, tiles=self.tiles)
+            return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw, tiles=self.tiles, warps=self.warps)
         return RawBatch(self.arena.pin_memory(), self.offsets, self.plans, self.out_hw, self.headers, self.host_offsets, self.device_bytes,
-                        self.tiles)
+                        self.tiles, self.warps)
 
     def cuda(self, device=None) -> torch.Tensor:
         return self.to(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
@@ -216,6 +290,14 @@ class RawBatch:
         if device.type != "cuda":
             raise RuntimeError("RawBatch.to(): the resize / normalise kernels run on the gfx950 GPU only (no CPU fallback); "
                                f"got device {device}")
+        x = self._preprocess(device)
+        if self.warps is None:
+            return x
+        mats = np.asarray([(1.0, 0.0, 0.0, 0.0, 1.0, 0.0) if w is None else w for w in self.warps], np.float32)
+        with torch.cuda.device(device):              # the random affine warp comes last, on the composed, normalised frame
+            return ops.affine_warp(x, mats, affine_fill())
+
+    def _preprocess(self, device) -> torch.Tensor:
         descs = (_lib.ImageDesc * len(self.plans))()
         for d, p, o in zip(descs, self.plans, self.offsets):
             d.src_offset, d.src_h, d.src_w = o, p.src_h, p.src_w
@@ -272,14 +354,39 @@ class RawBatch:
         return arena
 
 
-def pack_batch(images: Sequence, plans: Optional[Sequence[GeomPlan]] = None, size: Tuple[int, int] = (300, 300)) -> RawBatch:
+def _batch_warps(images: Sequence, warps: Optional[Sequence], size: Tuple[int, int]) -> Optional[list]:
+    """The six coefficients per output image of a batch, or None where no entry is warped.  warps[i] -- or, where `warps` is None, the
+    entry's own `.warp` -- is (m0 .. m5, H, W): a matrix is in the pixels of the frame it was drawn for, so another batch size is an error."""
+    if warps is not None and len(warps) != len(images):
+        raise ValueError("one warp slot per image")
+    ws = [getattr(im, "warp", None) for im in images] if warps is None else list(warps)
+    for i, w in enumerate(ws):
+        if w is None:
+            continue
+        if len(w) != 8:
+            raise ValueError(f"image {i}: a warp is six coefficients and the (H, W) frame they were drawn for")
+        if (int(w[6]), int(w[7])) != tuple(size):
+            raise ValueError(f"image {i}: warp drawn for a {(int(w[6]), int(w[7]))} frame (affine_size) in a batch of size {tuple(size)}")
+    return [None if w is None else tuple(w[:6]) for w in ws] if any(w is not None for w in ws) else None
+
+
+def pack_batch(images: Sequence, plans: Optional[Sequence[GeomPlan]] = None, size: Tuple[int, int] = (300, 300),
+               warps: Optional[Sequence] = None) -> RawBatch:
     """images: HWC uint8 RGB arrays / tensors / PIL images of any sizes -> RawBatch (host only; safe in a DataLoader worker).
     An entry may also be an `EncodedImage`, or the `bytes` of an image file: a baseline JPEG `parse_jpeg` accepts stays
     compressed and is decoded on the device by `.to(device)`; any other file is decoded here with PIL.
     An entry may be a `MosaicImage` too (its `out_hw` must be `size`; `plans[i]` is not read: its sources carry theirs): every source
-    gets a pixel slot, the batch a tile list (`RawBatch.tiles`), and a plain entry beside it is one full-frame tile."""
-    if any(isinstance(im, MosaicImage) for im in images):
-        return _pack_tiles(images, plans, size)
+    gets a pixel slot, the batch a tile list (`RawBatch.tiles`), and a plain entry beside it is one full-frame tile.
+    warps[i]: the `.warp` of a sample a dataset with `affine` > 0 made (None: not warped), for entries given as bare pixels; left out,
+    the entries' own `.warp` are taken.  They travel as `RawBatch.warps`; one drawn for another frame than `size` raises ValueError."""
+    warps = _batch_warps(images, warps, size)
+    rb = _pack_tiles(images, plans, size) if any(isinstance(im, MosaicImage) for im in images) else _pack_sources(images, plans, size)
+    rb.warps = _check_warps(warps, rb.n_images)
+    return rb
+
+
+def _pack_sources(images: Sequence, plans: Optional[Sequence[GeomPlan]], size: Tuple[int, int]) -> RawBatch:
+    """`pack_batch` of entries that are one source each: the pixel slots, and the streams of the encoded ones behind them."""
     items = []                                   # per image: pixels (ndarray) or an EncodedImage
     for im in images:
         if isinstance(im, (bytes, bytearray, memoryview)):
@@ -356,7 +463,7 @@ def _pack_tiles(images: Sequence, plans: Optional[Sequence[Optional[GeomPlan]]],
             tiles.append((len(sources), i, 0, 0, size[0], size[1]))
             sources.append(im)
             src_plans.append(None if plans is None else plans[i])
-    rb = pack_batch(sources, src_plans, size)
+    rb = _pack_sources(sources, src_plans, size)
     for src, i, _, _, h, w in tiles:
         ch, cw = rb.plans[src].crop[2:]
         if ch > TILE_MAX_SCALE * h or cw > TILE_MAX_SCALE * w:
@@ -386,11 +493,17 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
     dropped from the ground truth as with False -- same draws, same four items -- and returned as a fifth item `ignore_bbox`
     (m, 4), carried through the sample's plan by `map_regions` and standardised like the boxes, for `Losses.ssd(ignore_bboxs=...)`.
     mosaic (pass it and its companions by keyword; `decode` stays the last parameter): the probability that a training sample is a
-    `MosaicImage` of four files (see `_mosaic`).  The default 0.0 makes not one extra draw: the samples are exactly those without it."""
+    `MosaicImage` of four files (see `_mosaic`).  The default 0.0 makes not one extra draw: the samples are exactly those without it.
+    affine (keyword too): the probability that a training sample -- plain or mosaic, once it is formed -- is warped by a random affine
+    map of the `affine_size` = (H, W) frame: rotation within +-affine_degrees, scale in affine_scale = (lo, hi), shear within
+    +-affine_shear degrees per axis, the frame's centre moved to within +-affine_translate of the frame around its middle (see `_affine`,
+    `plan_affine`).  The pixels are warped on the device, after the resize (`RawBatch.to`).  The default 0.0 makes no draw at all."""
 
     def __init__(self, all_images, all_multi_bboxes, all_multi_labels, all_difficulties, all_indices, isTest=False,
                  keep_difficult=False, mosaic: float = 0.0, mosaic_center=(0.25, 0.75), mosaic_min_box: float = 2.0,
-                 mosaic_size=(300, 300), decode="host"):
+                 mosaic_size=(300, 300), affine: float = 0.0, affine_degrees: float = 10.0, affine_scale=(0.8, 1.25),
+                 affine_shear: float = 2.0, affine_translate: float = 0.1, affine_min_box: float = 2.0,
+                 affine_min_visible: float = 0.3, affine_size=(300, 300), decode="host"):
         if decode not in ("host", "device"):
             raise ValueError("decode must be 'host' (PIL in the worker) or 'device' (baseline JPEG streams decoded on the GPU)")
         self.decode = decode
@@ -412,6 +525,23 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
             raise ValueError("mosaic_center: 0 < lo <= hi < 1")
         if any(int(lo * n) < 1 or int(hi * n) > n - 1 for n in self.mosaic_size):
             raise ValueError("mosaic_center leaves a tile of mosaic_size without a pixel")
+        # random affine warp (training samples only): with probability `affine`, after the sample is formed; 0.0 draws nothing
+        self.affine, self.affine_degrees, self.affine_shear = float(affine), float(affine_degrees), float(affine_shear)
+        self.affine_scale, self.affine_translate = tuple(float(v) for v in affine_scale), float(affine_translate)
+        self.affine_min_box, self.affine_min_visible = float(affine_min_box), float(affine_min_visible)
+        self.affine_size = tuple(int(v) for v in affine_size)
+        if not 0.0 <= self.affine <= 1.0:
+            raise ValueError("affine is a probability")
+        if len(self.affine_scale) != 2 or not 0 < self.affine_scale[0] <= self.affine_scale[1]:
+            raise ValueError("affine_scale: 0 < lo <= hi")
+        if not (self.affine_degrees >= 0 and self.affine_translate >= 0 and self.affine_min_box >= 0 and self.affine_min_visible >= 0):
+            raise ValueError("affine_degrees, affine_translate, affine_min_box and affine_min_visible are not negative")
+        if not 0 <= self.affine_shear < 45:
+            raise ValueError("affine_shear: 0 <= degrees < 45 (two shears of 45 degrees make the map singular)")
+        if len(self.affine_size) != 2 or min(self.affine_size) < 1:
+            raise ValueError("affine_size is the (H, W) of the batch")
+        if self.affine > 0 and self.mosaic > 0 and self.affine_size != self.mosaic_size:
+            raise ValueError("affine_size and mosaic_size are both the batch's frame: they must be equal")
 
     def __len__(self):
         return len(self.images_list)
@@ -436,6 +566,33 @@ class MultiImageMultiBBoxDataset(torch.utils.data.Dataset):
         return image, c, bboxes, ignore
 
     def __getitem__(self, index):
+        sample = self._sample(index)
+        if self.isTest is False and self.affine > 0.0 and random.random() < self.affine:
+            return self._affine(sample)
+        return sample
+
+    def _affine(self, sample):
+        """The formed sample -- plain or mosaic -- under a random affine warp.  Six draws (`plan_affine`), always consumed.  The boxes go
+        through `affine_boxes`: in the `affine_size` frame, the hull of the four mapped corners (LOOSER than the object once it is
+        rotated or sheared), clipped to the frame, kept when at least `affine_min_box` pixels wide and high and at least
+        `affine_min_visible` of the hull is still in the frame.  If no box survives the sample comes back as it was: un-warped, its boxes
+        untouched, no matrix (`Losses.ssd` needs a box per image).  Otherwise the image carries the matrix as `.warp` = (m0 .. m5, H, W)
+        and the pixels are warped on the device by `RawBatch.to`.  Ignore boxes take the same hull and clip; only those left without
+        area are dropped."""
+        import dataclasses
+        H, W = self.affine_size
+        M, coef = plan_affine(W, H, random, self.affine_degrees, self.affine_scale, self.affine_shear, self.affine_translate)
+        boxes, keep = affine_boxes(M, sample[2], W, H, self.affine_min_box, self.affine_min_visible)
+        if not keep.any():
+            return sample
+        image = dataclasses.replace(sample[0], warp=coef + (float(H), float(W)))
+        out = (image, sample[1][keep], boxes[keep], sample[3])
+        if len(sample) == 5:
+            ignore, left = affine_boxes(M, sample[4], W, H, None)
+            out += (ignore[left],)
+        return out
+
+    def _sample(self, index):
         from .Util import transform
         if self.isTest is False and self.mosaic > 0.0 and random.random() < self.mosaic:
             return self._mosaic(index)
@@ -498,6 +655,7 @@ class RawImage:
     augmented image, what the reference reads from its PIL image at Dataset.py:35."""
     pixels: np.ndarray
     plan: GeomPlan
+    warp: Optional[Tuple[float, ...]] = None     # random affine warp of the resized frame: (m0 .. m5, H, W), see `_affine`; None: none
 
     @staticmethod
     def of(image) -> "RawImage":
@@ -660,6 +818,7 @@ class MosaicImage:
     sources: Tuple
     rects: Tuple[Tuple[int, int, int, int], ...]
     out_hw: Tuple[int, int]
+    warp: Optional[Tuple[float, ...]] = None     # random affine warp of the composed frame: (m0 .. m5, H, W); None: none
 
     @property
     def size(self) -> Tuple[int, int]:
@@ -673,6 +832,7 @@ class EncodedImage:
     data: bytes
     header: JpegHeader
     plan: GeomPlan
+    warp: Optional[Tuple[float, ...]] = None     # as `RawImage.warp`
 
     @staticmethod
     def of(data: bytes):
@@ -693,14 +853,15 @@ def collate_fn(batch):
     """Reference Dataset.py:41-53: (images, classes, boxes, indices) of a list of samples.  Host work only (it runs in the
     DataLoader's workers): RawImage entries are packed into one `RawBatch`; already-normalised tensors are stacked like the
     reference does.  Samples of `keep_difficult="ignore"` carry a fifth item: their ignore boxes come back as a fifth list.
-    `MosaicImage` entries (a dataset with `mosaic` > 0) may stand beside plain ones: the batch then carries a tile list."""
+    `MosaicImage` entries (a dataset with `mosaic` > 0) may stand beside plain ones: the batch then carries a tile list.
+    The entries' `.warp` (a dataset with `affine` > 0) travel as `RawBatch.warps`."""
     images, classes, boxes, indices = [], [], [], []
     for b in batch:
         images.append(b[0]); classes.append(b[1]); boxes.append(b[2]); indices.append(b[3])
     ignore = [b[4] for b in batch] if batch and len(batch[0]) == 5 else None
     if images and isinstance(images[0], (RawImage, EncodedImage, MosaicImage)):
         x = pack_batch([r.pixels if isinstance(r, RawImage) else r for r in images],
-                       [None if isinstance(r, MosaicImage) else r.plan for r in images])
+                       [None if isinstance(r, MosaicImage) else r.plan for r in images], warps=[r.warp for r in images])
     else:
         x = torch.stack(images, dim=0)
     if ignore is not None:

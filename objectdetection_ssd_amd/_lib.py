@@ -90,6 +90,7 @@ SIGNATURES = {
     "ssd_preprocess_u8": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_preprocess_tiles_workspace": (_Z, [_P, _I, _I, _I, _I]),
     "ssd_preprocess_tiles_u8": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "ssd_affine_warp_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "ssd_jpeg_decode_workspace": (_Z, [_P, _I]),
     "ssd_jpeg_decode_u8": (_I, [_P, _Z, _P, _P, _P, _P, _I, _I, _P, _P, _Z, _I, _P]),
     "ssd_jpeg_decode_split_workspace": (_Z, [_P, _I, _P, _I, _I]),

@@ -1386,6 +1386,37 @@ def preprocess_tiles_u8(arena: torch.Tensor, tiles, B: int, out_hw=(300, 300), m
     return out
 
 
+def affine_warp(x: torch.Tensor, mats, fill) -> torch.Tensor:
+    """Random affine augmentation of a normalised batch (include/ssd_gfx950.h ssd_affine_warp_f32).  x: (B,3,H,W) float32 device tensor;
+    mats: (B,6) float32 host array or CPU tensor, per image the coefficients that map an output pixel centre to input coordinates;
+    fill: the three normalised filler values every tap outside the image reads.  -> a new (B,3,H,W) float32 tensor; only enqueues."""
+    import numpy as np
+    _req(x, "x")
+    if x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+        raise ValueError(f"affine_warp: x must be (B,3,H,W) with B, H, W >= 1, got {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    if torch.is_tensor(mats):
+        if mats.is_cuda:
+            raise ValueError("affine_warp: mats is host data (a CPU tensor or an array): the library validates it before it enqueues")
+        mats = mats.numpy()
+    m = np.asarray(mats)
+    if m.dtype != np.float32 or m.shape != (B, 6):
+        raise ValueError(f"affine_warp: mats must be float32 of shape ({B}, 6), got {m.dtype} {m.shape}")
+    m = np.ascontiguousarray(m)
+    if not np.isfinite(m).all():
+        raise ValueError("affine_warp: a coefficient is not finite")
+    if B > 65535 or H * W >= 1 << 31:
+        raise ValueError("affine_warp: at most 65535 images of fewer than 2^31 pixels")
+    if len(fill) != 3:
+        raise ValueError("affine_warp: fill is three values, one per channel")
+    f = (C.c_float * 3)(*(float(v) for v in fill))
+    mats_dev = torch.from_numpy(m.copy()).to(x.device, non_blocking=True)
+    out = torch.empty_like(x)
+    check(_lib.load().ssd_affine_warp_f32(x.data_ptr(), out.data_ptr(), mats_dev.data_ptr(), m.ctypes.data, B, H, W, C.addressof(f),
+                                          _stream()), "affine_warp")
+    return out
+
+
 def clock_probe(device) -> torch.Tensor:
     """Enqueue a clock probe on the current stream; returns the (16, 2) int64 tensor it fills (counter, 100 MHz ticks per XCC)."""
     out = torch.zeros((16, 2), device=device, dtype=torch.int64)
