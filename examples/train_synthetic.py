@@ -100,6 +100,9 @@ def main():
     ap.add_argument("--ignore-difficult", action="store_true",
                     help="mark some objects `difficult` and train with them as ignore regions (Losses.ssd(ignore_bboxs=...)): the priors "
                          "over them are neither positives nor mined as hard negatives")
+    ap.add_argument("--loc-loss", choices=("l1", "iou", "giou", "diou", "ciou"), default="l1",
+                    help="the localisation term (Losses.ssd(loc_loss=...)): the reference's L1 over the encoded offsets, or a box-overlap "
+                         "term on the decoded prediction")
     ap.add_argument("--mosaic", type=float, default=0.0, metavar="P",
                     help="compose a sample with probability P of four files, each resized into one quadrant around a random centre "
                          "(mosaic augmentation; feeds from files: implies --decode host unless --decode is given)")
@@ -151,9 +154,9 @@ def main():
         optimizer.zero_grad()
         outputs = cnn(inputs)
         if ignore is None:
-            loss1, loss2 = ssd(outputs, classes, bboxes)
+            loss1, loss2 = ssd(outputs, classes, bboxes, loc_loss=a.loc_loss)
         else:
-            loss1, loss2 = ssd(outputs, classes, bboxes, ignore_bboxs=ignore)
+            loss1, loss2 = ssd(outputs, classes, bboxes, loc_loss=a.loc_loss, ignore_bboxs=ignore)
         loss = loss1 + loss2
         loss.backward()
         optimizer.step()

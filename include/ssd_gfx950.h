@@ -493,6 +493,33 @@ int ssd_multibox_loss_ignore(const float* loc, const float* conf, const float* g
                              float ignore_threshold, int overlap_mode, float* losses, int32_t* obj, int32_t* cls,
                              uint8_t* ign, float* dloc, float* dconf, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- MultiBox loss with a choice of localisation term (IoU, GIoU, DIoU, CIoU) ----------
+ * ssd_multibox_loss_ignore's arguments, meaning and status codes, plus int loc_mode: 0 = L1 (the reference's term), 1 = IoU,
+ * 2 = GIoU, 3 = DIoU, 4 = CIoU.  ign_start == NULL means "no ignore regions": ign, ign_boxes, n_ign, ignore_threshold and
+ * overlap_mode are then not looked at (ign and ign_boxes may be NULL) and nothing is written to ign.
+ * For a positive prior (pcx, pcy, pw, ph) with offsets l and matched box g = (gx1, gy1, gx2, gy2), T = log(1000 / 16), eps = 1e-7:
+ *   cx = l0 pw / 10 + pcx, cy = l1 ph / 10 + pcy, w = exp(clamp(l2 / 5, -T, T)) pw, h = exp(clamp(l3 / 5, -T, T)) ph,
+ *   (x1, y1, x2, y2) = (cx - w/2, cy - h/2, cx + w/2, cy + h/2), gw = gx2 - gx1, gh = gy2 - gy1,
+ *   inter = max(min(x2, gx2) - max(x1, gx1), 0) max(min(y2, gy2) - max(y1, gy1), 0), union = w h + gw gh - inter,
+ *   iou = inter / (union + eps), cw = max(x2, gx2) - min(x1, gx1), ch = max(y2, gy2) - min(y1, gy1),
+ *   1: L = 1 - iou                                  2: L = 1 - iou + (cw ch - union) / (cw ch + eps)
+ *   3: L = 1 - iou + rho2 / (cw^2 + ch^2 + eps), rho2 = squared distance of the two centres
+ *   4: L = (3) + alpha v, v = 4 / pi^2 (atan(gw / gh) - atan(w / h))^2, alpha = v / (1 - iou + v + eps), a constant of the gradient
+ *      (needs gh > 0; modes 1 .. 3 take boxes without area).
+ * losses[0] = sum of L over the positives / n_pos (norm_mode 0) or the sum itself (norm_mode 1); dloc is the gradient of that value,
+ * exactly zero at non-positive priors and at a clamped coordinate.  Mode 1 has no gradient where the boxes do not overlap.
+ * Matching, n_pos, the hard-negative quota and selection, ignore regions, losses[1], losses[2] and dconf do not depend on loc_mode.
+ * loc_mode 0 launches the very kernels of ssd_multibox_loss (ign_start NULL) or ssd_multibox_loss_ignore; always the three-launch
+ * form.  The workspace is ssd_multibox_loss's.
+ * Errors: as ssd_multibox_loss_ignore (its ignore rules only with ign_start given); loc_mode outside 0 .. 4 is SSD_ERR_BAD_SHAPE. */
+size_t ssd_multibox_loss_box_workspace(int bs, int P, int n_gt, int n_ign);
+int ssd_multibox_loss_box(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                          const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh, const float* priors_xyxy,
+                          int P, int n_classes, float iou_threshold, int neg_pos_ratio, int norm_mode, const float* ign_boxes,
+                          const int32_t* ign_start, int n_ign, float ignore_threshold, int overlap_mode, int loc_mode,
+                          float* losses, int32_t* obj, int32_t* cls, uint8_t* ign, float* dloc, float* dconf, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- decode + per-class NMS + top-k (Losses.py:11-98 inference; Util.py:86-96) ----------
  * l_ (P,4), c_ (P,n_classes) of ONE image, n_classes = conf width C, 2..256 (background = C-1 is never a detection).
  * Outputs (capacity top_k): boxes (top_k,4) xyxy scaled by (img_w,img_h,img_w,img_h), classes int64 (0..C-2), probs f32,

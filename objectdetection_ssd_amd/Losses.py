@@ -46,14 +46,14 @@ def _priors_on(dev: torch.device, n_priors: int = 8732):
 
 class _MultiBoxLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, loc, conf, gt, gt_cls, img_start, norm_mode, ignore=None):
+    def forward(ctx, loc, conf, gt, gt_cls, img_start, norm_mode, ignore=None, loc_loss="l1"):
         pri, pri_xyxy = _priors_on(loc.device, loc.shape[1])
         want = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         kw = {}
         if ignore is not None:                           # (boxes, starts, threshold, overlap): the entry with ignore regions
             kw = dict(ignore_boxes=ignore[0], ignore_start=ignore[1], ignore_threshold=ignore[2], ignore_overlap=ignore[3])
         out = ops.multibox_loss(loc.detach().contiguous(), conf.detach().contiguous(), gt, gt_cls, img_start, pri, pri_xyxy,
-                                IOU_THRESHOLD, NEG_POS_RATIO, norm_mode, want_grads=want, **kw)
+                                IOU_THRESHOLD, NEG_POS_RATIO, norm_mode, want_grads=want, loc_loss=loc_loss, **kw)
         ctx.dloc, ctx.dconf = out["dloc"], out["dconf"]
         global last_match
         last_match = dict(obj=out["obj"], cls=out["cls"], n_pos=out["losses"][2])
@@ -65,7 +65,7 @@ class _MultiBoxLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loc, g_conf, _g_npos):
         # loc_loss depends on loc only, conf_loss on conf only
-        return ctx.dloc * g_loc, ctx.dconf * g_conf, None, None, None, None, None
+        return ctx.dloc * g_loc, ctx.dconf * g_conf, None, None, None, None, None, None
 
 
 def _image_starts(start, dev: torch.device) -> torch.Tensor:
@@ -106,8 +106,8 @@ def _pack_ignore(ignore_bboxs, dev: torch.device):
     return boxes, _image_starts(start, dev)
 
 
-def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = False, ignore_bboxs=None, ignore_threshold: float = 0.5,
-        ignore_overlap: str = "iou"):
+def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = False, loc_loss: str = "l1", ignore_bboxs=None,
+        ignore_threshold: float = 0.5, ignore_overlap: str = "iou"):
     """outputs = (loc (bs,8732,4), conf (bs,8732,C)); tr_classes: list of (n_i,) float tensors with values
     0..C-2 (C = conf.shape[-1] = foreground classes + background, 21 for VOC; background = C-1); tr_bboxs: list of
     (n_i,4) xyxy fractional boxes.  Returns (loc_loss, conf_loss) as 0-dim tensors
@@ -117,8 +117,15 @@ def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = Fa
     ignore_bboxs: a list of (m_i,4) fractional xyxy boxes per image, m_i >= 0 (VOC `difficult` objects, COCO crowd regions).  A
     prior that is not positive and overlaps one of its image's ignore boxes by >= ignore_threshold -- ignore_overlap "iou", or "ioa" =
     intersection over the prior's area, the crowd rule -- is neither mined as a hard negative nor given a gradient; matching is
-    unchanged.  `last_match` then has "ignored" (bs,P) uint8."""
+    unchanged.  `last_match` then has "ignored" (bs,P) uint8.
+    loc_loss: "l1" (the reference's `nn.L1Loss` over the encoded offsets, the default), or a box-overlap term on the decoded
+    prediction -- "iou", "giou", "diou", "ciou" (torchvision's `*_box_iou_loss` formulas, eps = 1e-7; the exponent of the decoded
+    width / height is clamped to +-log(1000 / 16), a clamped coordinate gets gradient 0).  loc_loss is then the mean over the
+    positives (norm_mode 1: the sum); matching, mining, conf_loss and its gradient are the same.  "ciou" needs ground-truth boxes
+    of positive height; "iou" has no gradient where prediction and box do not overlap.  A weight on the term is the caller's: scale
+    the returned tensor."""
     ops.ignore_overlap_mode(ignore_overlap)
+    ops.loc_loss_mode(loc_loss)
     if ignore_bboxs is not None and len(ignore_bboxs) != len(tr_bboxs):
         raise ValueError(f"ssd(): ignore_bboxs has {len(ignore_bboxs)} entries for {len(tr_bboxs)} images")
     loc, conf = outputs
@@ -131,7 +138,7 @@ def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = Fa
     ignore = None
     if ignore_bboxs is not None:
         ignore = _pack_ignore(ignore_bboxs, loc.device) + (float(ignore_threshold), ignore_overlap)
-    l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode, ignore)
+    l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode, ignore, loc_loss)
     if with_n_pos:
         return l_loc, l_conf, n_pos.detach()
     return l_loc, l_conf

@@ -214,6 +214,9 @@ SIGNATURES = {
     "ssd_multibox_loss_ignore_workspace": (_Z, [_I, _I, _I, _I]),
     "ssd_multibox_loss_ignore": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P, _P,
                                       _P, _Z, _P]),
+    "ssd_multibox_loss_box_workspace": (_Z, [_I, _I, _I, _I]),
+    "ssd_multibox_loss_box": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P,
+                                   _P, _Z, _P]),
     "ssd_decode_nms_workspace": (_Z, [_I, _I]),
     "ssd_decode_nms": (_I, [_P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_decode_nms_batch_workspace": (_Z, [_I, _I, _I]),

@@ -37,6 +37,11 @@
 // gives those priors the mining value 0 where the positives get theirs (the reference's cce1[pos] = 0 becomes cce1[pos | ign] = 0)
 // and leaves their selection bit clear: L3 / L3w, which read nothing but cls and sel, then skip them -- the same kernels for both entries.
 //
+// Box-overlap localisation terms (ssd_multibox_loss_box: IoU, GIoU, DIoU, CIoU on the decoded prediction).  L2, L3 and L3w are templates
+// on BOX; the BOX = false instances are the kernels above, unchanged.  With BOX, L2 sums box_term()'s loss over the positives where it
+// summed the four absolute differences, and L3 / L3w write box_term()'s gradient where they wrote +-1/4: one device function for the
+// decode, the four losses and their gradients, so the two finalize kernels cannot drift apart.
+//
 // Class labels index conf rows: every kernel reads them through class_index(), which keeps any value (negative, >= C - 1, NaN)
 // inside the row.  Labels outside 0 .. C-2 are the caller's error and give unspecified losses, but no access outside the tensors.
 //
@@ -119,6 +124,82 @@ __device__ __forceinline__ void encode_gt(const float* __restrict__ gt, int k, c
     g[1] = (cy - pr[1]) / (pr[3] / 10.f);
     g[2] = logf(w / pr[2]) * 5.f;
     g[3] = logf(h / pr[3]) * 5.f;
+}
+
+// Box-overlap localisation terms (ssd_multibox_loss_box, loc_mode 1 .. 4 = IoU, GIoU, DIoU, CIoU): decode of the
+// predicted box (Util.gcxgcy_to_cxcy, the exponent clamped to +-log(1000 / 16)), the loss of one positive and its gradient with respect
+// to the four offsets, in ONE function for the per-image kernel (which keeps the loss) and both finalize kernels (which keep the
+// gradient).  `mode` is wave-uniform.  A clamped coordinate has gradient exactly +0; CIoU's alpha is a constant of the gradient.
+// Where two corners are equal (a kink of min / max) the gradient is one of the two one-sided ones.
+constexpr float BOX_T = 4.135166556742356f;      // log(1000 / 16)
+constexpr float BOX_EPS = 1e-7f;
+struct BoxTerm { float loss; float d[4]; };
+
+__device__ __forceinline__ f32x4 load_box(const float* __restrict__ gt, int k) {
+    const f32x4 g = {gt[k * 4 + 0], gt[k * 4 + 1], gt[k * 4 + 2], gt[k * 4 + 3]};
+    return g;
+}
+
+__device__ __forceinline__ BoxTerm box_term(int mode, const f32x4 l, const f32x4 pr, const f32x4 g) {
+    const float gx1 = g[0], gy1 = g[1], gx2 = g[2], gy2 = g[3];
+    const float cx = l[0] * pr[2] / 10.f + pr[0], cy = l[1] * pr[3] / 10.f + pr[1];
+    const float t2 = l[2] / 5.f, t3 = l[3] / 5.f;
+    const bool free_w = t2 >= -BOX_T && t2 <= BOX_T, free_h = t3 >= -BOX_T && t3 <= BOX_T;
+    const float w = expf(fminf(fmaxf(t2, -BOX_T), BOX_T)) * pr[2], h = expf(fminf(fmaxf(t3, -BOX_T), BOX_T)) * pr[3];
+    const float x1 = cx - w / 2.f, y1 = cy - h / 2.f, x2 = cx + w / 2.f, y2 = cy + h / 2.f;
+    const float gw = gx2 - gx1, gh = gy2 - gy1;
+    const float iw = fminf(x2, gx2) - fmaxf(x1, gx1), ih = fminf(y2, gy2) - fmaxf(y1, gy1);
+    const float iwc = fmaxf(iw, 0.f), ihc = fmaxf(ih, 0.f);
+    const float inter = iwc * ihc;
+    const float uni = w * h + gw * gh - inter;
+    const float ue = uni + BOX_EPS;
+    const float iou = inter / ue;
+    const float cw = fmaxf(x2, gx2) - fminf(x1, gx1), ch = fmaxf(y2, gy2) - fminf(y1, gy1);
+    float loss = 1.f - iou;
+    // d(loss) / d(inter) with the union held, d / d(union), d / d(cw | ch), and what reaches cx, cy, w, h without passing a corner
+    const float g_int = -1.f / ue;
+    float g_uni = inter / (ue * ue);
+    float g_cw = 0.f, g_ch = 0.f, g_cx = 0.f, g_cy = 0.f, g_w = 0.f, g_h = 0.f;
+    if (mode == 2) {
+        const float hull = cw * ch, he = hull + BOX_EPS;
+        loss += (hull - uni) / he;
+        g_uni -= 1.f / he;
+        const float g_hull = ue / (he * he);
+        g_cw = g_hull * ch;
+        g_ch = g_hull * cw;
+    } else if (mode >= 3) {
+        const float dx = cx - (gx1 + gx2) / 2.f, dy = cy - (gy1 + gy2) / 2.f;
+        const float rho2 = dx * dx + dy * dy, ce = cw * cw + ch * ch + BOX_EPS;
+        loss += rho2 / ce;
+        g_cx = 2.f * dx / ce;
+        g_cy = 2.f * dy / ce;
+        const float g_c2 = -rho2 / (ce * ce);
+        g_cw = g_c2 * 2.f * cw;
+        g_ch = g_c2 * 2.f * ch;
+        if (mode == 4) {
+            constexpr float K = 0.4052847345693511f;       // 4 / pi^2
+            const float da = atanf(gw / gh) - atanf(w / h);
+            const float v = K * da * da;
+            const float alpha = v / (1.f - iou + v + BOX_EPS);
+            loss += alpha * v;
+            const float sv = alpha * 2.f * K * da / (w * w + h * h);      // alpha * dv/dw = -sv * h, alpha * dv/dh = sv * w
+            g_w = -sv * h;
+            g_h = sv * w;
+        }
+    }
+    const float gi = g_int - g_uni;                        // the intersection also lowers the union
+    const float ox = iw > 0.f ? gi * ihc : 0.f, oy = ih > 0.f ? gi * iwc : 0.f;
+    const float d_x1 = (x1 > gx1 ? -ox : 0.f) + (x1 < gx1 ? -g_cw : 0.f);
+    const float d_x2 = (x2 < gx2 ? ox : 0.f) + (x2 > gx2 ? g_cw : 0.f);
+    const float d_y1 = (y1 > gy1 ? -oy : 0.f) + (y1 < gy1 ? -g_ch : 0.f);
+    const float d_y2 = (y2 < gy2 ? oy : 0.f) + (y2 > gy2 ? g_ch : 0.f);
+    BoxTerm o;
+    o.loss = loss;
+    o.d[0] = (d_x1 + d_x2 + g_cx) * (pr[2] / 10.f);
+    o.d[1] = (d_y1 + d_y2 + g_cy) * (pr[3] / 10.f);
+    o.d[2] = free_w ? ((d_x2 - d_x1) / 2.f + g_uni * h + g_w) * (w / 5.f) : 0.f;
+    o.d[3] = free_h ? ((d_y2 - d_y1) / 2.f + g_uni * w + g_h) * (h / 5.f) : 0.f;
+    return o;
 }
 
 __device__ __forceinline__ float block_sum_256(float v, float* sm) {
@@ -295,6 +376,7 @@ struct ImageArgs {
     float* bestv; float* cebg;                        // [bs][P]: IoU of the prior's best box (unforced); CE against the class that box gives it
     int32_t* best_prior; int32_t* obj; int32_t* cls; uint8_t* sel; float* stats;
     int P, C, ratio, NPW; float thr;
+    int loc_mode;                                     // loss_image_kernel<., true>: 1 .. 4 = IoU, GIoU, DIoU, CIoU (box_term)
 };
 
 constexpr int SG = 128;        // GT boxes of an image kept in LDS (more are read from memory: correct, slower)
@@ -514,7 +596,8 @@ __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a,
 
 // L2: one workgroup of 1024 threads per image.  IGN: the bytes L1 wrote stay set for non-positives only; those get the mining value 0
 // like the positives and never a selection bit (one bit per prior in LDS behind vals carries that to the last pass).
-template <bool IGN>
+// BOX: the localisation term of a positive is box_term's (stats[2] = the sum of the per-positive losses); false is the L1 kernel, unchanged.
+template <bool IGN, bool BOX>
 __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a, const IgnArgs g) {
     constexpr int NW = 16, NT = 1024;
     extern __shared__ __attribute__((aligned(16))) uint32_t vals[];            // [P] negative CE bits of this image (IGN: + [ceil(P / 32)] ignored bits)
@@ -608,16 +691,20 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a, con
                     nv = 0.f;
                     my_pos += 1.f;
                     my_ce += ce;
-                    float g[4];
-                    if (idx - s < SG) {
-                        const f32x4 g4 = sg_box[idx - s];
-                        const float gb[4] = {g4[0], g4[1], g4[2], g4[3]};
-                        encode_gt(gb, 0, prr[u], g);
+                    if (BOX) {
+                        my_l1 += box_term(a.loc_mode, lc[u], prr[u], idx - s < SG ? sg_box[idx - s] : load_box(a.gt, idx)).loss;
                     } else {
-                        encode_gt(a.gt, idx, prr[u], g);
+                        float g[4];
+                        if (idx - s < SG) {
+                            const f32x4 g4 = sg_box[idx - s];
+                            const float gb[4] = {g4[0], g4[1], g4[2], g4[3]};
+                            encode_gt(gb, 0, prr[u], g);
+                        } else {
+                            encode_gt(a.gt, idx, prr[u], g);
+                        }
+                        const f32x4 l = lc[u];
+                        my_l1 += (fabsf(l[0] - g[0]) + fabsf(l[1] - g[1])) + (fabsf(l[2] - g[2]) + fabsf(l[3] - g[3]));
                     }
-                    const f32x4 l = lc[u];
-                    my_l1 += (fabsf(l[0] - g[0]) + fabsf(l[1] - g[1])) + (fabsf(l[2] - g[2]) + fabsf(l[3] - g[3]));
                 }
                 if (IGN) {
                     const bool ignored = !pos && ig[u] != 0;
@@ -752,8 +839,11 @@ struct FinalArgs {
     const int32_t* obj; const int32_t* cls; const uint8_t* sel; const float* stats;
     float* losses; float* dloc; float* dconf;
     int P, C, bs, norm_mode;
+    int loc_mode;                                     // finalize kernels <true>: as ImageArgs::loc_mode
 };
 
+// BOX (both finalize kernels): loc_loss is the per-positive mean (or sum) of box_term's loss and dloc its gradient; false is the L1 form
+template <bool BOX>
 __global__ __launch_bounds__(LB) void finalize_kernel(const FinalArgs a) {
     __shared__ float tot[4];
     if (threadIdx.x == 0) {
@@ -767,7 +857,8 @@ __global__ __launch_bounds__(LB) void finalize_kernel(const FinalArgs a) {
     const float npos = tot[0];
     const float inv = a.norm_mode == 0 ? 1.f / npos : 1.f;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        a.losses[0] = a.norm_mode == 0 ? tot[2] / (npos * 4.f) : tot[2] / 4.f;     // nn.L1Loss mean over n_pos*4
+        if (BOX) a.losses[0] = a.norm_mode == 0 ? tot[2] / npos : tot[2];
+        else a.losses[0] = a.norm_mode == 0 ? tot[2] / (npos * 4.f) : tot[2] / 4.f;     // nn.L1Loss mean over n_pos*4
         a.losses[1] = a.norm_mode == 0 ? (tot[3] + tot[1]) / npos : (tot[3] + tot[1]);
         a.losses[2] = npos;
     }
@@ -797,14 +888,20 @@ __global__ __launch_bounds__(LB) void finalize_kernel(const FinalArgs a) {
         f32x4 dl = {0.f, 0.f, 0.f, 0.f};
         if (pos) {
             const f32x4 pr = *reinterpret_cast<const f32x4*>(a.pri + (size_t)p * 4);
-            float g[4];
-            encode_gt(a.gt, a.obj[ip], pr, g);
             const f32x4 l = *reinterpret_cast<const f32x4*>(a.loc + ip * 4);
-            const float sc = inv * 0.25f;
+            if (BOX) {
+                const BoxTerm bt = box_term(a.loc_mode, l, pr, load_box(a.gt, a.obj[ip]));
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float d = l[q] - g[q];
-                dl[q] = d > 0.f ? sc : (d < 0.f ? -sc : 0.f);
+                for (int q = 0; q < 4; ++q) dl[q] = bt.d[q] * inv;
+            } else {
+                float g[4];
+                encode_gt(a.gt, a.obj[ip], pr, g);
+                const float sc = inv * 0.25f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float d = l[q] - g[q];
+                    dl[q] = d > 0.f ? sc : (d < 0.f ? -sc : 0.f);
+                }
             }
         }
         *reinterpret_cast<f32x4*>(a.dloc + ip * 4) = dl;
@@ -817,6 +914,7 @@ __global__ __launch_bounds__(LB) void finalize_kernel(const FinalArgs a) {
 
 // L3w (64 < C <= 256): grid (ceil(P / 64), bs), 256 threads; block = 64 consecutive priors of image blockIdx.y
 constexpr int RW = 64;
+template <bool BOX>
 __global__ __launch_bounds__(LB) void finalize_wide_kernel(const FinalArgs a) {
     __shared__ float tot[4];
     __shared__ float s_m[RW], s_r[RW];
@@ -832,7 +930,8 @@ __global__ __launch_bounds__(LB) void finalize_wide_kernel(const FinalArgs a) {
     const float npos = tot[0];
     const float inv = a.norm_mode == 0 ? 1.f / npos : 1.f;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        a.losses[0] = a.norm_mode == 0 ? tot[2] / (npos * 4.f) : tot[2] / 4.f;
+        if (BOX) a.losses[0] = a.norm_mode == 0 ? tot[2] / npos : tot[2];
+        else a.losses[0] = a.norm_mode == 0 ? tot[2] / (npos * 4.f) : tot[2] / 4.f;
         a.losses[1] = a.norm_mode == 0 ? (tot[3] + tot[1]) / npos : (tot[3] + tot[1]);
         a.losses[2] = npos;
     }
@@ -862,14 +961,20 @@ __global__ __launch_bounds__(LB) void finalize_wide_kernel(const FinalArgs a) {
         f32x4 dl = {0.f, 0.f, 0.f, 0.f};
         if (a.cls[ip] != C - 1) {
             const f32x4 pr = *reinterpret_cast<const f32x4*>(a.pri + (size_t)p * 4);
-            float g[4];
-            encode_gt(a.gt, a.obj[ip], pr, g);
             const f32x4 l = *reinterpret_cast<const f32x4*>(a.loc + ip * 4);
-            const float sc = inv * 0.25f;
+            if (BOX) {
+                const BoxTerm bt = box_term(a.loc_mode, l, pr, load_box(a.gt, a.obj[ip]));
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float d = l[q] - g[q];
-                dl[q] = d > 0.f ? sc : (d < 0.f ? -sc : 0.f);
+                for (int q = 0; q < 4; ++q) dl[q] = bt.d[q] * inv;
+            } else {
+                float g[4];
+                encode_gt(a.gt, a.obj[ip], pr, g);
+                const float sc = inv * 0.25f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float d = l[q] - g[q];
+                    dl[q] = d > 0.f ? sc : (d < 0.f ? -sc : 0.f);
+                }
             }
         }
         *reinterpret_cast<f32x4*>(a.dloc + ip * 4) = dl;
@@ -925,8 +1030,8 @@ extern "C" size_t ssd_multibox_loss_workspace(int bs, int P, int n_gt) {
 
 namespace {
 
-// L1 (or L1w) and L2 of the three-launch form; IGN = false is what ssd_multibox_loss has always launched
-template <bool IGN>
+// L1 (or L1w) and L2 of the three-launch form; IGN = false, BOX = false is what ssd_multibox_loss has always launched
+template <bool IGN, bool BOX>
 int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, hipStream_t st) {
     const bool wide_rows = ia.C > 64;               // L1w / L3w: nothing staged per class
     const size_t l1_lds = wide_rows ? 0 : (size_t)4 * 64 * ia.C * 4;
@@ -936,7 +1041,7 @@ int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, h
     if ((l1_lds > 48 * 1024 || l2_lds > 48 * 1024) && ssd_attr_needed(raised_l12, dev)) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(loss_prior_kernel<IGN>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
                 hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(loss_image_kernel<IGN>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
+            hipFuncSetAttribute(reinterpret_cast<const void*>(loss_image_kernel<IGN, BOX>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
                 hipSuccess)
             return SSD_ERR_LAUNCH;
         ssd_attr_done(raised_l12, dev);
@@ -946,17 +1051,18 @@ int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, h
     else
         hipLaunchKernelGGL(loss_prior_kernel<IGN>, dim3(NB, bs), dim3(256), l1_lds, st, ia, ga);
     SSD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(loss_image_kernel<IGN>, dim3(bs), dim3(1024), l2_lds, st, ia, ga);
+    hipLaunchKernelGGL((loss_image_kernel<IGN, BOX>), dim3(bs), dim3(1024), l2_lds, st, ia, ga);
     SSD_CHECK_LAUNCH();
     return SSD_OK;
 }
 
-// L3 (or L3w): shared by both entries
+// L3 (or L3w): shared by the entries; BOX = false is what they have always launched
+template <bool BOX>
 int launch_finalize(const FinalArgs& fa, hipStream_t st) {
     const int NB = ssd_cdiv(fa.P, LB);
     const bool grads = fa.dloc != nullptr;
     if (fa.C > 64) {
-        hipLaunchKernelGGL(finalize_wide_kernel, grads ? dim3(ssd_cdiv(fa.P, RW), fa.bs) : dim3(1, 1), dim3(LB), 0, st, fa);
+        hipLaunchKernelGGL(finalize_wide_kernel<BOX>, grads ? dim3(ssd_cdiv(fa.P, RW), fa.bs) : dim3(1, 1), dim3(LB), 0, st, fa);
         SSD_CHECK_LAUNCH();
         return SSD_OK;
     }
@@ -965,13 +1071,13 @@ int launch_finalize(const FinalArgs& fa, hipStream_t st) {
         static std::atomic<unsigned long long> raised_fin{0};
         int dev;
         if (ssd_attr_needed(raised_fin, dev)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(finalize_kernel<BOX>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
                 hipSuccess)
                 return SSD_ERR_LAUNCH;
             ssd_attr_done(raised_fin, dev);
         }
     }
-    hipLaunchKernelGGL(finalize_kernel, grads ? dim3(NB, fa.bs) : dim3(1, 1), dim3(LB), fin_lds, st, fa);
+    hipLaunchKernelGGL(finalize_kernel<BOX>, grads ? dim3(NB, fa.bs) : dim3(1, 1), dim3(LB), fin_lds, st, fa);
     SSD_CHECK_LAUNCH();
     return SSD_OK;
 }
@@ -1012,7 +1118,7 @@ extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const floa
         // L1 wide (a wave per 64 priors), L2 one workgroup per image
         ImageArgs ia{loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, w.partv, w.parti, w.bestv, w.neg,
                      w.best_prior, obj, cls, w.sel, w.stats, P, n_classes, neg_pos_ratio, NB * 4, iou_threshold};
-        const int rc = launch_prior_image<false>(ia, IgnArgs{nullptr, nullptr, nullptr, 0.f, 0}, bs, NB, st);
+        const int rc = launch_prior_image<false, false>(ia, IgnArgs{nullptr, nullptr, nullptr, 0.f, 0}, bs, NB, st);
         if (rc != SSD_OK) return rc;
     } else {
         hipLaunchKernelGGL(best_prior_per_gt_kernel, dim3(n_gt), dim3(256), 0, st, gt_boxes, priors_xyxy, P, w.best_prior);
@@ -1035,7 +1141,7 @@ extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const floa
         hipLaunchKernelGGL(hard_negative_kernel, dim3(bs), dim3(HB), hn_lds, st, w.neg, w.part, w.sel, w.stats, P, NB, neg_pos_ratio);
         SSD_CHECK_LAUNCH();
     }
-    return launch_finalize(FinalArgs{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode},
+    return launch_finalize<false>(FinalArgs{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode},
                            st);
 }
 
@@ -1065,8 +1171,47 @@ extern "C" int ssd_multibox_loss_ignore(const float* loc, const float* conf, con
     const int NB = ssd_cdiv(P, LB);
     ImageArgs ia{loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, w.partv, w.parti, w.bestv, w.neg,
                  w.best_prior, obj, cls, w.sel, w.stats, P, n_classes, neg_pos_ratio, NB * 4, iou_threshold};
-    const int rc = launch_prior_image<true>(ia, IgnArgs{ign_boxes, ign_start, ign, ignore_threshold, overlap_mode}, bs, NB, st);
+    const int rc = launch_prior_image<true, false>(ia, IgnArgs{ign_boxes, ign_start, ign, ignore_threshold, overlap_mode}, bs, NB, st);
     if (rc != SSD_OK) return rc;
-    return launch_finalize(FinalArgs{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode},
+    return launch_finalize<false>(FinalArgs{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode},
                            st);
+}
+
+// The loss with a choice of localisation term; always the three-launch form.  loc_mode 0 launches exactly the kernels of the two
+// entries above (ign_start == NULL: ssd_multibox_loss's, else ssd_multibox_loss_ignore's); 1 .. 4 launch the BOX instances of the
+// per-image and finalize kernels.  The workspace is ssd_multibox_loss's.
+extern "C" size_t ssd_multibox_loss_box_workspace(int bs, int P, int n_gt, int n_ign) {
+    return ssd_multibox_loss_ignore_workspace(bs, P, n_gt, n_ign);
+}
+
+extern "C" int ssd_multibox_loss_box(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                                     const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh, const float* priors_xyxy,
+                                     int P, int n_classes, float iou_threshold, int neg_pos_ratio, int norm_mode, const float* ign_boxes,
+                                     const int32_t* ign_start, int n_ign, float ignore_threshold, int overlap_mode, int loc_mode,
+                                     float* losses, int32_t* obj, int32_t* cls, uint8_t* ign, float* dloc, float* dconf, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    const bool with_ign = ign_start != nullptr;
+    if (with_ign && (!ign || (n_ign > 0 && !ign_boxes))) return SSD_ERR_NULL;
+    const int bad = check_loss_args(loc, conf, gt_boxes, gt_classes, img_start, bs, n_gt, priors_cxcywh, priors_xyxy, P, n_classes,
+                                    neg_pos_ratio, norm_mode, losses, obj, cls, dloc, dconf, workspace, workspace_bytes);
+    if (bad == SSD_ERR_NULL) return bad;               // the header's order: null, shape, alignment, workspace
+    if (loc_mode < 0 || loc_mode > 4) return SSD_ERR_BAD_SHAPE;
+    if (with_ign && (n_ign < 0 || (overlap_mode != 0 && overlap_mode != 1))) return SSD_ERR_BAD_SHAPE;
+    if (bad == SSD_ERR_BAD_SHAPE || bad == SSD_ERR_ALIGN) return bad;
+    if (with_ign && n_ign > 0 && !ssd_aligned16(ign_boxes)) return SSD_ERR_ALIGN;
+    if (bad != SSD_OK) return bad;
+    hipStream_t st = (hipStream_t)stream;
+    const LossWs w = carve(workspace, bs, P, n_gt);
+    const int NB = ssd_cdiv(P, LB);
+    const ImageArgs ia{loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, w.partv, w.parti, w.bestv, w.neg,
+                       w.best_prior, obj, cls, w.sel, w.stats, P, n_classes, neg_pos_ratio, NB * 4, iou_threshold, loc_mode};
+    const IgnArgs ga = with_ign ? IgnArgs{ign_boxes, ign_start, ign, ignore_threshold, overlap_mode} : IgnArgs{nullptr, nullptr, nullptr, 0.f, 0};
+    const FinalArgs fa{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode, loc_mode};
+    int rc;
+    if (loc_mode == 0)
+        rc = with_ign ? launch_prior_image<true, false>(ia, ga, bs, NB, st) : launch_prior_image<false, false>(ia, ga, bs, NB, st);
+    else
+        rc = with_ign ? launch_prior_image<true, true>(ia, ga, bs, NB, st) : launch_prior_image<false, true>(ia, ga, bs, NB, st);
+    if (rc != SSD_OK) return rc;
+    return loc_mode == 0 ? launch_finalize<false>(fa, st) : launch_finalize<true>(fa, st);
 }

@@ -600,11 +600,14 @@ class GraphedTrainStep:
     none at all included, replays without a re-capture.  `ignore_threshold` / `ignore_overlap` (attributes, 0.5 / "iou") are baked
     in; changing one re-captures.
 
+    loc_loss (default "l1": the captured graph is the one it always was): the localisation term of `Losses.ssd(loc_loss=...)`, "iou" /
+    "giou" / "diou" / "ciou", passed to the eager and to the captured loss call; an attribute, changing it re-captures.
+
     `__call__(x, classes, boxes, ignore=None)` -> (loc_sum, conf_sum, n_pos): 0-dim views of a static device tensor holding this rank's
     un-normalised loss sums and positive count (`Losses.ssd(..., norm_mode=1, with_n_pos=True)`), overwritten by the next call."""
 
     def __init__(self, net, trainer: FlatSGDDataParallel, max_boxes_per_image: int = 8, warmup: int = 2, two_streams: bool = True,
-                 max_ignore_per_image: int = 0):
+                 loc_loss: str = "l1", max_ignore_per_image: int = 0):
         if trainer.grad_dtype == torch.bfloat16 and trainer.world > 1:       # (before anything below touches the trainer or the net)
             raise ValueError("GraphedTrainStep exchanges the f32 gradient buffer in one all-reduce behind the replay: a trainer built with "
                              "grad_dtype=torch.bfloat16 would silently send f32 -- build it with the f32 default, or step it eagerly")
@@ -614,6 +617,8 @@ class GraphedTrainStep:
             raise ValueError("max_ignore_per_image must be >= 0")
         self.max_ignore_per_image = int(max_ignore_per_image)
         self.ignore_threshold, self.ignore_overlap = 0.5, "iou"
+        ops.loc_loss_mode(loc_loss)
+        self.loc_loss = loc_loss
         self.two_streams = bool(two_streams)
         self.graph = None
         self._sig = None
@@ -710,7 +715,7 @@ class GraphedTrainStep:
             kw = dict(ignore_boxes=S["ign"], ignore_start=S["ign_start"], ignore_threshold=self.ignore_threshold,
                       ignore_overlap=self.ignore_overlap)
         out = ops.multibox_loss(loc, conf, S["gt"], S["cls"], S["start"], pri, pri_xyxy, Losses.IOU_THRESHOLD, Losses.NEG_POS_RATIO, 1,
-                                want_grads=True, **kw)
+                                want_grads=True, loc_loss=self.loc_loss, **kw)
         need = {n: bool(P[n].requires_grad) for n in eng.names}
         eng.backward(saved, out["dloc"], out["dconf"], P, need)
         tr.flat_grad[tr.n:tr.n + 1].copy_(out["losses"][2:3])
@@ -725,7 +730,7 @@ class GraphedTrainStep:
         eng = self.net._engine
         return tuple((g["lr"], g.get("momentum"), g["weight_decay"], g.get("betas"), g.get("eps")) for g in tr.param_groups) + (
             tr.optimizer_kind, tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + tr._clip_settings() + tr._sched_settings() + eng.schedule_key() + (
-            (self.ignore_threshold, self.ignore_overlap) if self.max_ignore_per_image > 0 else ())
+            (self.ignore_threshold, self.ignore_overlap) if self.max_ignore_per_image > 0 else ()) + (self.loc_loss,)
 
     def _eager(self, x, classes, boxes, ignore=None):
         from . import Losses
@@ -736,7 +741,7 @@ class GraphedTrainStep:
         if self.max_ignore_per_image > 0:
             kw = dict(ignore_bboxs=self._ignore_lists(ignore, x.shape[0]), ignore_threshold=self.ignore_threshold,
                       ignore_overlap=self.ignore_overlap)
-        l1, l2, n_pos = Losses.ssd((loc, conf), classes, boxes, norm_mode=1, with_n_pos=True, **kw)
+        l1, l2, n_pos = Losses.ssd((loc, conf), classes, boxes, norm_mode=1, with_n_pos=True, loc_loss=self.loc_loss, **kw)
         (l1 + l2).backward()
         tr.reduce_and_step(n_pos)
         return l1.detach(), l2.detach(), n_pos

@@ -869,15 +869,31 @@ def ignore_overlap_mode(overlap):
         raise ValueError(f"ignore_overlap must be 'iou' or 'ioa', not {overlap!r}") from None
 
 
+LOC_LOSSES = {"l1": 0, "iou": 1, "giou": 2, "diou": 3, "ciou": 4}
+
+
+def loc_loss_mode(name):
+    """0 .. 4 for "l1" / "iou" / "giou" / "diou" / "ciou" (the `loc_mode` of the C ABI); ValueError for anything else."""
+    try:
+        return LOC_LOSSES[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"loc_loss must be one of {', '.join(map(repr, LOC_LOSSES))}, not {name!r}") from None
+
+
 def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, iou_threshold=0.5,
-                  neg_pos_ratio=3, norm_mode=0, want_grads=True, ignore_boxes=None, ignore_start=None, ignore_threshold=0.5,
-                  ignore_overlap="iou"):
+                  neg_pos_ratio=3, norm_mode=0, want_grads=True, loc_loss="l1", ignore_boxes=None, ignore_start=None,
+                  ignore_threshold=0.5, ignore_overlap="iou"):
     """-> dict(losses (3,), obj (bs,P) i32, cls (bs,P) i32, dloc, dconf).
     ignore_boxes (n_ign, 4) fractional xyxy with ignore_start (bs + 1,) int32 prefix offsets (both on the device; n_ign may be 0):
     the loss with ignore regions (`ssd_multibox_loss_ignore`) -- a prior that is not positive and overlaps an ignore box of its
     image by >= ignore_threshold ("iou", or "ioa" = intersection over the prior's area) is neither mined nor given a gradient; the
-    dict then has "ign" (bs,P) uint8 too.  None: the plain entry."""
+    dict then has "ign" (bs,P) uint8 too.  None: the plain entry.
+    loc_loss: "l1" (the reference's term: exactly the two entries above), or "iou" / "giou" / "diou" / "ciou" -- the entry
+    `ssd_multibox_loss_box`: the predicted box of each positive is decoded (exponent clamped to +-log(1000 / 16)) and losses[0] is the
+    per-positive mean (norm_mode 1: sum) of 1 - IoU plus the mode's penalty, dloc its gradient; everything else is unchanged.  "ciou"
+    needs ground-truth boxes of positive height; "iou" gives no gradient where the two boxes do not overlap."""
     mode = ignore_overlap_mode(ignore_overlap)
+    loc_mode = loc_loss_mode(loc_loss)
     if (ignore_boxes is None) != (ignore_start is None):
         raise ValueError("multibox_loss: ignore_boxes and ignore_start go together")
     _req(loc, "loc"); _req(conf, "conf"); _req(gt_boxes, "gt_boxes"); _req(gt_classes, "gt_classes")
@@ -895,6 +911,26 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
     cls = torch.empty((bs, p), device=dev, dtype=torch.int32)
     dloc = torch.empty_like(loc) if want_grads else None
     dconf = torch.empty_like(conf) if want_grads else None
+    if loc_mode != 0:
+        n_ign, ign = 0, None
+        if ignore_boxes is not None:
+            _req(ignore_boxes, "ignore_boxes"); _req(ignore_start, "ignore_start", torch.int32)
+            n_ign = ignore_boxes.shape[0]
+            if tuple(ignore_boxes.shape) != (n_ign, 4) or ignore_start.numel() != bs + 1:
+                raise ValueError("multibox_loss ignore shapes")
+            ign = torch.empty((bs, p), device=dev, dtype=torch.uint8)
+        ws = workspace(lib.ssd_multibox_loss_box_workspace(bs, p, n_gt, n_ign), loc.device, "loss")
+        check(lib.ssd_multibox_loss_box(loc.data_ptr(), conf.data_ptr(), gt_boxes.data_ptr(), gt_classes.data_ptr(),
+                                        img_start.data_ptr(), bs, n_gt, priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, ncls,
+                                        float(iou_threshold), int(neg_pos_ratio), int(norm_mode),
+                                        ignore_boxes.data_ptr() if n_ign else None, _ptr(ignore_start), n_ign,
+                                        float(ignore_threshold), mode, loc_mode, losses.data_ptr(), obj.data_ptr(), cls.data_ptr(),
+                                        _ptr(ign), _ptr(dloc), _ptr(dconf), ws.data_ptr(), ws.numel(), _stream()),
+              "multibox_loss_box")
+        out = dict(losses=losses, obj=obj, cls=cls, dloc=dloc, dconf=dconf)
+        if ign is not None:
+            out["ign"] = ign
+        return out
     if ignore_boxes is not None:
         _req(ignore_boxes, "ignore_boxes"); _req(ignore_start, "ignore_start", torch.int32)
         n_ign = ignore_boxes.shape[0]
