@@ -1015,21 +1015,6 @@ LossWs carve(void* ws, int bs, int P, int n_gt) {
     return w;
 }
 
-}  // namespace
-
-// Cross-check aid: 1 = the three-launch form (default), 0 = the four-launch form of rounds 1-3.
-extern "C" int ssd_tune_set_loss_form(int three_launch) {
-    g_loss_form = three_launch ? 1 : 0;
-    return SSD_OK;
-}
-
-extern "C" size_t ssd_multibox_loss_workspace(int bs, int P, int n_gt) {
-    if (bs <= 0 || P <= 0 || n_gt <= 0) return 0;
-    return carve(nullptr, bs, P, n_gt).bytes;
-}
-
-namespace {
-
 // L1 (or L1w) and L2 of the three-launch form; IGN = false, BOX = false is what ssd_multibox_loss has always launched
 template <bool IGN, bool BOX>
 int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, hipStream_t st) {
@@ -1082,136 +1067,160 @@ int launch_finalize(const FinalArgs& fa, hipStream_t st) {
     return SSD_OK;
 }
 
-// argument checks common to ssd_multibox_loss and ssd_multibox_loss_ignore
-int check_loss_args(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes, const int32_t* img_start, int bs,
-                    int n_gt, const float* priors_cxcywh, const float* priors_xyxy, int P, int n_classes, int neg_pos_ratio, int norm_mode,
-                    const float* losses, const int32_t* obj, const int32_t* cls, const float* dloc, const float* dconf,
-                    const void* workspace, size_t workspace_bytes) {
-    if (!loc || !conf || !gt_boxes || !gt_classes || !img_start || !priors_cxcywh || !priors_xyxy || !losses || !obj ||
-        !cls || !workspace)
+// Everything an entry receives: ssd_multibox_loss_box's parameters in their order, plus with_ign ahead of the ignore arguments.
+// An entry without ignore regions leaves with_ign false (the ignore fields are then read by nothing); one without a choice of
+// localisation term leaves loc_mode 0.
+struct LossCall {
+    const float* loc; const float* conf; const float* gt_boxes; const float* gt_classes; const int32_t* img_start;
+    int bs, n_gt;
+    const float* priors_cxcywh; const float* priors_xyxy;
+    int P, n_classes; float iou_threshold; int neg_pos_ratio, norm_mode;
+    bool with_ign; const float* ign_boxes; const int32_t* ign_start; int n_ign; float ignore_threshold; int overlap_mode;
+    int loc_mode;
+    float* losses; int32_t* obj; int32_t* cls; uint8_t* ign; float* dloc; float* dconf;
+    void* workspace; size_t workspace_bytes; hipStream_t stream;
+};
+
+// The status of a call in the header's order: null, shape, alignment, workspace
+int check_loss_call(const LossCall& c) {
+    if (!c.loc || !c.conf || !c.gt_boxes || !c.gt_classes || !c.img_start || !c.priors_cxcywh || !c.priors_xyxy || !c.losses || !c.obj ||
+        !c.cls || !c.workspace)
         return SSD_ERR_NULL;
-    if ((dloc == nullptr) != (dconf == nullptr)) return SSD_ERR_NULL;
-    if (bs <= 0 || n_gt < bs || P <= 0 || P > 36000 || n_classes < 2 || n_classes > 256 || neg_pos_ratio < 0 ||
-        (norm_mode != 0 && norm_mode != 1))
+    if ((c.dloc == nullptr) != (c.dconf == nullptr)) return SSD_ERR_NULL;
+    if (c.with_ign && (!c.ign_start || !c.ign || (c.n_ign > 0 && !c.ign_boxes))) return SSD_ERR_NULL;
+    if (c.bs <= 0 || c.n_gt < c.bs || c.P <= 0 || c.P > 36000 || c.n_classes < 2 || c.n_classes > 256 || c.neg_pos_ratio < 0 ||
+        (c.norm_mode != 0 && c.norm_mode != 1) || c.loc_mode < 0 || c.loc_mode > 4)
         return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(loc) || !ssd_aligned16(priors_cxcywh) || !ssd_aligned16(priors_xyxy) || (dloc && !ssd_aligned16(dloc)) ||
-        !ssd_aligned16(workspace))
+    if (c.with_ign && (c.n_ign < 0 || (c.overlap_mode != 0 && c.overlap_mode != 1))) return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(c.loc) || !ssd_aligned16(c.priors_cxcywh) || !ssd_aligned16(c.priors_xyxy) || (c.dloc && !ssd_aligned16(c.dloc)) ||
+        !ssd_aligned16(c.workspace))
         return SSD_ERR_ALIGN;
-    if (workspace_bytes < ssd_multibox_loss_workspace(bs, P, n_gt)) return SSD_ERR_WORKSPACE;
+    if (c.with_ign && c.n_ign > 0 && !ssd_aligned16(c.ign_boxes)) return SSD_ERR_ALIGN;
+    if (c.workspace_bytes < carve(nullptr, c.bs, c.P, c.n_gt).bytes) return SSD_ERR_WORKSPACE;
     return SSD_OK;
+}
+
+// The three launches of a checked call.  with_ign picks the IGN instances of L1 / L1w / L2, loc_mode != 0 the BOX instances of L2 and
+// L3 / L3w: without either these are the kernels of the plain loss.
+int run_loss(const LossCall& c) {
+    const LossWs w = carve(c.workspace, c.bs, c.P, c.n_gt);
+    const int NB = ssd_cdiv(c.P, LB);
+    const ImageArgs ia{c.loc, c.conf, c.gt_boxes, c.gt_classes, c.img_start, c.priors_cxcywh, c.priors_xyxy, w.partv, w.parti, w.bestv,
+                       w.neg, w.best_prior, c.obj, c.cls, w.sel, w.stats, c.P, c.n_classes, c.neg_pos_ratio, NB * 4, c.iou_threshold,
+                       c.loc_mode};
+    const IgnArgs ga = c.with_ign ? IgnArgs{c.ign_boxes, c.ign_start, c.ign, c.ignore_threshold, c.overlap_mode}
+                                  : IgnArgs{nullptr, nullptr, nullptr, 0.f, 0};
+    const FinalArgs fa{c.loc, c.conf, c.gt_boxes, c.priors_cxcywh, c.obj, c.cls, w.sel, w.stats, c.losses, c.dloc, c.dconf, c.P,
+                       c.n_classes, c.bs, c.norm_mode, c.loc_mode};
+    const bool box = c.loc_mode != 0;
+    int rc;
+    if (c.with_ign)
+        rc = box ? launch_prior_image<true, true>(ia, ga, c.bs, NB, c.stream) : launch_prior_image<true, false>(ia, ga, c.bs, NB, c.stream);
+    else
+        rc = box ? launch_prior_image<false, true>(ia, ga, c.bs, NB, c.stream) : launch_prior_image<false, false>(ia, ga, c.bs, NB, c.stream);
+    if (rc != SSD_OK) return rc;
+    return box ? launch_finalize<true>(fa, c.stream) : launch_finalize<false>(fa, c.stream);
+}
+
+// The four-launch form of rounds 1-3 (K1 - K3, then L3), the cross-check ssd_tune_set_loss_form(0) selects.  It has neither ignore
+// regions nor box terms and is reached from ssd_multibox_loss alone.
+int run_loss_four_launch(const LossCall& c) {
+    hipStream_t st = c.stream;
+    const LossWs w = carve(c.workspace, c.bs, c.P, c.n_gt);
+    const int NB = ssd_cdiv(c.P, LB);
+    hipLaunchKernelGGL(best_prior_per_gt_kernel, dim3(c.n_gt), dim3(256), 0, st, c.gt_boxes, c.priors_xyxy, c.P, w.best_prior);
+    SSD_CHECK_LAUNCH();
+    MatchArgs ma{c.loc, c.conf, c.gt_boxes, c.gt_classes, c.img_start, w.best_prior, c.priors_cxcywh, c.priors_xyxy,
+                 c.obj, c.cls, w.neg, w.part, c.P, c.n_classes, NB, c.iou_threshold};
+    hipLaunchKernelGGL(match_ce_kernel, dim3(NB, c.bs), dim3(LB), 0, st, ma);
+    SSD_CHECK_LAUNCH();
+    const size_t hn_lds = (size_t)c.P * sizeof(uint32_t);
+    if (hn_lds > 48 * 1024) {
+        static std::atomic<unsigned long long> raised{0};     // one bit per device (common.h)
+        int dev;
+        if (ssd_attr_needed(raised, dev)) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(hard_negative_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    150 * 1024) != hipSuccess)
+                return SSD_ERR_LAUNCH;
+            ssd_attr_done(raised, dev);
+        }
+    }
+    hipLaunchKernelGGL(hard_negative_kernel, dim3(c.bs), dim3(HB), hn_lds, st, w.neg, w.part, w.sel, w.stats, c.P, NB, c.neg_pos_ratio);
+    SSD_CHECK_LAUNCH();
+    return launch_finalize<false>(FinalArgs{c.loc, c.conf, c.gt_boxes, c.priors_cxcywh, c.obj, c.cls, w.sel, w.stats, c.losses, c.dloc, c.dconf,
+                                            c.P, c.n_classes, c.bs, c.norm_mode},
+                                  st);
 }
 
 }  // namespace
 
-extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
-                                 const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh,
-                                 const float* priors_xyxy, int P, int n_classes, float iou_threshold, int neg_pos_ratio,
-                                 int norm_mode, float* losses, int32_t* obj, int32_t* cls, float* dloc, float* dconf,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
-    const int bad = check_loss_args(loc, conf, gt_boxes, gt_classes, img_start, bs, n_gt, priors_cxcywh, priors_xyxy, P, n_classes,
-                                    neg_pos_ratio, norm_mode, losses, obj, cls, dloc, dconf, workspace, workspace_bytes);
-    if (bad != SSD_OK) return bad;
-    hipStream_t st = (hipStream_t)stream;
-    const LossWs w = carve(workspace, bs, P, n_gt);
-    const int NB = ssd_cdiv(P, LB);
-    if (g_loss_form != 0) {
-        // L1 wide (a wave per 64 priors), L2 one workgroup per image
-        ImageArgs ia{loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, w.partv, w.parti, w.bestv, w.neg,
-                     w.best_prior, obj, cls, w.sel, w.stats, P, n_classes, neg_pos_ratio, NB * 4, iou_threshold};
-        const int rc = launch_prior_image<false, false>(ia, IgnArgs{nullptr, nullptr, nullptr, 0.f, 0}, bs, NB, st);
-        if (rc != SSD_OK) return rc;
-    } else {
-        hipLaunchKernelGGL(best_prior_per_gt_kernel, dim3(n_gt), dim3(256), 0, st, gt_boxes, priors_xyxy, P, w.best_prior);
-        SSD_CHECK_LAUNCH();
-        MatchArgs ma{loc, conf, gt_boxes, gt_classes, img_start, w.best_prior, priors_cxcywh, priors_xyxy,
-                     obj, cls, w.neg, w.part, P, n_classes, NB, iou_threshold};
-        hipLaunchKernelGGL(match_ce_kernel, dim3(NB, bs), dim3(LB), 0, st, ma);
-        SSD_CHECK_LAUNCH();
-        const size_t hn_lds = (size_t)P * sizeof(uint32_t);
-        if (hn_lds > 48 * 1024) {
-            static std::atomic<unsigned long long> raised{0};     // one bit per device (common.h)
-            int dev;
-            if (ssd_attr_needed(raised, dev)) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(hard_negative_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        150 * 1024) != hipSuccess)
-                    return SSD_ERR_LAUNCH;
-                ssd_attr_done(raised, dev);
-            }
-        }
-        hipLaunchKernelGGL(hard_negative_kernel, dim3(bs), dim3(HB), hn_lds, st, w.neg, w.part, w.sel, w.stats, P, NB, neg_pos_ratio);
-        SSD_CHECK_LAUNCH();
-    }
-    return launch_finalize<false>(FinalArgs{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode},
-                           st);
+// Cross-check aid: 1 = the three-launch form (default), 0 = the four-launch form of rounds 1-3.
+extern "C" int ssd_tune_set_loss_form(int three_launch) {
+    g_loss_form = three_launch ? 1 : 0;
+    return SSD_OK;
 }
 
-// The loss with ignore regions; always the three-launch form (ssd_tune_set_loss_form does not reach it).  The workspace is the one of
-// ssd_multibox_loss: the ignore byte per prior is the caller's `ign`, nothing else is kept per ignore box.
+// One workspace for the three entries: the ignore byte per prior is the caller's `ign`, nothing is kept per ignore box or per loc_mode.
+extern "C" size_t ssd_multibox_loss_workspace(int bs, int P, int n_gt) {
+    if (bs <= 0 || P <= 0 || n_gt <= 0) return 0;
+    return carve(nullptr, bs, P, n_gt).bytes;
+}
+
 extern "C" size_t ssd_multibox_loss_ignore_workspace(int bs, int P, int n_gt, int n_ign) {
     if (n_ign < 0) return 0;
     return ssd_multibox_loss_workspace(bs, P, n_gt);
 }
 
+extern "C" size_t ssd_multibox_loss_box_workspace(int bs, int P, int n_gt, int n_ign) {
+    return ssd_multibox_loss_ignore_workspace(bs, P, n_gt, n_ign);
+}
+
+// The plain loss: no ignore regions, L1 localisation term.  The one entry ssd_tune_set_loss_form reaches.
+extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                                 const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh,
+                                 const float* priors_xyxy, int P, int n_classes, float iou_threshold, int neg_pos_ratio,
+                                 int norm_mode, float* losses, int32_t* obj, int32_t* cls, float* dloc, float* dconf,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    const LossCall c{.loc = loc, .conf = conf, .gt_boxes = gt_boxes, .gt_classes = gt_classes, .img_start = img_start, .bs = bs, .n_gt = n_gt,
+                     .priors_cxcywh = priors_cxcywh, .priors_xyxy = priors_xyxy, .P = P, .n_classes = n_classes,
+                     .iou_threshold = iou_threshold, .neg_pos_ratio = neg_pos_ratio, .norm_mode = norm_mode, .with_ign = false,
+                     .loc_mode = 0, .losses = losses, .obj = obj, .cls = cls, .dloc = dloc, .dconf = dconf, .workspace = workspace,
+                     .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream};
+    const int bad = check_loss_call(c);
+    if (bad != SSD_OK) return bad;
+    return g_loss_form != 0 ? run_loss(c) : run_loss_four_launch(c);
+}
+
+// The loss with ignore regions (always: a null ign_start or ign is an error here), L1 localisation term
 extern "C" int ssd_multibox_loss_ignore(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
                                         const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh,
                                         const float* priors_xyxy, int P, int n_classes, float iou_threshold, int neg_pos_ratio,
                                         int norm_mode, const float* ign_boxes, const int32_t* ign_start, int n_ign,
                                         float ignore_threshold, int overlap_mode, float* losses, int32_t* obj, int32_t* cls,
                                         uint8_t* ign, float* dloc, float* dconf, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!ign_start || !ign || (n_ign > 0 && !ign_boxes)) return SSD_ERR_NULL;
-    const int bad = check_loss_args(loc, conf, gt_boxes, gt_classes, img_start, bs, n_gt, priors_cxcywh, priors_xyxy, P, n_classes,
-                                    neg_pos_ratio, norm_mode, losses, obj, cls, dloc, dconf, workspace, workspace_bytes);
-    if (bad == SSD_ERR_NULL) return bad;               // the header's order: null, shape, alignment, workspace
-    if (n_ign < 0 || (overlap_mode != 0 && overlap_mode != 1)) return SSD_ERR_BAD_SHAPE;
-    if (bad == SSD_ERR_BAD_SHAPE || bad == SSD_ERR_ALIGN) return bad;
-    if (n_ign > 0 && !ssd_aligned16(ign_boxes)) return SSD_ERR_ALIGN;
-    if (bad != SSD_OK) return bad;
-    hipStream_t st = (hipStream_t)stream;
-    const LossWs w = carve(workspace, bs, P, n_gt);
-    const int NB = ssd_cdiv(P, LB);
-    ImageArgs ia{loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, w.partv, w.parti, w.bestv, w.neg,
-                 w.best_prior, obj, cls, w.sel, w.stats, P, n_classes, neg_pos_ratio, NB * 4, iou_threshold};
-    const int rc = launch_prior_image<true, false>(ia, IgnArgs{ign_boxes, ign_start, ign, ignore_threshold, overlap_mode}, bs, NB, st);
-    if (rc != SSD_OK) return rc;
-    return launch_finalize<false>(FinalArgs{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode},
-                           st);
+    const LossCall c{.loc = loc, .conf = conf, .gt_boxes = gt_boxes, .gt_classes = gt_classes, .img_start = img_start, .bs = bs, .n_gt = n_gt,
+                     .priors_cxcywh = priors_cxcywh, .priors_xyxy = priors_xyxy, .P = P, .n_classes = n_classes,
+                     .iou_threshold = iou_threshold, .neg_pos_ratio = neg_pos_ratio, .norm_mode = norm_mode, .with_ign = true,
+                     .ign_boxes = ign_boxes, .ign_start = ign_start, .n_ign = n_ign, .ignore_threshold = ignore_threshold,
+                     .overlap_mode = overlap_mode, .loc_mode = 0, .losses = losses, .obj = obj, .cls = cls, .ign = ign, .dloc = dloc,
+                     .dconf = dconf, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream};
+    const int bad = check_loss_call(c);
+    return bad != SSD_OK ? bad : run_loss(c);
 }
 
-// The loss with a choice of localisation term; always the three-launch form.  loc_mode 0 launches exactly the kernels of the two
-// entries above (ign_start == NULL: ssd_multibox_loss's, else ssd_multibox_loss_ignore's); 1 .. 4 launch the BOX instances of the
-// per-image and finalize kernels.  The workspace is ssd_multibox_loss's.
-extern "C" size_t ssd_multibox_loss_box_workspace(int bs, int P, int n_gt, int n_ign) {
-    return ssd_multibox_loss_ignore_workspace(bs, P, n_gt, n_ign);
-}
-
+// The loss with a choice of localisation term; ignore regions where ign_start is given
 extern "C" int ssd_multibox_loss_box(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
                                      const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh, const float* priors_xyxy,
                                      int P, int n_classes, float iou_threshold, int neg_pos_ratio, int norm_mode, const float* ign_boxes,
                                      const int32_t* ign_start, int n_ign, float ignore_threshold, int overlap_mode, int loc_mode,
                                      float* losses, int32_t* obj, int32_t* cls, uint8_t* ign, float* dloc, float* dconf, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    const bool with_ign = ign_start != nullptr;
-    if (with_ign && (!ign || (n_ign > 0 && !ign_boxes))) return SSD_ERR_NULL;
-    const int bad = check_loss_args(loc, conf, gt_boxes, gt_classes, img_start, bs, n_gt, priors_cxcywh, priors_xyxy, P, n_classes,
-                                    neg_pos_ratio, norm_mode, losses, obj, cls, dloc, dconf, workspace, workspace_bytes);
-    if (bad == SSD_ERR_NULL) return bad;               // the header's order: null, shape, alignment, workspace
-    if (loc_mode < 0 || loc_mode > 4) return SSD_ERR_BAD_SHAPE;
-    if (with_ign && (n_ign < 0 || (overlap_mode != 0 && overlap_mode != 1))) return SSD_ERR_BAD_SHAPE;
-    if (bad == SSD_ERR_BAD_SHAPE || bad == SSD_ERR_ALIGN) return bad;
-    if (with_ign && n_ign > 0 && !ssd_aligned16(ign_boxes)) return SSD_ERR_ALIGN;
-    if (bad != SSD_OK) return bad;
-    hipStream_t st = (hipStream_t)stream;
-    const LossWs w = carve(workspace, bs, P, n_gt);
-    const int NB = ssd_cdiv(P, LB);
-    const ImageArgs ia{loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, w.partv, w.parti, w.bestv, w.neg,
-                       w.best_prior, obj, cls, w.sel, w.stats, P, n_classes, neg_pos_ratio, NB * 4, iou_threshold, loc_mode};
-    const IgnArgs ga = with_ign ? IgnArgs{ign_boxes, ign_start, ign, ignore_threshold, overlap_mode} : IgnArgs{nullptr, nullptr, nullptr, 0.f, 0};
-    const FinalArgs fa{loc, conf, gt_boxes, priors_cxcywh, obj, cls, w.sel, w.stats, losses, dloc, dconf, P, n_classes, bs, norm_mode, loc_mode};
-    int rc;
-    if (loc_mode == 0)
-        rc = with_ign ? launch_prior_image<true, false>(ia, ga, bs, NB, st) : launch_prior_image<false, false>(ia, ga, bs, NB, st);
-    else
-        rc = with_ign ? launch_prior_image<true, true>(ia, ga, bs, NB, st) : launch_prior_image<false, true>(ia, ga, bs, NB, st);
-    if (rc != SSD_OK) return rc;
-    return loc_mode == 0 ? launch_finalize<false>(fa, st) : launch_finalize<true>(fa, st);
+    const LossCall c{.loc = loc, .conf = conf, .gt_boxes = gt_boxes, .gt_classes = gt_classes, .img_start = img_start, .bs = bs, .n_gt = n_gt,
+                     .priors_cxcywh = priors_cxcywh, .priors_xyxy = priors_xyxy, .P = P, .n_classes = n_classes,
+                     .iou_threshold = iou_threshold, .neg_pos_ratio = neg_pos_ratio, .norm_mode = norm_mode, .with_ign = ign_start != nullptr,
+                     .ign_boxes = ign_boxes, .ign_start = ign_start, .n_ign = n_ign, .ignore_threshold = ignore_threshold,
+                     .overlap_mode = overlap_mode, .loc_mode = loc_mode, .losses = losses, .obj = obj, .cls = cls, .ign = ign, .dloc = dloc,
+                     .dconf = dconf, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream};
+    const int bad = check_loss_call(c);
+    return bad != SSD_OK ? bad : run_loss(c);
 }

@@ -883,15 +883,16 @@ def loc_loss_mode(name):
 def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, iou_threshold=0.5,
                   neg_pos_ratio=3, norm_mode=0, want_grads=True, loc_loss="l1", ignore_boxes=None, ignore_start=None,
                   ignore_threshold=0.5, ignore_overlap="iou"):
-    """-> dict(losses (3,), obj (bs,P) i32, cls (bs,P) i32, dloc, dconf).
+    """-> dict(losses (3,), obj (bs,P) i32, cls (bs,P) i32, dloc, dconf).  `ssd_multibox_loss_box` serves every option; the call without any goes
+    to `ssd_multibox_loss`, the same host path.
     ignore_boxes (n_ign, 4) fractional xyxy with ignore_start (bs + 1,) int32 prefix offsets (both on the device; n_ign may be 0):
-    the loss with ignore regions (`ssd_multibox_loss_ignore`) -- a prior that is not positive and overlaps an ignore box of its
-    image by >= ignore_threshold ("iou", or "ioa" = intersection over the prior's area) is neither mined nor given a gradient; the
-    dict then has "ign" (bs,P) uint8 too.  None: the plain entry.
-    loc_loss: "l1" (the reference's term: exactly the two entries above), or "iou" / "giou" / "diou" / "ciou" -- the entry
-    `ssd_multibox_loss_box`: the predicted box of each positive is decoded (exponent clamped to +-log(1000 / 16)) and losses[0] is the
-    per-positive mean (norm_mode 1: sum) of 1 - IoU plus the mode's penalty, dloc its gradient; everything else is unchanged.  "ciou"
-    needs ground-truth boxes of positive height; "iou" gives no gradient where the two boxes do not overlap."""
+    the loss with ignore regions -- a prior that is not positive and overlaps an ignore box of its image by >= ignore_threshold
+    ("iou", or "ioa" = intersection over the prior's area) is neither mined nor given a gradient; the dict then has "ign" (bs,P)
+    uint8 too.  None: no ignore regions.
+    loc_loss: "l1" (the reference's term), or "iou" / "giou" / "diou" / "ciou": the predicted box of each positive is decoded
+    (exponent clamped to +-log(1000 / 16)) and losses[0] is the per-positive mean (norm_mode 1: sum) of 1 - IoU plus the mode's
+    penalty, dloc its gradient; everything else is unchanged.  "ciou" needs ground-truth boxes of positive height; "iou" gives no
+    gradient where the two boxes do not overlap."""
     mode = ignore_overlap_mode(ignore_overlap)
     loc_mode = loc_loss_mode(loc_loss)
     if (ignore_boxes is None) != (ignore_start is None):
@@ -903,54 +904,33 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
     if tuple(loc.shape) != (bs, p, 4) or tuple(gt_boxes.shape) != (n_gt, 4) or gt_classes.numel() != n_gt or \
             img_start.numel() != bs + 1 or tuple(priors_cxcywh.shape) != (p, 4) or tuple(priors_xyxy.shape) != (p, 4):
         raise ValueError("multibox_loss shapes")
-    lib = _lib.load()
-    ws = workspace(lib.ssd_multibox_loss_workspace(bs, p, n_gt), loc.device, "loss")
-    dev = loc.device
-    losses = torch.empty((3,), device=dev, dtype=torch.float32)
-    obj = torch.empty((bs, p), device=dev, dtype=torch.int32)
-    cls = torch.empty((bs, p), device=dev, dtype=torch.int32)
-    dloc = torch.empty_like(loc) if want_grads else None
-    dconf = torch.empty_like(conf) if want_grads else None
-    if loc_mode != 0:
-        n_ign, ign = 0, None
-        if ignore_boxes is not None:
-            _req(ignore_boxes, "ignore_boxes"); _req(ignore_start, "ignore_start", torch.int32)
-            n_ign = ignore_boxes.shape[0]
-            if tuple(ignore_boxes.shape) != (n_ign, 4) or ignore_start.numel() != bs + 1:
-                raise ValueError("multibox_loss ignore shapes")
-            ign = torch.empty((bs, p), device=dev, dtype=torch.uint8)
-        ws = workspace(lib.ssd_multibox_loss_box_workspace(bs, p, n_gt, n_ign), loc.device, "loss")
-        check(lib.ssd_multibox_loss_box(loc.data_ptr(), conf.data_ptr(), gt_boxes.data_ptr(), gt_classes.data_ptr(),
-                                        img_start.data_ptr(), bs, n_gt, priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, ncls,
-                                        float(iou_threshold), int(neg_pos_ratio), int(norm_mode),
-                                        ignore_boxes.data_ptr() if n_ign else None, _ptr(ignore_start), n_ign,
-                                        float(ignore_threshold), mode, loc_mode, losses.data_ptr(), obj.data_ptr(), cls.data_ptr(),
-                                        _ptr(ign), _ptr(dloc), _ptr(dconf), ws.data_ptr(), ws.numel(), _stream()),
-              "multibox_loss_box")
-        out = dict(losses=losses, obj=obj, cls=cls, dloc=dloc, dconf=dconf)
-        if ign is not None:
-            out["ign"] = ign
-        return out
+    n_ign = 0
     if ignore_boxes is not None:
         _req(ignore_boxes, "ignore_boxes"); _req(ignore_start, "ignore_start", torch.int32)
         n_ign = ignore_boxes.shape[0]
         if tuple(ignore_boxes.shape) != (n_ign, 4) or ignore_start.numel() != bs + 1:
             raise ValueError("multibox_loss ignore shapes")
-        ws = workspace(lib.ssd_multibox_loss_ignore_workspace(bs, p, n_gt, n_ign), loc.device, "loss")
-        ign = torch.empty((bs, p), device=dev, dtype=torch.uint8)
-        check(lib.ssd_multibox_loss_ignore(loc.data_ptr(), conf.data_ptr(), gt_boxes.data_ptr(), gt_classes.data_ptr(),
-                                           img_start.data_ptr(), bs, n_gt, priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, ncls,
-                                           float(iou_threshold), int(neg_pos_ratio), int(norm_mode),
-                                           ignore_boxes.data_ptr() if n_ign else None, ignore_start.data_ptr(), n_ign,
-                                           float(ignore_threshold), mode, losses.data_ptr(), obj.data_ptr(), cls.data_ptr(),
-                                           ign.data_ptr(), _ptr(dloc), _ptr(dconf), ws.data_ptr(), ws.numel(), _stream()),
-              "multibox_loss_ignore")
-        return dict(losses=losses, obj=obj, cls=cls, dloc=dloc, dconf=dconf, ign=ign)
-    check(lib.ssd_multibox_loss(loc.data_ptr(), conf.data_ptr(), gt_boxes.data_ptr(), gt_classes.data_ptr(), img_start.data_ptr(),
-                                bs, n_gt, priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, ncls, float(iou_threshold),
-                                int(neg_pos_ratio), int(norm_mode), losses.data_ptr(), obj.data_ptr(), cls.data_ptr(),
-                                _ptr(dloc), _ptr(dconf), ws.data_ptr(), ws.numel(), _stream()), "multibox_loss")
-    return dict(losses=losses, obj=obj, cls=cls, dloc=dloc, dconf=dconf)
+    lib = _lib.load()
+    dev = loc.device
+    ws = workspace(lib.ssd_multibox_loss_box_workspace(bs, p, n_gt, n_ign), dev, "loss")
+    out = dict(losses=torch.empty((3,), device=dev, dtype=torch.float32),
+               obj=torch.empty((bs, p), device=dev, dtype=torch.int32),
+               cls=torch.empty((bs, p), device=dev, dtype=torch.int32),
+               dloc=torch.empty_like(loc) if want_grads else None,
+               dconf=torch.empty_like(conf) if want_grads else None)
+    if ignore_boxes is not None:
+        out["ign"] = torch.empty((bs, p), device=dev, dtype=torch.uint8)
+    head = (loc.data_ptr(), conf.data_ptr(), gt_boxes.data_ptr(), gt_classes.data_ptr(), img_start.data_ptr(), bs, n_gt,
+            priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, ncls, float(iou_threshold), int(neg_pos_ratio), int(norm_mode))
+    outs = (out["losses"].data_ptr(), out["obj"].data_ptr(), out["cls"].data_ptr())
+    tail = (_ptr(out["dloc"]), _ptr(out["dconf"]), ws.data_ptr(), ws.numel(), _stream())
+    if loc_mode == 0 and ignore_boxes is None:                # (the entry the cross-check switch `ssd_tune_set_loss_form` reaches)
+        check(lib.ssd_multibox_loss(*head, *outs, *tail), "multibox_loss")
+    else:
+        check(lib.ssd_multibox_loss_box(*head, ignore_boxes.data_ptr() if n_ign else None, _ptr(ignore_start), n_ign,
+                                        float(ignore_threshold), mode, loc_mode, *outs, _ptr(out.get("ign")), *tail),
+              "multibox_loss_box" if loc_mode else "multibox_loss_ignore")
+    return out
 
 
 NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}

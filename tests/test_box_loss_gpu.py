@@ -130,9 +130,9 @@ def test_box_loss_equals_the_restatement(case_id, mode, norm_mode):
     assert "ign" not in before[0] and "ign" in before[1]
 
 
-def _raw_box_entry(case_id, norm_mode, loc_mode, with_ignore):
-    """ssd_multibox_loss_box itself (ops.multibox_loss sends "l1" to the two existing entries): loc_mode as given, the ignore pointers
-    given or NULL"""
+def _raw_entry(case_id, norm_mode, with_ignore, loc_mode=None):
+    """A C entry called directly.  loc_mode 0 .. 4: ssd_multibox_loss_box (the entry ops.multibox_loss calls whenever an option is set), the
+    ignore pointers given or NULL.  loc_mode None: the entries without a loc_mode, ssd_multibox_loss_ignore or ssd_multibox_loss."""
     from objectdetection_ssd_amd import _lib, ops
     case, _ = BC.case_and_reference(case_id)
     (loc, conf, gt, gcl, start, pri, pri_xyxy), (ib, ist) = _args(case_id)
@@ -144,12 +144,19 @@ def _raw_box_entry(case_id, norm_mode, loc_mode, with_ignore):
     obj, cls = torch.empty((bs, p), device=DEV, dtype=torch.int32), torch.empty((bs, p), device=DEV, dtype=torch.int32)
     ign = torch.empty((bs, p), device=DEV, dtype=torch.uint8) if with_ignore else None
     dloc, dconf = torch.empty_like(loc), torch.empty_like(conf)
-    ops.check(lib.ssd_multibox_loss_box(loc.data_ptr(), conf.data_ptr(), gt.data_ptr(), gcl.data_ptr(), start.data_ptr(), bs, gt.shape[0],
-                                        pri.data_ptr(), pri_xyxy.data_ptr(), p, ncls, 0.5, case.neg_pos_ratio, norm_mode,
-                                        ib.data_ptr() if n_ign else None, ist.data_ptr() if with_ignore else None, n_ign,
-                                        float(case.threshold), ops.ignore_overlap_mode(case.overlap), loc_mode, losses.data_ptr(),
-                                        obj.data_ptr(), cls.data_ptr(), None if ign is None else ign.data_ptr(), dloc.data_ptr(),
-                                        dconf.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), "multibox_loss_box")
+    head = (loc.data_ptr(), conf.data_ptr(), gt.data_ptr(), gcl.data_ptr(), start.data_ptr(), bs, gt.shape[0], pri.data_ptr(),
+            pri_xyxy.data_ptr(), p, ncls, 0.5, case.neg_pos_ratio, norm_mode)
+    ignore = (ib.data_ptr() if n_ign else None, ist.data_ptr() if with_ignore else None, n_ign, float(case.threshold),
+              ops.ignore_overlap_mode(case.overlap))
+    outs = (losses.data_ptr(), obj.data_ptr(), cls.data_ptr())
+    tail = (dloc.data_ptr(), dconf.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    ign_ptr = None if ign is None else ign.data_ptr()
+    if loc_mode is not None:
+        ops.check(lib.ssd_multibox_loss_box(*head, *ignore, loc_mode, *outs, ign_ptr, *tail), "multibox_loss_box")
+    elif with_ignore:
+        ops.check(lib.ssd_multibox_loss_ignore(*head, *ignore, *outs, ign_ptr, *tail), "multibox_loss_ignore")
+    else:
+        ops.check(lib.ssd_multibox_loss(*head, *outs, *tail), "multibox_loss")
     out = dict(losses=losses, obj=obj, cls=cls, dloc=dloc, dconf=dconf)
     if ign is not None:
         out["ign"] = ign
@@ -160,11 +167,13 @@ def _raw_box_entry(case_id, norm_mode, loc_mode, with_ignore):
 @pytest.mark.parametrize("case_id", ["trained-P777-C21-bs3-near-ignore", "trained-P1000-C81-bs3-noise-ignore", "many_boxes-P1000-C81-bs3-noise",
                                      "many_boxes-P777-C21-bs3-near", "trained-P8732-C21-bs2-near-ignore"])
 def test_loc_mode_0_through_the_new_entry_is_the_existing_entries_bit_for_bit(case_id, norm_mode):
-    _same_bits(_raw_box_entry(case_id, norm_mode, 0, False), _run(case_id, norm_mode, ignore=False))
-    _same_bits(_raw_box_entry(case_id, norm_mode, 0, True), _run(case_id, norm_mode, ignore=True))
+    for with_ignore in (False, True):
+        box0 = _raw_entry(case_id, norm_mode, with_ignore, 0)
+        _same_bits(box0, _raw_entry(case_id, norm_mode, with_ignore))
+        _same_bits(box0, _run(case_id, norm_mode, ignore=with_ignore))
     # and the raw call is the one ops makes for a box mode
-    _same_bits(_raw_box_entry(case_id, norm_mode, 3, True), _run(case_id, norm_mode, "diou", ignore=True))
-    _same_bits(_raw_box_entry(case_id, norm_mode, 3, False), _run(case_id, norm_mode, "diou", ignore=False))
+    _same_bits(_raw_entry(case_id, norm_mode, True, 3), _run(case_id, norm_mode, "diou", ignore=True))
+    _same_bits(_raw_entry(case_id, norm_mode, False, 3), _run(case_id, norm_mode, "diou", ignore=False))
 
 
 @pytest.mark.parametrize("with_ignore", [False, True])
