@@ -555,6 +555,20 @@ int ssd_decode_nms_batch_soft(const float* l_, const float* c_, const float* pri
                               int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
                               float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes, void* stream,
                               int method, float sigma, float keep_score);
+/* The first two stages of the decode alone, for tests and tools, launched exactly as the decode launches them: every prior's box and
+ * class probabilities, the candidates prob >= min_score of every class but the last (NaN is not >=), and their sort.  l_ (B,P,4),
+ * c_ (B,P,n_classes), priors_cxcywh (P,4); n_classes = 2..256, C1 = n_classes - 1, P <= 100000.  Outputs, caller-owned, in the layout
+ * the three entries below consume: boxes (B,P,4) xyxy of every prior; cand_cnt (B, C1+1) candidates per (image, class), the last
+ * entry of an image 0; and per (image, class) the first cand_cnt entries of s_boxes (B,C1,P,4), s_prob (B,C1,P) and s_idx (B,C1,P)
+ * prior ids, in descending order of probability, lower prior index first among equal probabilities.  Slots past a class's count are
+ * not written.  Priors per block: 256 while 256 rows of (n_classes | 1) floats fit 48 KB (n_classes <= 47), 128 while 128 such rows
+ * do (<= 95), else 64.  clear_with_kernel: 0 clears the counters with a memset node, as ssd_decode_nms[_batch] does, 1 with a kernel,
+ * as the Soft-NMS decode does.  l_, priors_cxcywh, boxes, s_boxes and workspace 16-byte aligned; workspace: the candidate keys,
+ * 8 * B * C1 * P bytes rounded up to a multiple of 256. */
+size_t ssd_decode_sorted_workspace(int B, int P, int n_classes);
+int ssd_decode_sorted(const float* l_, const float* c_, const float* priors_cxcywh, int B, int P, int n_classes, float min_score,
+                      float* boxes, float* s_boxes, float* s_prob, int32_t* s_idx, int32_t* cand_cnt, void* workspace,
+                      size_t workspace_bytes, void* stream, int clear_with_kernel);
 /* The Soft-NMS kernel alone, for tests and tools: s_boxes (B,C1,P,4) xyxy and s_prob (B,C1,P) hold, per (image, class), the
  * cand_cnt[b * (C1 + 1) + c] candidates in descending order of probability (cand_cnt is (B, C1+1)); C1 = 1..255.  Outputs, per
  * (image, class) in pick order: kept_pos (B,C1,P) sorted positions, kept_prob (B,C1,P) decayed scores, kept_cnt (B, C1+1) number of

@@ -223,6 +223,8 @@ SIGNATURES = {
     "ssd_decode_nms_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_decode_nms_soft": (_I, [_P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _F, _F]),
     "ssd_decode_nms_batch_soft": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _F, _F]),
+    "ssd_decode_sorted_workspace": (_Z, [_I, _I, _I]),
+    "ssd_decode_sorted": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _Z, _P, _I]),
     "ssd_soft_nms_sorted": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P]),
     "ssd_nms_plan": (_I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ssd_nms_sorted": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),

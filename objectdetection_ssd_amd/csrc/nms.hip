@@ -757,6 +757,49 @@ static int launch_topk(const float* s_boxes, const int32_t* s_idx, const uint32_
     return SSD_OK;
 }
 
+// D1 and D3 as the decode launches them, one place for the decode and for ssd_decode_sorted: the counter clear, decode_compact at the
+// block size its class count asks for, rank_scatter.  cand_cnt is (B, C1 + 1), keys (B, C1, P).
+// The candidate counters of decode_compact are cleared by a memset node, or (clear_with_kernel) by zero_counts_kernel: the Soft-NMS
+// decode is replayed from captured graphs, and a memset node of this size was seen to complete only in part against the work in front
+// of it on replay -- with counters left over, decode_compact and rank_scatter index past their arrays.  The
+// hard rule's launches stay as they were.
+static int launch_decode_sort(const float* l_, const float* c_, const float* priors_cxcywh, int B, int P, int n_classes, float min_score,
+                              float* boxes, uint64_t* keys, int32_t* cand_cnt, float* s_boxes, float* s_prob, int32_t* s_idx,
+                              bool clear_with_kernel, hipStream_t st) {
+    const int C1 = n_classes - 1;
+    if (clear_with_kernel) {
+        hipLaunchKernelGGL(zero_counts_kernel, dim3(ssd_cdiv(n_classes * B, 256)), dim3(256), 0, st, cand_cnt, n_classes * B);
+        SSD_CHECK_LAUNCH();
+    } else if (hipMemsetAsync(cand_cnt, 0, (size_t)n_classes * 4 * B, st) != hipSuccess) return SSD_ERR_LAUNCH;
+    // priors per block: as many as keep the staged rows within 48 KB (256 up to C = 47, C = 21 as always), 64 beyond C = 95
+    const int S = decode_stride(n_classes);
+    const int nt = 256 * S * 4 <= 48 * 1024 ? 256 : (128 * S * 4 <= 48 * 1024 ? 128 : 64);
+    const size_t dlds = (size_t)nt * S * 4;                    // <= 64 x 257 x 4 = 66 KB
+    if (dlds > 48 * 1024) {
+        static std::atomic<unsigned long long> raised{0};
+        int dev;
+        if (ssd_attr_needed(raised, dev)) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(decode_compact_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)((size_t)64 * decode_stride(256) * 4)) != hipSuccess)
+                return SSD_ERR_LAUNCH;
+            ssd_attr_done(raised, dev);
+        }
+    }
+    if (nt == 256)
+        hipLaunchKernelGGL(decode_compact_kernel<256>, dim3(ssd_cdiv(P, 256), 1, B), dim3(256), dlds, st, l_, c_, priors_cxcywh, P,
+                           n_classes, min_score, boxes, keys, cand_cnt);
+    else if (nt == 128)
+        hipLaunchKernelGGL(decode_compact_kernel<128>, dim3(ssd_cdiv(P, 128), 1, B), dim3(128), dlds, st, l_, c_, priors_cxcywh, P,
+                           n_classes, min_score, boxes, keys, cand_cnt);
+    else
+        hipLaunchKernelGGL(decode_compact_kernel<64>, dim3(ssd_cdiv(P, 64), 1, B), dim3(64), dlds, st, l_, c_, priors_cxcywh, P,
+                           n_classes, min_score, boxes, keys, cand_cnt);
+    SSD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(rank_scatter_kernel, dim3(ssd_cdiv(P, 256), C1, B), dim3(256), 0, st, keys, cand_cnt, boxes, P, s_boxes, s_prob, s_idx);
+    SSD_CHECK_LAUNCH();
+    return SSD_OK;
+}
+
 // D1, D3, then D4 (method 0: the greedy rule, nms_kernel) or D4s (method 1 / 2: Soft-NMS, soft_nms_kernel), then D5.
 static int decode_nms_batch_impl(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
                                  int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
@@ -770,42 +813,11 @@ static int decode_nms_batch_impl(const float* l_, const float* c_, const float* 
     hipStream_t st = (hipStream_t)stream;
     const NmsWs w = carve(workspace, P, n_classes, B);
     const int C1 = n_classes - 1;
-    // The candidate counters of decode_compact.  The Soft-NMS decode clears them with a kernel: it is replayed from captured graphs, and a
-    // memset node of this size was seen to complete only in part against the work in front of it on replay -- with
-    // counters left over, decode_compact and rank_scatter index past their arrays.  The hard rule's launches stay as they were.
-    if (method != 0) {
-        hipLaunchKernelGGL(zero_counts_kernel, dim3(ssd_cdiv(n_classes * B, 256)), dim3(256), 0, st, w.cand_cnt, n_classes * B);
-        SSD_CHECK_LAUNCH();
-    } else
-    if (hipMemsetAsync(w.cand_cnt, 0, (size_t)n_classes * 4 * B, st) != hipSuccess) return SSD_ERR_LAUNCH;     // the candidate counters of decode_compact
     {
-        // priors per block: as many as keep the staged rows within 48 KB (256 up to C = 47, C = 21 as always), 64 beyond C = 95
-        const int S = decode_stride(n_classes);
-        const int nt = 256 * S * 4 <= 48 * 1024 ? 256 : (128 * S * 4 <= 48 * 1024 ? 128 : 64);
-        const size_t dlds = (size_t)nt * S * 4;                    // <= 64 x 257 x 4 = 66 KB
-        if (dlds > 48 * 1024) {
-            static std::atomic<unsigned long long> raised{0};
-            int dev;
-            if (ssd_attr_needed(raised, dev)) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(decode_compact_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)((size_t)64 * decode_stride(256) * 4)) != hipSuccess)
-                    return SSD_ERR_LAUNCH;
-                ssd_attr_done(raised, dev);
-            }
-        }
-        if (nt == 256)
-            hipLaunchKernelGGL(decode_compact_kernel<256>, dim3(ssd_cdiv(P, 256), 1, B), dim3(256), dlds, st, l_, c_, priors_cxcywh, P,
-                               n_classes, min_score, w.boxes, w.keys, w.cand_cnt);
-        else if (nt == 128)
-            hipLaunchKernelGGL(decode_compact_kernel<128>, dim3(ssd_cdiv(P, 128), 1, B), dim3(128), dlds, st, l_, c_, priors_cxcywh, P,
-                               n_classes, min_score, w.boxes, w.keys, w.cand_cnt);
-        else
-            hipLaunchKernelGGL(decode_compact_kernel<64>, dim3(ssd_cdiv(P, 64), 1, B), dim3(64), dlds, st, l_, c_, priors_cxcywh, P,
-                               n_classes, min_score, w.boxes, w.keys, w.cand_cnt);
-        SSD_CHECK_LAUNCH();
+        const int rc = launch_decode_sort(l_, c_, priors_cxcywh, B, P, n_classes, min_score, w.boxes, w.keys, w.cand_cnt, w.s_boxes, w.s_prob,
+                                          w.s_idx, method != 0, st);
+        if (rc != SSD_OK) return rc;
     }
-    hipLaunchKernelGGL(rank_scatter_kernel, dim3(ssd_cdiv(P, 256), C1, B), dim3(256), 0, st, w.keys, w.cand_cnt, w.boxes, P, w.s_boxes, w.s_prob, w.s_idx);
-    SSD_CHECK_LAUNCH();
     if (method != 0) {
         const int rc = launch_soft_nms(w.s_boxes, w.s_prob, w.cand_cnt, B, C1, P, method, iou_threshold, sigma, keep_score, top_k, w.kept_pos,
                                        w.kept_prob, w.kept_cnt, st);
@@ -866,6 +878,25 @@ extern "C" int ssd_decode_nms_soft(const float* l_, const float* c_, const float
     if (method != 1 && method != 2) return SSD_ERR_BAD_SHAPE;
     return decode_nms_impl(l_, c_, priors_cxcywh, P, n_classes, min_score, iou_threshold, top_k, img_w, img_h, boxes, classes, probs,
                            prior_ids, count, workspace, workspace_bytes, stream, method, sigma, keep_score);
+}
+
+// D1 + D3 alone, into the caller's arrays: launch_decode_sort as the decode calls it, nothing forced.  The workspace holds the keys.
+extern "C" size_t ssd_decode_sorted_workspace(int B, int P, int n_classes) {
+    if (B <= 0 || P <= 0 || n_classes < 2) return 0;
+    return ((size_t)B * (n_classes - 1) * P * 8 + 255) / 256 * 256;
+}
+
+extern "C" int ssd_decode_sorted(const float* l_, const float* c_, const float* priors_cxcywh, int B, int P, int n_classes, float min_score,
+                                 float* boxes, float* s_boxes, float* s_prob, int32_t* s_idx, int32_t* cand_cnt, void* workspace,
+                                 size_t workspace_bytes, void* stream, int clear_with_kernel) {
+    if (!l_ || !c_ || !priors_cxcywh || !boxes || !s_boxes || !s_prob || !s_idx || !cand_cnt || !workspace) return SSD_ERR_NULL;
+    if (B <= 0 || B > 65535 || P <= 0 || P > 100000 || n_classes < 2 || n_classes > 256) return SSD_ERR_BAD_SHAPE;
+    if (clear_with_kernel != 0 && clear_with_kernel != 1) return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(l_) || !ssd_aligned16(priors_cxcywh) || !ssd_aligned16(boxes) || !ssd_aligned16(s_boxes) || !ssd_aligned16(workspace))
+        return SSD_ERR_ALIGN;
+    if (workspace_bytes < ssd_decode_sorted_workspace(B, P, n_classes)) return SSD_ERR_WORKSPACE;
+    return launch_decode_sort(l_, c_, priors_cxcywh, B, P, n_classes, min_score, boxes, reinterpret_cast<uint64_t*>(workspace), cand_cnt,
+                              s_boxes, s_prob, s_idx, clear_with_kernel == 1, (hipStream_t)stream);
 }
 
 extern "C" int ssd_soft_nms_sorted(const float* s_boxes, const float* s_prob, const int32_t* cand_cnt, int B, int C1, int P, int method,

@@ -174,9 +174,33 @@ def test_bare_entry_points_validate_before_launching():
     """nothing is enqueued for a refused call, so the made-up pointer values are never dereferenced"""
     from objectdetection_ssd_amd import _lib
     lib = _lib.load()
-    for name in ("ssd_nms_plan", "ssd_nms_sorted", "ssd_topk_emit_sorted"):
+    for name in ("ssd_nms_plan", "ssd_nms_sorted", "ssd_topk_emit_sorted", "ssd_decode_sorted", "ssd_decode_sorted_workspace"):
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
     P = OK_PTR
+
+    # the keys: 8 bytes per (image, class, prior), rounded up to 256
+    assert lib.ssd_decode_sorted_workspace(2, 8732, 21) == 2 * 20 * 8732 * 8 == 2794240 and 2794240 % 256 == 0
+    assert lib.ssd_decode_sorted_workspace(1, 1, 2) == 256 and lib.ssd_decode_sorted_workspace(3, 577, 256) == (3 * 255 * 577 * 8 + 255) // 256 * 256
+    assert lib.ssd_decode_sorted_workspace(0, 8732, 21) == lib.ssd_decode_sorted_workspace(1, 0, 21) == lib.ssd_decode_sorted_workspace(1, 8732, 1) == 0
+    dneed = lib.ssd_decode_sorted_workspace(2, 8732, 21)
+
+    def dec(B=2, n=8732, C=21, ws_bytes=dneed, clear=0, **ptr):
+        a = dict(l=P, c=P, pri=P, boxes=P, s_boxes=P, s_prob=P, s_idx=P, cnt=P, ws=P)
+        a.update(ptr)
+        return lib.ssd_decode_sorted(a["l"], a["c"], a["pri"], B, n, C, 0.2, a["boxes"], a["s_boxes"], a["s_prob"], a["s_idx"], a["cnt"],
+                                     a["ws"], ws_bytes, None, clear)
+
+    for name in ("l", "c", "pri", "boxes", "s_boxes", "s_prob", "s_idx", "cnt", "ws"):
+        assert dec(**{name: None}) == -3, name
+    for kw in (dict(B=0), dict(B=65536), dict(n=0), dict(n=100001), dict(C=1), dict(C=257), dict(clear=2), dict(clear=-1)):
+        assert dec(**kw) == -1, kw
+    for name in ("l", "pri", "boxes", "s_boxes", "ws"):
+        assert dec(**{name: ODD_PTR}) == -5, name
+    for name in ("c", "s_prob", "s_idx", "cnt"):                        # read and written four bytes at a time: any float address
+        assert dec(**{name: ODD_PTR}, ws_bytes=dneed - 1) == -2, name
+    assert dec(ws_bytes=dneed - 1) == -2 and dec(ws_bytes=dneed - 1, clear=1) == -2
+    assert dec(B=3, ws_bytes=dneed) == -2 and dec(C=22, ws_bytes=dneed) == -2
+    assert dec(ws=None, ws_bytes=0) == -3 and dec(B=0, ws_bytes=0) == -1 and dec(l=ODD_PTR, ws_bytes=0) == -5     # in that order
 
     def nms(B=1, C1=20, n=8732, boxes=P, prob=P, cnt=P, kpos=P, kprob=P, kcnt=P):
         return lib.ssd_nms_sorted(boxes, prob, cnt, B, C1, n, 0.45, kpos, kprob, kcnt, None)
