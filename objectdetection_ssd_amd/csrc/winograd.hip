@@ -8,6 +8,7 @@
 // The transforms are exact in binary arithmetic up to the usual rounding of their additions (factors 1, 1/2, 1/4); the result
 // differs from the direct sum at the 1e-6 level.  V and M live in a caller-provided workspace (16 planes each).
 #include <cstdlib>
+#include <type_traits>
 //
 // Host side: a forward or data-gradient entry point fills in a WinoConv record (internal.h); its direction's one validator (wino_fwd /
 // wino_dgrad) holds the common rules and hands the record to wino_conv, the one launch sequence.  The weight gradient is wino_wgrad
@@ -25,10 +26,11 @@ struct Lat { int D; int h0[4], w0[4]; };
 // tile row / column t of a map whose lattices start at first[]: offset of its sub-lattice, lattice coordinate of its first OUTPUT row
 __device__ __forceinline__ void lat_tile(const int (&first)[4], int D, int t, int& off, int& base) {
     off = 0;
+    int f = first[0];                                        // = first[off], chosen and not looked up: no load per thread
 #pragma unroll
     for (int a = 1; a < 4; ++a)
-        if (a < D && t >= first[a]) off = a;
-    base = 4 * (t - first[off]);
+        if (a < D && t >= first[a]) { off = a; f = first[a]; }
+    base = 4 * (t - f);
 }
 
 // U[xi][n][k]: rows n = output channels of the GEMM, k = its reduction channels.
@@ -401,13 +403,41 @@ __global__ void wino4_weight_kernel(const float* __restrict__ w, float* __restri
     }
 }
 
+// ---- patch fetch of the F(4x4) transform kernels that write planes (wino4_input_kernel, wino4_dy_kernel) -----------------------------
+// These kernels are HBM streams: what bounds them is how many bytes a CU keeps in flight.  A thread therefore requests its whole patch
+// before it uses any of it, and no request sits behind a branch.  SRD: the tensor is read through a buffer descriptor with one 32-bit
+// byte offset per request; a border or padding element gets an out-of-range offset, for which the hardware range check returns zeros
+// without touching memory (the idiom of the GEMM kernels).  A descriptor spans less than 4 GB: a larger tensor takes the form without
+// (SRD = false: 64-bit addresses, a refused element is not requested), same values.
+constexpr unsigned XF_OOB = 0xFFFFFFF0u;                     // beyond any descriptor extent
+constexpr size_t XF_SRD_MAX = 0xFFFFFF00u;                   // most bytes a tensor may have to be read through a descriptor
+template <bool SRD> using xf_off_t = std::conditional_t<SRD, unsigned, size_t>;      // byte offset into the tensor (wraps like its type)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t xf_srd(const void* base, size_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+template <bool SRD>
+__device__ __forceinline__ f32x4 xf_load16(const void* base, __amdgpu_buffer_rsrc_t srd, xf_off_t<SRD> off, bool ok) {
+    if constexpr (SRD) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd, (int)(ok ? off : XF_OOB), 0, 0));
+    else return ok ? *reinterpret_cast<const f32x4*>(static_cast<const char*>(base) + off) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+template <bool SRD>
+__device__ __forceinline__ uint32_t xf_load4(const void* base, __amdgpu_buffer_rsrc_t srd, xf_off_t<SRD> off, bool ok) {
+    if constexpr (SRD) return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srd, (int)(ok ? off : XF_OOB), 0, 0);
+    else return ok ? *reinterpret_cast<const uint32_t*>(static_cast<const char*>(base) + off) : 0u;
+}
+
 // bits (optional): per (tile, channel quad) one 64-bit word, bit (a*4+b)*4+e = x[4th+a][4tw+b][4c4+e] > 0 -- the ReLU mask of this
 // layer's input on the tile grid its data gradient is written on: the dgrad epilogue then reads 1 bit instead of 32 per element.
-__global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restrict__ x, float* __restrict__ V, int N, int H, int W, int C,
-                                                          int TH, int TW, unsigned long long* __restrict__ bits, const Lat lat) {
+// The 36 patch requests (16 B per lane each) go out together; two waves per SIMD hold 144 patch registers each.
+template <bool SRD>
+__global__ __launch_bounds__(256, SRD ? 2 : 1) void wino4_input_kernel(const float* __restrict__ x, float* __restrict__ V, int N, int H, int W, int C,
+                                                             int TH, int TW, unsigned long long* __restrict__ bits, const Lat lat) {
+    using off_t = xf_off_t<SRD>;
     const int C4 = C >> 2;
     const size_t tiles = (size_t)N * TH * TW, total = tiles * C4;
     const size_t plane = tiles * C;
+    const __amdgpu_buffer_rsrc_t srd = xf_srd(x, (size_t)N * H * W * C * 4);
+    const off_t rs = (off_t)lat.D * (off_t)W * (off_t)C * 4u, cs = (off_t)lat.D * (off_t)C * 4u;      // patch row / column step in bytes
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int c4 = (int)(i % C4);
         const size_t tile = i / C4;
@@ -415,29 +445,41 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
         int offh, bh, offw, bw;
         lat_tile(lat.h0, lat.D, th, offh, bh);
         lat_tile(lat.w0, lat.D, tw, offw, bw);
-        f32x4 t[6][6];                                       // B^T d, one input row at a time
-        unsigned long long word = 0ull;
+        // element (0, 0) of the patch; it may lie before the tensor (row / column -1), and the offset then wraps back for the elements inside
+        const off_t o00 = ((((off_t)n * (off_t)H + (off_t)(lat.D * (bh - 1) + offh)) * (off_t)W + (off_t)(lat.D * (bw - 1) + offw)) * (off_t)C +
+                           (off_t)(c4 * 4)) * 4u;
+        bool okh[6], okw[6];                                 // patch row a / column b inside the map (& not &&: no branches)
 #pragma unroll
-        for (int b = 0; b < 6; ++b) {
-            f32x4 d[6];
-            const int lw = bw - 1 + b, iw = lat.D * lw + offw;
+        for (int a = 0; a < 6; ++a) {
+            const int lh = bh - 1 + a, lw = bw - 1 + a;
+            okh[a] = (lh >= 0) & (lat.D * lh + offh < H);
+            okw[a] = (lw >= 0) & (lat.D * lw + offw < W);
+        }
+        f32x4 d[6][6];                                       // the patch, [row a][column b]
 #pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                const int lh = bh - 1 + a, ih = lat.D * lh + offh;
-                const bool ok = lh >= 0 && lw >= 0 && ih < H && iw < W;
-                d[a] = ok ? *reinterpret_cast<const f32x4*>(x + (((size_t)n * H + ih) * W + iw) * C + c4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-                if (a >= 1 && a <= 4 && b >= 1 && b <= 4) {
+        for (int b = 0; b < 6; ++b)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) word |= (unsigned long long)(d[a][e] > 0.f) << (((a - 1) * 4 + (b - 1)) * 4 + e);
-                }
-            }
+            for (int a = 0; a < 6; ++a) d[a][b] = xf_load16<SRD>(x, srd, o00 + (off_t)a * rs + (off_t)b * cs, okh[a] & okw[b]);
+        __builtin_amdgcn_sched_barrier(0);                   // every request is out before the first use: the scheduler would sink them
+        unsigned long long word = 0ull;                      // from the raw interior values
+#pragma unroll
+        for (int b = 1; b <= 4; ++b)
+#pragma unroll
+            for (int a = 1; a <= 4; ++a)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) word |= (unsigned long long)(d[a][b][e] > 0.f) << (((a - 1) * 4 + (b - 1)) * 4 + e);
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {                        // B^T d, column by column, in place
+            f32x4 col[6];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) col[a] = d[a][b];
 #pragma unroll
             for (int a = 0; a < 6; ++a) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int k = 0; k < 6; ++k)
-                    if (W4_BT[a][k] != 0.f) acc += W4_BT[a][k] * d[k];
-                t[a][b] = acc;
+                    if (W4_BT[a][k] != 0.f) acc += W4_BT[a][k] * col[k];
+                d[a][b] = acc;
             }
         }
         float* dst = V + tile * C + c4 * 4;
@@ -448,7 +490,7 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int k = 0; k < 6; ++k)
-                    if (W4_BT[b][k] != 0.f) acc += W4_BT[b][k] * t[a][k];
+                    if (W4_BT[b][k] != 0.f) acc += W4_BT[b][k] * d[a][k];
                 *reinterpret_cast<f32x4*>(dst + (size_t)(a * 6 + b) * plane) = acc;
             }
         if (bits != nullptr) bits[i] = word;
@@ -672,78 +714,101 @@ __global__ __launch_bounds__(256) void wino4_xform_t_kernel(const float* __restr
 // BIAS: the pass also leaves per-block column sums of dy (the bias gradient) in part[block][Cvalid]; the launch makes the thread
 // count a multiple of C/4, so a thread keeps its channel quad over the grid-stride loop, and a block combines its threads in a fixed order.
 // Vd (optional): the same pass also writes B^T dy B of the 6x6 patch around each block -- the input planes of this layer's dgrad
-// (wino4_input_kernel's output) -- so dy is read from HBM once for both; the 4x4 block is the patch's interior and comes from cache.
+// (wino4_input_kernel's output) -- so dy is read once for both; the 4x4 block is the patch's interior and stays in registers.
 // POOLED: dy is not in memory.  It is the gradient of a 2x2 / stride-2 max pool of this layer's ReLU output, given as the pooled
 // gradient dpool (Hp x Wp), the window argmax codes (byte = 2 * row + column inside the window, as the pool kernels write them) and the
 // pooled forward output (the ReLU gate: > 0).  The 4x4 pooled cells under a 6x6 patch are read once, and dy(ih, iw) = the gated dpool
 // of the cell where the code names (ih & 1, iw & 1), else 0 -- exactly what ssd_maxpool_bwd_gated would have scattered to memory.
 struct PoolSrc { const uint8_t* am; const float* gate; int Hp, Wp; };
-template <bool BIAS, bool POOLED = false>
-__global__ __launch_bounds__(256) void wino4_dy_kernel(const float* __restrict__ dy, float* __restrict__ Y, int N, int H, int W, int C,
-                                                       int TH, int TW, float* __restrict__ part, int Cvalid, float* __restrict__ Vd,
-                                                       const PoolSrc ps, const Lat lat) {
+// Every request of a thread's patch goes out before the first use (xf_load16): the 6x6 patch with the dgrad planes, its 4x4 interior
+// without; POOLED the 4x4 (2x2) pooled cells under it, gradient, gate and codes each.  SRD as in wino4_input_kernel.
+template <bool BIAS, bool POOLED, bool SRD>
+__global__ __launch_bounds__(256, SRD ? 2 : 1) void wino4_dy_kernel(const float* __restrict__ dy, float* __restrict__ Y, int N, int H, int W, int C,
+                                                          int TH, int TW, float* __restrict__ part, int Cvalid, float* __restrict__ Vd,
+                                                          const PoolSrc ps, const Lat lat) {
+    using off_t = xf_off_t<SRD>;
     const int C4 = C >> 2;
     f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
     const size_t tiles = (size_t)N * TH * TW, total = tiles * C4;
     const size_t plane = tiles * C;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    // what the pass reads: dy (N,H,W,C), or the three pooled tensors (N,Hp,Wp,C): gradient, gate, and the codes at a byte per element
+    const size_t src_bytes = POOLED ? (size_t)N * ps.Hp * ps.Wp * C * 4 : (size_t)N * H * W * C * 4;
+    const __amdgpu_buffer_rsrc_t srd_dy = xf_srd(dy, src_bytes), srd_gate = xf_srd(ps.gate, src_bytes), srd_am = xf_srd(ps.am, src_bytes / 4);
+    const off_t rs = (off_t)lat.D * (off_t)W * (off_t)C * 4u, cs = (off_t)lat.D * (off_t)C * 4u;      // patch row / column step in bytes
+    // one (tile, channel quad).  VD: with the dgrad planes, as wino4_input_kernel forms them
+    auto one = [&](auto with_vd, size_t i) {
+        constexpr bool VD = decltype(with_vd)::value;
+        constexpr int P0 = VD ? 0 : 1, P1 = VD ? 6 : 5;      // rows / columns of the patch that are needed
         const int c4 = (int)(i % C4);
         const size_t tile = i / C4;
         const int tw = (int)(tile % TW), th = (int)((tile / TW) % TH), n = (int)(tile / ((size_t)TW * TH));
         int offh, bh, offw, bw;                              // sub-lattice of the tile (POOLED sources are plain: D = 1)
         lat_tile(lat.h0, lat.D, th, offh, bh);
         lat_tile(lat.w0, lat.D, tw, offw, bw);
-        f32x4 pg[4][4];                                      // POOLED: gated pooled gradient and codes of cells (2th-1+r, 2tw-1+q)
-        uint32_t pc[4][4];
-        if (POOLED) {
+        bool okh[6], okw[6];                                 // patch row a / column b inside the map (& not &&: no branches)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool inner = (r == 1 || r == 2) && (q == 1 || q == 2);
-                    const int ph = 2 * th - 1 + r, pw = 2 * tw - 1 + q;
-                    const bool ok = (inner || Vd != nullptr) && (unsigned)ph < (unsigned)ps.Hp && (unsigned)pw < (unsigned)ps.Wp;
-                    f32x4 d = {0.f, 0.f, 0.f, 0.f};
-                    uint32_t a = 0xffffffffu;
-                    if (ok) {
-                        const size_t idx = (((size_t)n * ps.Hp + ph) * ps.Wp + pw) * C4 + c4;
-                        d = *reinterpret_cast<const f32x4*>(dy + idx * 4);
-                        const f32x4 yv = *reinterpret_cast<const f32x4*>(ps.gate + idx * 4);
-                        a = *reinterpret_cast<const uint32_t*>(ps.am + idx * 4);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) d[e] = yv[e] > 0.f ? d[e] : 0.f;
-                    }
-                    pg[r][q] = d;
-                    pc[r][q] = a;
-                }
+        for (int a = 0; a < 6; ++a) {
+            const int lh = bh - 1 + a, lw = bw - 1 + a;
+            okh[a] = (lh >= 0) & (lat.D * lh + offh < H);
+            okw[a] = (lw >= 0) & (lat.D * lw + offw < W);
         }
-        // element (a, b) of the 6x6 patch whose corner is (4th-1, 4tw-1); a, b are compile-time after unrolling
-        auto patch = [&](int a, int b) -> f32x4 {
-            const int lh = bh - 1 + a, lw = bw - 1 + b;
-            const int ih = lat.D * lh + offh, iw = lat.D * lw + offw;
-            const bool ok = lh >= 0 && lw >= 0 && ih < H && iw < W;
-            if (!POOLED)
-                return ok ? *reinterpret_cast<const f32x4*>(dy + (((size_t)n * H + ih) * W + iw) * C + c4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-            const int r = (a + 1) >> 1, q = (b + 1) >> 1;
-            const uint32_t code = (uint32_t)(((a + 1) & 1) * 2 + ((b + 1) & 1));
-            f32x4 g;
+        f32x4 d[6][6];                                       // the 6x6 patch of dy whose corner is (4th-1, 4tw-1), [row][column]
+        if constexpr (POOLED) {
+            constexpr int Q0 = VD ? 0 : 1, Q1 = VD ? 4 : 3;  // pooled cells (2th-1+r, 2tw-1+q) under those rows / columns
+            f32x4 pg[4][4], gt[4][4];
+            uint32_t pc[4][4];
+            // cell (0, 0), in channel quads; it may lie before the tensor, and the index then wraps back for the cells inside
+            const off_t i00 = (((off_t)n * (off_t)ps.Hp + (off_t)(2 * th - 1)) * (off_t)ps.Wp + (off_t)(2 * tw - 1)) * (off_t)C4 + (off_t)c4;
+            const off_t prs = (off_t)ps.Wp * (off_t)C4;      // cell row step (the column step is C4)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) g[e] = (ok && ((pc[r][q] >> (8 * e)) & 0xffu) == code) ? pg[r][q][e] : 0.f;
-            return g;
-        };
-        if (Vd != nullptr) {                                 // uniform: the dgrad planes, as wino4_input_kernel forms them
+            for (int r = Q0; r < Q1; ++r)
+#pragma unroll
+                for (int q = Q0; q < Q1; ++q) {
+                    const int ph = 2 * th - 1 + r, pw = 2 * tw - 1 + q;
+                    const bool ok = ((unsigned)ph < (unsigned)ps.Hp) & ((unsigned)pw < (unsigned)ps.Wp);
+                    const off_t idx = i00 + (off_t)r * prs + (off_t)q * (off_t)C4;
+                    pg[r][q] = xf_load16<SRD>(dy, srd_dy, idx * 16u, ok);
+                    gt[r][q] = xf_load16<SRD>(ps.gate, srd_gate, idx * 16u, ok);
+                    pc[r][q] = xf_load4<SRD>(ps.am, srd_am, idx * 4u, ok);      // a cell outside: gradient 0 under any code
+                }
+            __builtin_amdgcn_sched_barrier(0);               // every request is out before the first use: the scheduler would sink them
+#pragma unroll
+            for (int r = Q0; r < Q1; ++r)
+#pragma unroll
+                for (int q = Q0; q < Q1; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) pg[r][q][e] = gt[r][q][e] > 0.f ? pg[r][q][e] : 0.f;
+            // dy(ih, iw) = the gated gradient of its cell where the code names (ih & 1, iw & 1)
+#pragma unroll
+            for (int b = P0; b < P1; ++b)
+#pragma unroll
+                for (int a = P0; a < P1; ++a) {
+                    const int r = (a + 1) >> 1, q = (b + 1) >> 1;
+                    const uint32_t code = (uint32_t)(((a + 1) & 1) * 2 + ((b + 1) & 1));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        d[a][b][e] = ((okh[a] & okw[b]) & (((pc[r][q] >> (8 * e)) & 0xffu) == code)) ? pg[r][q][e] : 0.f;
+                }
+        } else {
+            // element (0, 0) of the patch; it may lie before the tensor, and the offset then wraps back for the elements inside
+            const off_t o00 = ((((off_t)n * (off_t)H + (off_t)(lat.D * (bh - 1) + offh)) * (off_t)W + (off_t)(lat.D * (bw - 1) + offw)) * (off_t)C +
+                               (off_t)(c4 * 4)) * 4u;
+#pragma unroll
+            for (int b = P0; b < P1; ++b)
+#pragma unroll
+                for (int a = P0; a < P1; ++a) d[a][b] = xf_load16<SRD>(dy, srd_dy, o00 + (off_t)a * rs + (off_t)b * cs, okh[a] & okw[b]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (VD) {
             f32x4 u[6][6];
 #pragma unroll
             for (int b = 0; b < 6; ++b) {
-                f32x4 d[6];
-#pragma unroll
-                for (int a = 0; a < 6; ++a) d[a] = patch(a, b);
 #pragma unroll
                 for (int a = 0; a < 6; ++a) {
                     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int k = 0; k < 6; ++k)
-                        if (W4_BT[a][k] != 0.f) acc += W4_BT[a][k] * d[k];
+                        if (W4_BT[a][k] != 0.f) acc += W4_BT[a][k] * d[k][b];
                     u[a][b] = acc;
                 }
             }
@@ -762,16 +827,16 @@ __global__ __launch_bounds__(256) void wino4_dy_kernel(const float* __restrict__
         f32x4 t[6][4];
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            f32x4 d[4];
+            f32x4 blk[4];
 #pragma unroll
-            for (int a = 0; a < 4; ++a) d[a] = patch(a + 1, b + 1);      // the 4x4 block is the patch's interior (from cache / registers)
-            if (BIAS) bsum += (d[0] + d[1]) + (d[2] + d[3]);
+            for (int a = 0; a < 4; ++a) blk[a] = d[a + 1][b + 1];        // the 4x4 block is the patch's interior
+            if (BIAS) bsum += (blk[0] + blk[1]) + (blk[2] + blk[3]);
 #pragma unroll
             for (int a = 0; a < 6; ++a) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (W4_AT[k][a] != 0.f) acc += W4_AT[k][a] * d[k];
+                    if (W4_AT[k][a] != 0.f) acc += W4_AT[k][a] * blk[k];
                 t[a][b] = acc;
             }
         }
@@ -786,7 +851,12 @@ __global__ __launch_bounds__(256) void wino4_dy_kernel(const float* __restrict__
                     if (W4_AT[k][b] != 0.f) acc += W4_AT[k][b] * t[a][k];
                 *reinterpret_cast<f32x4*>(dst + (size_t)(a * 6 + b) * plane) = acc;
             }
-    }
+    };
+    // uniform: one loop with the dgrad planes, one without
+    if (Vd != nullptr)
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) one(std::true_type{}, i);
+    else
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) one(std::false_type{}, i);
     if (BIAS) {
         __shared__ f32x4 red[256];
         red[threadIdx.x] = bsum;
@@ -1178,19 +1248,32 @@ LatPlan lat_plan(int H, int W, int D) {
     return p;
 }
 
+// the F(4x4) input transform of x (N,H,W,C) into planes V; the descriptor form wherever the tensor fits one
+void launch_input4(const float* x, float* V, int N, int H, int W, int C, const LatPlan& lp, unsigned long long* bits, hipStream_t st) {
+    const dim3 grid(grid_for((size_t)N * lp.TH * lp.TW * (C / 4)));
+    if ((size_t)N * H * W * C * 4 <= XF_SRD_MAX) hipLaunchKernelGGL(wino4_input_kernel<true>, grid, dim3(256), 0, st, x, V, N, H, W, C, lp.TH, lp.TW, bits, lp.lat);
+    else hipLaunchKernelGGL(wino4_input_kernel<false>, grid, dim3(256), 0, st, x, V, N, H, W, C, lp.TH, lp.TW, bits, lp.lat);
+}
+
 // one launch of the dy pass: bias_blocks > 0 = with the bias partial sums on a grid of exactly that many blocks; ps = pooled source or NULL
 void launch_dy_pass(const float* dy, float* Y, const ssd_conv_geom* g, int ldy, const LatPlan& lp, float* part, int bias_blocks, float* Vd,
                     const PoolSrc* ps, hipStream_t st) {
     const int TH = lp.TH, TW = lp.TW;
     const size_t tiles = (size_t)g->N * TH * TW;
-    const PoolSrc none{nullptr, nullptr, 0, 0};
-    if (bias_blocks > 0) {
-        if (ps) hipLaunchKernelGGL((wino4_dy_kernel<true, true>), dim3(bias_blocks), dim3(256), 0, st, dy, Y, g->N, g->H, g->W, ldy, TH, TW, part, g->Co, Vd, *ps, lp.lat);
-        else hipLaunchKernelGGL((wino4_dy_kernel<true, false>), dim3(bias_blocks), dim3(256), 0, st, dy, Y, g->N, g->H, g->W, ldy, TH, TW, part, g->Co, Vd, none, lp.lat);
+    const PoolSrc src = ps ? *ps : PoolSrc{nullptr, nullptr, 0, 0};
+    const bool bias = bias_blocks > 0;
+    const dim3 grid(bias ? bias_blocks : grid_for(tiles * (ldy / 4)));
+    const int cvalid = bias ? g->Co : 0;
+    if (!bias) part = nullptr;
+    // the descriptor form wherever the tensors read fit one (the codes are a quarter of the gradient's bytes)
+    const bool srd = (ps ? (size_t)g->N * ps->Hp * ps->Wp : (size_t)g->N * g->H * g->W) * ldy * 4 <= XF_SRD_MAX;
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, dy, Y, g->N, g->H, g->W, ldy, TH, TW, part, cvalid, Vd, src, lp.lat); };
+    if (srd) {
+        if (bias) ps ? go(wino4_dy_kernel<true, true, true>) : go(wino4_dy_kernel<true, false, true>);
+        else ps ? go(wino4_dy_kernel<false, true, true>) : go(wino4_dy_kernel<false, false, true>);
     } else {
-        const dim3 grid(grid_for(tiles * (ldy / 4)));
-        if (ps) hipLaunchKernelGGL((wino4_dy_kernel<false, true>), grid, dim3(256), 0, st, dy, Y, g->N, g->H, g->W, ldy, TH, TW, static_cast<float*>(nullptr), 0, Vd, *ps, lp.lat);
-        else hipLaunchKernelGGL((wino4_dy_kernel<false, false>), grid, dim3(256), 0, st, dy, Y, g->N, g->H, g->W, ldy, TH, TW, static_cast<float*>(nullptr), 0, Vd, none, lp.lat);
+        if (bias) ps ? go(wino4_dy_kernel<true, true, false>) : go(wino4_dy_kernel<true, false, false>);
+        else ps ? go(wino4_dy_kernel<false, true, false>) : go(wino4_dy_kernel<false, false, false>);
     }
 }
 
@@ -1214,7 +1297,7 @@ int wino_conv(const WinoConv& c, const ssd_conv_geom* g, void* ws, size_t ws_byt
         return ssd_internal_wino4_full(c, (int)tiles, H, W, TH, TW, st);
     if (c.planes != nullptr) V = const_cast<float*>(c.planes);             // input planes already formed (by the dy pass of the wgrad)
     else if (mo == 2) hipLaunchKernelGGL(wino_input_kernel, dim3(grid_for(tiles * (Cin / 4))), dim3(256), 0, st, c.in, V, N, H, W, Cin, TH, TW);
-    else hipLaunchKernelGGL(wino4_input_kernel, dim3(grid_for(tiles * (Cin / 4))), dim3(256), 0, st, c.in, V, N, H, W, Cin, TH, TW, c.bits_out, lp.lat);
+    else launch_input4(c.in, V, N, H, W, Cin, lp, c.bits_out, st);
     SSD_CHECK_LAUNCH();
     if (c.mask_bits != nullptr && mo != 4) return SSD_ERR_BAD_SHAPE;
     if (D == 1 && use_fused(mo, Cin, Cout)) return ssd_internal_wino4_gemm_out(c, V, (int)tiles, H, W, TH, TW, st);
@@ -1590,9 +1673,7 @@ int wino_wgrad(const float* x, const float* planes, const float* dy, int ldy, fl
         // planes in the forward layout [plane][tile][channel]; the GEMM reduces over the tile rows of both.  The x planes are the
         // forward convolution's own B^T d B when the caller kept them.
         launch_dy_pass(dy, Yt, g, ldy, w.lp, part, dy_bias_blocks, dgrad_planes, pool, st);
-        if (planes == nullptr)
-            hipLaunchKernelGGL(wino4_input_kernel, dim3(grid_for(w.tiles * (g->Ci / 4))), dim3(256), 0, st, x, Vt, g->N, g->H, g->W, g->Ci, w.TH,
-                               w.TW, static_cast<unsigned long long*>(nullptr), w.lp.lat);
+        if (planes == nullptr) launch_input4(x, Vt, g->N, g->H, g->W, g->Ci, w.lp, nullptr, st);
         SSD_CHECK_LAUNCH();
         if (int e = wgrad4_tail(Yt, planes != nullptr ? planes : Vt, Zs, part, dy_bias_blocks, dw_oihw, dbias, g, ldy, w, true, st)) return e;
     } else {
