@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 import ssd_oracle as O
+from bn_ref import philox4x32_10 as _philox_np, philox_keep as _keep_np  # noqa: F401
 
 EPS, MOM = 1e-5, 0.1
 BLOCKS = ("conv2d_0", "conv2d_01", "conv2d_02")
@@ -252,32 +253,6 @@ def test_dropout_masks_statistics_and_determinism():
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     assert a[2].keys() == b[2].keys() and all(torch.equal(a[2][k], b[2][k]) for k in a[2])
     assert a[3].keys() == b[3].keys() and len(a[3]) == 30 and all(torch.equal(a[3][k], b[3][k]) for k in a[3])
-
-
-def _philox_np(ctr, key):
-    """numpy uint64 restatement of Philox4x32-10: ctr (4, n), key (2,) -> (4, n) uint32 words"""
-    M = 0xFFFFFFFF
-    c = [v.astype(np.uint64) for v in ctr]
-    k0, k1 = np.uint64(key[0]), np.uint64(key[1])
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[0]
-        p1 = np.uint64(0xCD9E8D57) * c[2]
-        hi0, lo0 = p0 >> np.uint64(32), p0 & np.uint64(M)
-        hi1, lo1 = p1 >> np.uint64(32), p1 & np.uint64(M)
-        c = [hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0]
-        k0 = (k0 + np.uint64(0x9E3779B9)) & np.uint64(M)
-        k1 = (k1 + np.uint64(0xBB67AE85)) & np.uint64(M)
-    return c
-
-
-def _keep_np(seed, site, n, p):
-    idx = np.arange(n, dtype=np.uint64)
-    q = idx >> np.uint64(2)
-    ctr = [q & np.uint64(0xFFFFFFFF), q >> np.uint64(32), np.full(n, site, np.uint64), np.zeros(n, np.uint64)]
-    words = _philox_np(ctr, (seed & 0xFFFFFFFF, seed >> 32))
-    w = np.choose((idx & np.uint64(3)).astype(np.int64), words)
-    u = (w >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
-    return u < float(np.float32(1.0) - np.float32(p))
 
 
 @pytest.mark.gpu
