@@ -436,12 +436,17 @@ int pick_ksplit(int blocks, int kt, size_t tile_elems_total) {
     return k < 2 ? 1 : k;
 }
 
-template <int BM, int BN, int WM, int WN, int NBUF, bool BATCHED = false, bool PARITY = false>
-int launch_igemm(IgemmParams& p, hipStream_t st) {
+// what every igemm launch derives from the tile it picked: the tile grid and the reciprocals of div_small_q
+void set_tiles(IgemmParams& p, int BM, int BN) {
     p.tiles_m = ssd_cdiv(p.M, BM);
     p.tiles_n = ssd_cdiv(p.Nout, BN);
     p.rcp_howo = 1.0f / (float)(p.Ho * p.Wo);
     p.rcp_wo = 1.0f / (float)p.Wo;
+}
+
+template <int BM, int BN, int WM, int WN, int NBUF, bool BATCHED = false, bool PARITY = false>
+int launch_igemm(IgemmParams& p, hipStream_t st) {
+    set_tiles(p, BM, BN);
     const int ks = p.ksplit > 1 ? p.ksplit : 1;
     p.units = 0;
     if (BATCHED && ks == 1 && g_batched_units && p.tiles_m * p.tiles_n >= 8) {
@@ -469,13 +474,12 @@ enum Tile { T256x64 = 0, T128x128 = 1, T128x64 = 2, T64x64 = 3, TAUTO = -1 };
 int g_force_tile = TAUTO, g_force_nbuf = -1;      // tuning aid (ssd_tune_set); -1 = automatic
 
 struct TileChoice { Tile tile; int nbuf; };
-TileChoice pick_tile(int M, int Nout) {
+TileChoice pick_tile() {
     // Measured on MI355X at bs=32 (tools/conv_bench.py, gpurun_out/convbench1.log): on every layer of the
     // network the 64x64 tile with ONE LDS stage (18 KB, 70 registers -> 7 blocks per CU) beats the wider
     // tiles and the double-buffered variants (125-141 vs 95-130 TFLOP/s): with a 64-cycle MFMA, occupancy
     // hides the barrier and staging better than a second stage does, and small tiles quantise better.
     TileChoice c;
-    (void)M; (void)Nout;
     c.tile = T64x64;
     if (g_force_tile != TAUTO) c.tile = (Tile)g_force_tile;
     c.nbuf = 1;
@@ -490,25 +494,18 @@ int plan_ksplit(int M, int Nout, int Ca, int taps) {
     return k > 1 ? ssd_cdiv(kt, ssd_cdiv(kt, k)) : 1;            // no empty slice
 }
 
-int dispatch_igemm(IgemmParams& p, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0) {
-    const TileChoice c = pick_tile(p.M, p.Nout);
+// The launch runs in the `k` K slices a plan asked for where the workspace holds their slab, else whole.
+void set_ksplit(IgemmParams& p, int k, void* ws, size_t ws_bytes) {
     p.ksplit = 1;
-    p.stamps = g_stamps;
-    if (ws != nullptr && c.tile == T64x64) {
-        const int k = plan_ksplit(p.M, p.Nout, p.Ca, p.R * p.S);
-        if (k > 1 && (size_t)k * p.M * p.Nout * sizeof(float) <= ws_bytes) {
-            p.ksplit = k;
-            p.kt_per_split = ssd_cdiv(p.R * p.S * (p.Ca / BK), k);
-            p.slab = static_cast<float*>(ws);
-        }
+    if (ws != nullptr && k > 1 && (size_t)k * p.M * p.Nout * sizeof(float) <= ws_bytes) {
+        p.ksplit = k;
+        p.kt_per_split = ssd_cdiv(p.R * p.S * (p.Ca / BK), k);
+        p.slab = static_cast<float*>(ws);
     }
-    int e;
-    switch (c.tile) {
-        case T256x64: e = c.nbuf == 2 ? launch_igemm<256, 64, 4, 1, 2>(p, st) : launch_igemm<256, 64, 4, 1, 1>(p, st); break;
-        case T128x128: e = c.nbuf == 2 ? launch_igemm<128, 128, 2, 2, 2>(p, st) : launch_igemm<128, 128, 2, 2, 1>(p, st); break;
-        case T128x64: e = c.nbuf == 2 ? launch_igemm<128, 64, 4, 1, 2>(p, st) : launch_igemm<128, 64, 4, 1, 1>(p, st); break;
-        default: e = c.nbuf == 2 ? launch_igemm<64, 64, 2, 2, 2>(p, st) : launch_igemm<64, 64, 2, 2, 1>(p, st); break;
-    }
+}
+
+// after a launch that answered `e`: the reduction of its K slices, where it ran in slices
+int reduce_ksplit(const IgemmParams& p, int e, hipStream_t st) {
     if (e != SSD_OK || p.ksplit <= 1) return e;
     const size_t total = (size_t)p.M * p.Nout;
     const int rb = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
@@ -516,6 +513,20 @@ int dispatch_igemm(IgemmParams& p, hipStream_t st, void* ws = nullptr, size_t ws
                        p.relu, p.accumulate);
     SSD_CHECK_LAUNCH();
     return SSD_OK;
+}
+
+int dispatch_igemm(IgemmParams& p, hipStream_t st, void* ws, size_t ws_bytes) {
+    const TileChoice c = pick_tile();
+    p.stamps = g_stamps;
+    set_ksplit(p, c.tile == T64x64 ? plan_ksplit(p.M, p.Nout, p.Ca, p.R * p.S) : 1, ws, ws_bytes);
+    int e;
+    switch (c.tile) {
+        case T256x64: e = c.nbuf == 2 ? launch_igemm<256, 64, 4, 1, 2>(p, st) : launch_igemm<256, 64, 4, 1, 1>(p, st); break;
+        case T128x128: e = c.nbuf == 2 ? launch_igemm<128, 128, 2, 2, 2>(p, st) : launch_igemm<128, 128, 2, 2, 1>(p, st); break;
+        case T128x64: e = c.nbuf == 2 ? launch_igemm<128, 64, 4, 1, 2>(p, st) : launch_igemm<128, 64, 4, 1, 1>(p, st); break;
+        default: e = c.nbuf == 2 ? launch_igemm<64, 64, 2, 2, 2>(p, st) : launch_igemm<64, 64, 2, 2, 1>(p, st); break;
+    }
+    return reduce_ksplit(p, e, st);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1130,10 +1141,7 @@ int g_x3_tile = -1;          // tuning aid: 1 = 128x128, 2 = 128x64, 3 = 64x64; 
 
 template <int BM, int BN, int WM, int WN>
 int launch_igemm_x3(X3Params& q, hipStream_t st) {
-    q.g.tiles_m = ssd_cdiv(q.g.M, BM);
-    q.g.tiles_n = ssd_cdiv(q.g.Nout, BN);
-    q.g.rcp_howo = 1.0f / (float)(q.g.Ho * q.g.Wo);
-    q.g.rcp_wo = 1.0f / (float)q.g.Wo;
+    set_tiles(q.g, BM, BN);
     hipLaunchKernelGGL((igemm_x3_kernel<BM, BN, WM, WN>), dim3(q.g.tiles_m * q.g.tiles_n), dim3(256), 0, st, q);
     SSD_CHECK_LAUNCH();
     return SSD_OK;
@@ -1169,16 +1177,12 @@ int g_bf16_tile = -1;        // tuning aid: 0 = 256x128, 1 = 128x128, 2 = 128x64
 
 template <int BM, int BN, int WM, int WN>
 int launch_igemm_bf16(IgemmParams& p, hipStream_t st) {
-    p.tiles_m = ssd_cdiv(p.M, BM);
-    p.tiles_n = ssd_cdiv(p.Nout, BN);
-    p.rcp_howo = 1.0f / (float)(p.Ho * p.Wo);
-    p.rcp_wo = 1.0f / (float)p.Wo;
+    set_tiles(p, BM, BN);
     hipLaunchKernelGGL((igemm_bf16_kernel<BM, BN, WM, WN>), dim3(p.tiles_m * p.tiles_n, p.ksplit > 1 ? p.ksplit : 1), dim3(256), 0, st, p);
     SSD_CHECK_LAUNCH();
     return SSD_OK;
 }
 
-int plan_ksplit(int M, int Nout, int Ca, int taps);
 // K slices of a bf16-operand launch on 128 x 128 tiles (1 = none): only where those tiles are chosen (>= 300 of them), fill less than two
 // thirds of the 768 resident workgroups, and every slice keeps at least 32 K steps; the slab is capped at 128 MB
 int plan_ksplit128(int M, int Nout, int Ca, int taps) {
@@ -1192,33 +1196,19 @@ int plan_ksplit128(int M, int Nout, int Ca, int taps) {
     return k < 2 ? 1 : ssd_cdiv(kt, ssd_cdiv(kt, k));
 }
 
-int dispatch_igemm_bf16(IgemmParams& p, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0) {
+int dispatch_igemm_bf16(IgemmParams& p, hipStream_t st, void* ws, size_t ws_bytes) {
     int t = g_bf16_tile;
-    p.ksplit = 1;
     if (t < 0) {
         // measured (tools/conv_bench.py bf16): 128x128 wins once it yields >= ~300 blocks (300-620 TFLOP/s),
         // 128x64 for the 64-channel outputs, 64x64 for the small maps
         const long b128 = (long)ssd_cdiv(p.M, 128) * ssd_cdiv(p.Nout, 128);
         t = p.Nout <= 64 ? 2 : (b128 >= 300 ? 1 : 3);
     }
-    if (t == 1 && ws != nullptr) {
-        // 128 x 128 tiles, three workgroups per CU = 768 resident: a grid that fills less than two thirds of them with a deep K loop
-        // (fc6's data gradient in the bf16 mode: 364 blocks, 288 K steps) runs in K slices (round 4: 0.254 -> 0.202 ms with the reduction)
-        const int k = plan_ksplit128(p.M, p.Nout, p.Ca, p.R * p.S);
-        if (k > 1 && (size_t)k * p.M * p.Nout * sizeof(float) <= ws_bytes) {
-            p.ksplit = k;
-            p.kt_per_split = ssd_cdiv(p.R * p.S * (p.Ca / BK), k);
-            p.slab = static_cast<float*>(ws);
-        }
-    }
-    if (t == 3 && ws != nullptr) {                              // 64 x 64 tiles on a small grid with a deep K loop: K slices + the f32 path's reduction
-        const int k = plan_ksplit(p.M, p.Nout, p.Ca, p.R * p.S);
-        if (k > 1 && (size_t)k * p.M * p.Nout * sizeof(float) <= ws_bytes) {
-            p.ksplit = k;
-            p.kt_per_split = ssd_cdiv(p.R * p.S * (p.Ca / BK), k);
-            p.slab = static_cast<float*>(ws);
-        }
-    }
+    // 128 x 128 tiles, three workgroups per CU = 768 resident: a grid that fills less than two thirds of them with a deep K loop
+    // (fc6's data gradient in the bf16 mode: 364 blocks, 288 K steps) runs in K slices (round 4: 0.254 -> 0.202 ms with the reduction);
+    // 64 x 64 tiles on a small grid with a deep K loop: K slices by the f32 path's rule.  Both end in the f32 path's reduction.
+    const int taps = p.R * p.S;
+    set_ksplit(p, t == 1 ? plan_ksplit128(p.M, p.Nout, p.Ca, taps) : (t == 3 ? plan_ksplit(p.M, p.Nout, p.Ca, taps) : 1), ws, ws_bytes);
     int e;
     switch (t) {
         case 0: e = launch_igemm_bf16<256, 128, 4, 1>(p, st); break;
@@ -1226,13 +1216,25 @@ int dispatch_igemm_bf16(IgemmParams& p, hipStream_t st, void* ws = nullptr, size
         case 2: e = launch_igemm_bf16<128, 64, 4, 1>(p, st); break;
         default: e = launch_igemm_bf16<64, 64, 2, 2>(p, st); break;
     }
-    if (e != SSD_OK || p.ksplit <= 1) return e;
-    const size_t total = (size_t)p.M * p.Nout;
-    const int rb = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rb), dim3(256), 0, st, p.slab, p.ksplit, p.M, p.Nout, p.ldo, p.bias, p.out, p.mask,
-                       p.relu, p.accumulate);
-    SSD_CHECK_LAUNCH();
-    return SSD_OK;
+    return reduce_ksplit(p, e, st);
+}
+
+// stride-2 data gradient on the PARITY kernel: rows grouped by the parity of the dx pixel, every block multiplies only the taps that
+// reach its class
+int launch_dgrad_parity(IgemmParams& p, const ssd_conv_geom* g, hipStream_t st) {
+    int base = 0;
+    for (int c = 0; c < 4; ++c) {
+        const int hc = (g->H + 1 - (c >> 1)) / 2, wc = (g->W + 1 - (c & 1)) / 2;
+        p.par_base[c] = base;
+        p.par_hc[c >> 1] = hc; p.par_wc[c & 1] = wc;
+        base += (g->N * hc * wc + 63) / 64 * 64;
+    }
+    p.par_base[4] = base;
+    p.M_img = g->N;
+    p.M = base;
+    p.ksplit = 1;
+    p.stamps = nullptr;
+    return launch_igemm<64, 64, 2, 2, 1, false, true>(p, st);
 }
 
 int check_geom(const ssd_conv_geom* g) {
@@ -1250,133 +1252,11 @@ int check_geom(const ssd_conv_geom* g) {
 
 }  // namespace
 
-static int conv2d_fwd_impl(const float* x, const float* w_ohwi, const float* bias, float* y, int ldy,
-                           const ssd_conv_geom* g, int relu, void* stream, bool bf16, int accumulate = 0,
-                           void* ws = nullptr, size_t ws_bytes = 0) {
-    if (int e = check_geom(g)) return e;
-    if (!x || !w_ohwi || !y) return SSD_ERR_NULL;
-    if (g->Ci % 32 != 0 || ldy < g->Co) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(x) || !ssd_aligned16(w_ohwi)) return SSD_ERR_ALIGN;
-    IgemmParams p{};
-    p.a = x; p.w = w_ohwi; p.bias = bias; p.out = y; p.mask = nullptr;
-    {
-        const size_t ab = (size_t)g->N * g->H * g->W * g->Ci * 4, wb = (size_t)g->Co * g->R * g->S * g->Ci * 4;
-        if (ab >= 0xF0000000ull || wb >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;   // 32-bit buffer offsets
-        p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    }
-    p.Ha = g->H; p.Wa = g->W; p.Ca = g->Ci; p.Ho = g->Ho; p.Wo = g->Wo;
-    p.Nout = g->Co; p.Nrows = g->Co; p.ldo = ldy; p.R = g->R; p.S = g->S;
-    p.sm = g->stride; p.sd = 1; p.off = -g->pad; p.dstep = g->dil;
-    p.M = g->N * g->Ho * g->Wo; p.relu = relu; p.accumulate = accumulate;
-    return bf16 ? dispatch_igemm_bf16(p, (hipStream_t)stream, ws, ws_bytes) : dispatch_igemm(p, (hipStream_t)stream, ws, ws_bytes);
-}
-
-// Workspace the split-K path of ssd_conv2d_fwd_ws (direction 0) / ssd_conv2d_dgrad_ws (direction 1) wants for this
-// geometry; 0 = the launch is not split (large grids), and the _ws entry points accept workspace == NULL.
-extern "C" size_t ssd_conv2d_igemm_workspace(const ssd_conv_geom* g, int direction) {
-    if (check_geom(g) != SSD_OK) return 0;
-    const int taps = g->R * g->S;
-    if (direction == 0) {
-        if (g->Ci % 32 != 0) return 0;
-        const int M = g->N * g->Ho * g->Wo;
-        const int k = plan_ksplit(M, g->Co, g->Ci, taps), k2 = plan_ksplit128(M, g->Co, g->Ci, taps), km = k > k2 ? k : k2;
-        return km > 1 ? (size_t)km * M * g->Co * sizeof(float) : 0;     // (the bf16-operand path's 128 x 128 rule or the 64 x 64 rule, whichever wants more)
-    }
-    const int M = g->N * g->H * g->W, co_pad = (g->Co + 31) / 32 * 32;
-    const int k = plan_ksplit(M, g->Ci, co_pad, taps), k2 = plan_ksplit128(M, g->Ci, co_pad, taps), km = k > k2 ? k : k2;
-    return km > 1 ? (size_t)km * M * g->Ci * sizeof(float) : 0;
-}
-extern "C" int ssd_conv2d_fwd_ws(const float* x, const float* w_ohwi, const float* bias, float* y, int ldy, const ssd_conv_geom* g,
-                                 int relu, void* workspace, size_t workspace_bytes, void* stream) {
-    if (workspace != nullptr && !ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
-    return conv2d_fwd_impl(x, w_ohwi, bias, y, ldy, g, relu, stream, false, 0, workspace, workspace_bytes);
-}
-
-extern "C" int ssd_conv2d_fwd_accum(const float* x, const float* w_ohwi, const float* bias, float* y_inout, int ldy,
-                                    const ssd_conv_geom* g, int relu, void* stream) {
-    return conv2d_fwd_impl(x, w_ohwi, bias, y_inout, ldy, g, relu, stream, false, 1);
-}
-extern "C" int ssd_conv2d_fwd_accum_bf16(const float* x, const float* w_ohwi, const float* bias, float* y_inout, int ldy,
-                                         const ssd_conv_geom* g, int relu, void* stream) {
-    return conv2d_fwd_impl(x, w_ohwi, bias, y_inout, ldy, g, relu, stream, true, 1);
-}
-
-extern "C" int ssd_conv2d_fwd(const float* x, const float* w_ohwi, const float* bias, float* y, int ldy,
-                              const ssd_conv_geom* g, int relu, void* stream) {
-    return conv2d_fwd_impl(x, w_ohwi, bias, y, ldy, g, relu, stream, false);
-}
-// bf16-operand kernels with the split-K workspace of ssd_conv2d_igemm_workspace (same plan as the f32 kernels: small grids, deep K)
-extern "C" int ssd_conv2d_fwd_bf16_ws(const float* x, const float* w_ohwi, const float* bias, float* y, int ldy, const ssd_conv_geom* g,
-                                      int relu, void* workspace, size_t workspace_bytes, void* stream) {
-    if (workspace != nullptr && !ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
-    return conv2d_fwd_impl(x, w_ohwi, bias, y, ldy, g, relu, stream, true, 0, workspace, workspace_bytes);
-}
-extern "C" int ssd_conv2d_fwd_bf16(const float* x, const float* w_ohwi, const float* bias, float* y, int ldy,
-                                   const ssd_conv_geom* g, int relu, void* stream) {
-    return conv2d_fwd_impl(x, w_ohwi, bias, y, ldy, g, relu, stream, true);
-}
-
-static int conv2d_dgrad_impl(const float* dy, int ldy, const float* w_ihwo, int Co_pad, float* dx,
-                             const float* relu_mask, int accumulate, const ssd_conv_geom* g, void* stream, bool bf16,
-                             void* ws = nullptr, size_t ws_bytes = 0) {
-    if (int e = check_geom(g)) return e;
-    if (!dy || !w_ihwo || !dx) return SSD_ERR_NULL;
-    if (Co_pad % 32 != 0 || Co_pad < g->Co || ldy != Co_pad || g->Ci % 4 != 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(dy) || !ssd_aligned16(w_ihwo)) return SSD_ERR_ALIGN;
-    IgemmParams p{};
-    p.a = dy; p.w = w_ihwo; p.bias = nullptr; p.out = dx; p.mask = relu_mask;
-    {
-        const size_t ab = (size_t)g->N * g->Ho * g->Wo * Co_pad * 4, wb = (size_t)g->Ci * g->R * g->S * Co_pad * 4;
-        if (ab >= 0xF0000000ull || wb >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;
-        p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
-    }
-    p.Ha = g->Ho; p.Wa = g->Wo; p.Ca = Co_pad; p.Ho = g->H; p.Wo = g->W;
-    p.Nout = g->Ci; p.Nrows = g->Ci; p.ldo = g->Ci; p.R = g->R; p.S = g->S;
-    p.sm = 1; p.sd = g->stride; p.off = g->pad; p.dstep = -g->dil;
-    p.M = g->N * g->H * g->W; p.relu = 0; p.accumulate = accumulate;
-    if (!bf16 && g_dgrad_parity && g->stride == 2 && g->dil == 1 && g_force_tile == TAUTO) {
-        // rows grouped by the parity of the dx pixel: every block multiplies only the taps that reach its class
-        int base = 0;
-        for (int c = 0; c < 4; ++c) {
-            const int hc = (g->H + 1 - (c >> 1)) / 2, wc = (g->W + 1 - (c & 1)) / 2;
-            p.par_base[c] = base;
-            p.par_hc[c >> 1] = hc; p.par_wc[c & 1] = wc;
-            base += (g->N * hc * wc + 63) / 64 * 64;
-        }
-        p.par_base[4] = base;
-        p.M_img = g->N;
-        p.M = base;
-        p.ksplit = 1;
-        p.stamps = nullptr;
-        return launch_igemm<64, 64, 2, 2, 1, false, true>(p, (hipStream_t)stream);
-    }
-    return bf16 ? dispatch_igemm_bf16(p, (hipStream_t)stream, ws, ws_bytes) : dispatch_igemm(p, (hipStream_t)stream, ws, ws_bytes);
-}
-
 extern "C" int ssd_tune_set_dgrad_parity(int on) {
     g_dgrad_parity = on != 0;
     return SSD_OK;
 }
 
-extern "C" int ssd_conv2d_dgrad_ws(const float* dy, int ldy, const float* w_ihwo, int Co_pad, float* dx, const float* relu_mask,
-                                   int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream) {
-    if (workspace != nullptr && !ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
-    return conv2d_dgrad_impl(dy, ldy, w_ihwo, Co_pad, dx, relu_mask, accumulate, g, stream, false, workspace, workspace_bytes);
-}
-
-extern "C" int ssd_conv2d_dgrad(const float* dy, int ldy, const float* w_ihwo, int Co_pad, float* dx,
-                                const float* relu_mask, int accumulate, const ssd_conv_geom* g, void* stream) {
-    return conv2d_dgrad_impl(dy, ldy, w_ihwo, Co_pad, dx, relu_mask, accumulate, g, stream, false);
-}
-extern "C" int ssd_conv2d_dgrad_bf16(const float* dy, int ldy, const float* w_ihwo, int Co_pad, float* dx,
-                                     const float* relu_mask, int accumulate, const ssd_conv_geom* g, void* stream) {
-    return conv2d_dgrad_impl(dy, ldy, w_ihwo, Co_pad, dx, relu_mask, accumulate, g, stream, true);
-}
-extern "C" int ssd_conv2d_dgrad_bf16_ws(const float* dy, int ldy, const float* w_ihwo, int Co_pad, float* dx, const float* relu_mask,
-                                        int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream) {
-    if (workspace != nullptr && !ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
-    return conv2d_dgrad_impl(dy, ldy, w_ihwo, Co_pad, dx, relu_mask, accumulate, g, stream, true, workspace, workspace_bytes);
-}
 extern "C" int ssd_tune_set_igemm_bf16(int tile) {
     if (tile < -1 || tile > 3) return SSD_ERR_BAD_SHAPE;
     g_bf16_tile = tile;
@@ -1386,9 +1266,7 @@ extern "C" int ssd_tune_set_igemm_bf16(int tile) {
 extern "C" int ssd_conv2d_igemm_tile(const ssd_conv_geom* g, int direction, int* bm, int* bn) {
     if (int e = check_geom(g)) return e;
     if (!bm || !bn || (direction != 0 && direction != 1)) return SSD_ERR_NULL;
-    const int M = direction == 0 ? g->N * g->Ho * g->Wo : g->N * g->H * g->W;
-    const int Nout = direction == 0 ? g->Co : g->Ci;
-    switch (pick_tile(M, Nout).tile) {
+    switch (pick_tile().tile) {
         case T256x64: *bm = 256; *bn = 64; break;
         case T128x128: *bm = 128; *bn = 128; break;
         case T128x64: *bm = 128; *bn = 64; break;
@@ -1520,7 +1398,7 @@ extern "C" int ssd_prof_gemm_collect_kinds(float* ms_out, double* flops_out, int
     return n;
 }
 
-// ---- "f32 from three bf16 limbs" entry points (opt-in; see igemm_x3_kernel) -----------------------------------
+// the three bf16 limb planes of a filter, for the f32x3 and halo entry points (see igemm_x3_kernel)
 extern "C" int ssd_weight_split_bf16x3(const float* w, void* planes, size_t n, void* stream) {
     if (!w || !planes) return SSD_ERR_NULL;
     if (n == 0) return SSD_OK;
@@ -1529,46 +1407,6 @@ extern "C" int ssd_weight_split_bf16x3(const float* w, void* planes, size_t n, v
                        reinterpret_cast<__bf16*>(planes), n);
     SSD_CHECK_LAUNCH();
     return SSD_OK;
-}
-
-extern "C" int ssd_conv2d_fwd_x3(const float* x, const void* w3_ohwi, int w_rows, const float* bias, float* y, int ldy,
-                                 const ssd_conv_geom* g, int relu, void* stream) {
-    if (int e = check_geom(g)) return e;
-    if (!x || !w3_ohwi || !y) return SSD_ERR_NULL;
-    if (g->Ci % 32 != 0 || ldy < g->Co || w_rows < g->Co) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(x) || !ssd_aligned16(w3_ohwi)) return SSD_ERR_ALIGN;
-    X3Params q{};
-    IgemmParams& p = q.g;
-    p.a = x; p.w = nullptr; p.bias = bias; p.out = y; p.mask = nullptr;
-    const size_t ab = (size_t)g->N * g->H * g->W * g->Ci * 4, pb = (size_t)w_rows * g->R * g->S * g->Ci * 2;
-    if (ab >= 0xF0000000ull || 3 * pb >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;
-    p.a_bytes = (unsigned)ab; q.plane_bytes = (unsigned)pb; q.w3 = reinterpret_cast<const __bf16*>(w3_ohwi);
-    p.Ha = g->H; p.Wa = g->W; p.Ca = g->Ci; p.Ho = g->Ho; p.Wo = g->Wo;
-    p.Nout = g->Co; p.Nrows = g->Co; p.ldo = ldy; p.R = g->R; p.S = g->S;
-    p.sm = g->stride; p.sd = 1; p.off = -g->pad; p.dstep = g->dil;
-    p.M = g->N * g->Ho * g->Wo; p.relu = relu; p.accumulate = 0;
-    { const int h = try_halo<3>(q, g, (hipStream_t)stream); if (h <= 0) return h; }
-    return dispatch_igemm_x3(q, (hipStream_t)stream);
-}
-
-extern "C" int ssd_conv2d_dgrad_x3(const float* dy, int ldy, const void* w3_ihwo, int Co_pad, float* dx,
-                                   const float* relu_mask, int accumulate, const ssd_conv_geom* g, void* stream) {
-    if (int e = check_geom(g)) return e;
-    if (!dy || !w3_ihwo || !dx) return SSD_ERR_NULL;
-    if (Co_pad % 32 != 0 || Co_pad < g->Co || ldy != Co_pad || g->Ci % 4 != 0) return SSD_ERR_BAD_SHAPE;
-    if (!ssd_aligned16(dy) || !ssd_aligned16(w3_ihwo)) return SSD_ERR_ALIGN;
-    X3Params q{};
-    IgemmParams& p = q.g;
-    p.a = dy; p.w = nullptr; p.bias = nullptr; p.out = dx; p.mask = relu_mask;
-    const size_t ab = (size_t)g->N * g->Ho * g->Wo * Co_pad * 4, pb = (size_t)g->Ci * g->R * g->S * Co_pad * 2;
-    if (ab >= 0xF0000000ull || 3 * pb >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;
-    p.a_bytes = (unsigned)ab; q.plane_bytes = (unsigned)pb; q.w3 = reinterpret_cast<const __bf16*>(w3_ihwo);
-    p.Ha = g->Ho; p.Wa = g->Wo; p.Ca = Co_pad; p.Ho = g->H; p.Wo = g->W;
-    p.Nout = g->Ci; p.Nrows = g->Ci; p.ldo = g->Ci; p.R = g->R; p.S = g->S;
-    p.sm = 1; p.sd = g->stride; p.off = g->pad; p.dstep = -g->dil;
-    p.M = g->N * g->H * g->W; p.relu = 0; p.accumulate = accumulate;
-    { const int h = try_halo<3>(q, g, (hipStream_t)stream); if (h <= 0) return h; }
-    return dispatch_igemm_x3(q, (hipStream_t)stream);
 }
 
 extern "C" int ssd_tune_set_igemm_x3(int tile) {
@@ -1588,39 +1426,182 @@ extern "C" int ssd_tune_set_halo(int mode) {
     return SSD_OK;
 }
 
+// ---- one direct convolution (DirectConv, internal.h) from an entry point to its launch: check, fill, launch -----------------------
+namespace {
+
+// The GEMM a direction runs: M rows (pixels of the destination) x N channels, reduced over `taps` taps of C channels each.
+struct GemmView { int M, N, C, taps; };
+GemmView gemm_view(const ssd_conv_geom* g, int dgrad, int Co_pad) {
+    if (dgrad) return {g->N * g->H * g->W, g->Ci, Co_pad, g->R * g->S};
+    return {g->N * g->Ho * g->Wo, g->Co, g->Ci, g->R * g->S};
+}
+
+bool limb_planes(const DirectConv& c) { return c.form == DIRECT_X3 || c.form == DIRECT_HALO1; }
+size_t source_bytes(const DirectConv& c) {
+    const ssd_conv_geom* g = c.g;
+    return c.dgrad ? (size_t)g->N * g->Ho * g->Wo * c.Co_pad * 4 : (size_t)g->N * g->H * g->W * g->Ci * 4;
+}
+size_t filter_bytes(const DirectConv& c) {       // of the f32 filter, or of one bf16 limb plane
+    return (size_t)c.w_rows * c.g->R * c.g->S * (c.dgrad ? c.Co_pad : c.g->Ci) * (limb_planes(c) ? 2 : 4);
+}
+
+// The rules both directions end in: alignment of what the kernels read in 16-byte pieces, then the 32-bit buffer offsets.
+int check_operands(const DirectConv& c) {
+    if (!ssd_aligned16(c.src) || !ssd_aligned16(c.w)) return SSD_ERR_ALIGN;
+    if (source_bytes(c) >= 0xF0000000ull || (limb_planes(c) ? 3 : 1) * filter_bytes(c) >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;
+    return SSD_OK;
+}
+
+int check_fwd(DirectConv& c) {
+    if (c.ws != nullptr && !ssd_aligned16(c.ws)) return SSD_ERR_ALIGN;
+    if (int e = check_geom(c.g)) return e;
+    if (!c.src || !c.w || !c.dst) return SSD_ERR_NULL;
+    if (!limb_planes(c)) c.w_rows = c.g->Co;
+    if (c.g->Ci % 32 != 0 || c.ldy < c.g->Co || c.w_rows < c.g->Co) return SSD_ERR_BAD_SHAPE;
+    return check_operands(c);
+}
+
+int check_dgrad(DirectConv& c) {
+    if (c.ws != nullptr && !ssd_aligned16(c.ws)) return SSD_ERR_ALIGN;
+    if (int e = check_geom(c.g)) return e;
+    if (!c.src || !c.w || !c.dst) return SSD_ERR_NULL;
+    if (c.Co_pad % 32 != 0 || c.Co_pad < c.g->Co || c.ldy != c.Co_pad || c.g->Ci % 4 != 0) return SSD_ERR_BAD_SHAPE;
+    c.w_rows = c.g->Ci;
+    return check_operands(c);
+}
+
+// what the two views share: operands, extents, the GEMM and the epilogue switches
+void fill_common(const DirectConv& c, IgemmParams& p) {
+    const GemmView v = gemm_view(c.g, c.dgrad, c.Co_pad);
+    p.a = c.src; p.bias = c.bias; p.out = c.dst; p.mask = c.mask;
+    p.a_bytes = (unsigned)source_bytes(c);
+    if (!limb_planes(c)) { p.w = static_cast<const float*>(c.w); p.w_bytes = (unsigned)filter_bytes(c); }
+    p.M = v.M; p.Nout = v.N; p.Nrows = v.N; p.Ca = v.C; p.R = c.g->R; p.S = c.g->S;
+    p.relu = c.relu; p.accumulate = c.accumulate;
+}
+
+// forward view: A = x, gather (oh * stride - pad + r * dil, ...)
+void fill_fwd(const DirectConv& c, IgemmParams& p) {
+    const ssd_conv_geom* g = c.g;
+    fill_common(c, p);
+    p.Ha = g->H; p.Wa = g->W; p.Ho = g->Ho; p.Wo = g->Wo; p.ldo = c.ldy;
+    p.sm = g->stride; p.sd = 1; p.off = -g->pad; p.dstep = g->dil;
+}
+
+// data-gradient view: A = dy, gather ((ih + pad - r * dil) / stride, ...) where divisible
+void fill_dgrad(const DirectConv& c, IgemmParams& p) {
+    const ssd_conv_geom* g = c.g;
+    fill_common(c, p);
+    p.Ha = g->Ho; p.Wa = g->Wo; p.Ho = g->H; p.Wo = g->W; p.ldo = g->Ci;
+    p.sm = 1; p.sd = g->stride; p.off = g->pad; p.dstep = -g->dil;
+}
+
+// The one way from a record to its kernels.  The halo forms answer 1 where the geometry is not a halo case: DIRECT_HALO1 hands that to
+// its caller, DIRECT_X3 goes on to the limb igemm.
+int run_direct(DirectConv c, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = c.dgrad ? check_dgrad(c) : check_fwd(c)) return e;
+    X3Params q{};
+    IgemmParams& p = q.g;
+    if (c.dgrad) fill_dgrad(c, p); else fill_fwd(c, p);
+    if (limb_planes(c)) {
+        q.w3 = static_cast<const __bf16*>(c.w); q.plane_bytes = (unsigned)filter_bytes(c);
+        const int h = c.form == DIRECT_X3 ? try_halo<3>(q, c.g, st) : try_halo<1>(q, c.g, st);
+        return h <= 0 || c.form == DIRECT_HALO1 ? h : dispatch_igemm_x3(q, st);
+    }
+    if (c.form == DIRECT_BF16) return dispatch_igemm_bf16(p, st, c.ws, c.ws_bytes);
+    if (c.dgrad && g_dgrad_parity && c.g->stride == 2 && c.g->dil == 1 && g_force_tile == TAUTO) return launch_dgrad_parity(p, c.g, st);
+    return dispatch_igemm(p, st, c.ws, c.ws_bytes);
+}
+
+DirectConv fwd_record(DirectForm form, const float* x, const void* w, int w_rows, const float* bias, float* y, int ldy,
+                      const ssd_conv_geom* g, int relu, int accumulate, void* ws, size_t ws_bytes) {
+    DirectConv c{};
+    c.g = g; c.form = form; c.src = x; c.w = w; c.w_rows = w_rows; c.bias = bias; c.dst = y; c.ldy = ldy;
+    c.relu = relu; c.accumulate = accumulate; c.ws = ws; c.ws_bytes = ws_bytes;
+    return c;
+}
+
+DirectConv dgrad_record(DirectForm form, const float* dy, int ldy, const void* w, int Co_pad, float* dx, const float* relu_mask,
+                        int accumulate, const ssd_conv_geom* g, void* ws, size_t ws_bytes) {
+    DirectConv c{};
+    c.g = g; c.dgrad = 1; c.form = form; c.src = dy; c.ldy = ldy; c.w = w; c.Co_pad = Co_pad; c.dst = dx; c.mask = relu_mask;
+    c.accumulate = accumulate; c.ws = ws; c.ws_bytes = ws_bytes;
+    return c;
+}
+
+}  // namespace
+
+// Workspace the split-K path of ssd_conv2d_fwd_ws (direction 0) / ssd_conv2d_dgrad_ws (direction 1) wants for this
+// geometry; 0 = the launch is not split (large grids), and the _ws entry points accept workspace == NULL.
+extern "C" size_t ssd_conv2d_igemm_workspace(const ssd_conv_geom* g, int direction) {
+    if (check_geom(g) != SSD_OK) return 0;
+    if (direction == 0 && g->Ci % 32 != 0) return 0;
+    const GemmView v = gemm_view(g, direction != 0, (g->Co + 31) / 32 * 32);
+    // the bf16-operand path's 128 x 128 rule or the 64 x 64 rule, whichever wants more
+    const int k = plan_ksplit(v.M, v.N, v.C, v.taps), k2 = plan_ksplit128(v.M, v.N, v.C, v.taps), km = k > k2 ? k : k2;
+    return km > 1 ? (size_t)km * v.M * v.N * sizeof(float) : 0;
+}
+
+// ---- the direct-convolution entry points (include/ssd_gfx950.h): each fills a DirectConv and passes it on ---------------------------
+extern "C" int ssd_conv2d_fwd(const float* x, const float* w_ohwi, const float* bias, float* y, int ldy,
+                              const ssd_conv_geom* g, int relu, void* stream) {
+    return run_direct(fwd_record(DIRECT_F32, x, w_ohwi, 0, bias, y, ldy, g, relu, 0, nullptr, 0), stream);
+}
+extern "C" int ssd_conv2d_fwd_ws(const float* x, const float* w_ohwi, const float* bias, float* y, int ldy, const ssd_conv_geom* g,
+                                 int relu, void* workspace, size_t workspace_bytes, void* stream) {
+    return run_direct(fwd_record(DIRECT_F32, x, w_ohwi, 0, bias, y, ldy, g, relu, 0, workspace, workspace_bytes), stream);
+}
+extern "C" int ssd_conv2d_fwd_accum(const float* x, const float* w_ohwi, const float* bias, float* y_inout, int ldy,
+                                    const ssd_conv_geom* g, int relu, void* stream) {
+    return run_direct(fwd_record(DIRECT_F32, x, w_ohwi, 0, bias, y_inout, ldy, g, relu, 1, nullptr, 0), stream);
+}
+extern "C" int ssd_conv2d_fwd_bf16(const float* x, const float* w_ohwi, const float* bias, float* y, int ldy,
+                                   const ssd_conv_geom* g, int relu, void* stream) {
+    return run_direct(fwd_record(DIRECT_BF16, x, w_ohwi, 0, bias, y, ldy, g, relu, 0, nullptr, 0), stream);
+}
+// bf16-operand kernels with the split-K workspace of ssd_conv2d_igemm_workspace (same plan as the f32 kernels: small grids, deep K)
+extern "C" int ssd_conv2d_fwd_bf16_ws(const float* x, const float* w_ohwi, const float* bias, float* y, int ldy, const ssd_conv_geom* g,
+                                      int relu, void* workspace, size_t workspace_bytes, void* stream) {
+    return run_direct(fwd_record(DIRECT_BF16, x, w_ohwi, 0, bias, y, ldy, g, relu, 0, workspace, workspace_bytes), stream);
+}
+extern "C" int ssd_conv2d_fwd_accum_bf16(const float* x, const float* w_ohwi, const float* bias, float* y_inout, int ldy,
+                                         const ssd_conv_geom* g, int relu, void* stream) {
+    return run_direct(fwd_record(DIRECT_BF16, x, w_ohwi, 0, bias, y_inout, ldy, g, relu, 1, nullptr, 0), stream);
+}
+// "f32 from three bf16 limbs" (opt-in; see igemm_x3_kernel)
+extern "C" int ssd_conv2d_fwd_x3(const float* x, const void* w3_ohwi, int w_rows, const float* bias, float* y, int ldy,
+                                 const ssd_conv_geom* g, int relu, void* stream) {
+    return run_direct(fwd_record(DIRECT_X3, x, w3_ohwi, w_rows, bias, y, ldy, g, relu, 0, nullptr, 0), stream);
+}
 // bf16-operand halo entry points (configs[2]): same pre-split weight planes as f32x3 (plane 0 = RNE bf16 of the weight);
 // geometries the halo kernel does not take return 1 so that the caller uses ssd_conv2d_fwd_bf16 / _dgrad_bf16 instead.
 extern "C" int ssd_conv3x3_halo_fwd_bf16(const float* x, const void* w3_ohwi, int w_rows, const float* bias, float* y, int ldy,
                                          const ssd_conv_geom* g, int relu, void* stream) {
-    if (int e = check_geom(g)) return e;
-    if (!x || !w3_ohwi || !y) return SSD_ERR_NULL;
-    if (g->Ci % 32 != 0 || ldy < g->Co || w_rows < g->Co) return SSD_ERR_BAD_SHAPE;
-    X3Params q{};
-    IgemmParams& p = q.g;
-    p.a = x; p.bias = bias; p.out = y; p.mask = nullptr;
-    const size_t ab = (size_t)g->N * g->H * g->W * g->Ci * 4, pb = (size_t)w_rows * g->R * g->S * g->Ci * 2;
-    if (ab >= 0xF0000000ull || 3 * pb >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;
-    p.a_bytes = (unsigned)ab; q.plane_bytes = (unsigned)pb; q.w3 = reinterpret_cast<const __bf16*>(w3_ohwi);
-    p.Ha = g->H; p.Wa = g->W; p.Ca = g->Ci; p.Ho = g->Ho; p.Wo = g->Wo;
-    p.Nout = g->Co; p.Nrows = g->Co; p.ldo = ldy; p.R = 3; p.S = 3;
-    p.sm = 1; p.sd = 1; p.off = -g->pad; p.dstep = g->dil;
-    p.M = g->N * g->Ho * g->Wo; p.relu = relu; p.accumulate = 0;
-    return try_halo<1>(q, g, (hipStream_t)stream);
+    return run_direct(fwd_record(DIRECT_HALO1, x, w3_ohwi, w_rows, bias, y, ldy, g, relu, 0, nullptr, 0), stream);
+}
+
+extern "C" int ssd_conv2d_dgrad(const float* dy, int ldy, const float* w_ihwo, int Co_pad, float* dx,
+                                const float* relu_mask, int accumulate, const ssd_conv_geom* g, void* stream) {
+    return run_direct(dgrad_record(DIRECT_F32, dy, ldy, w_ihwo, Co_pad, dx, relu_mask, accumulate, g, nullptr, 0), stream);
+}
+extern "C" int ssd_conv2d_dgrad_ws(const float* dy, int ldy, const float* w_ihwo, int Co_pad, float* dx, const float* relu_mask,
+                                   int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream) {
+    return run_direct(dgrad_record(DIRECT_F32, dy, ldy, w_ihwo, Co_pad, dx, relu_mask, accumulate, g, workspace, workspace_bytes), stream);
+}
+extern "C" int ssd_conv2d_dgrad_bf16(const float* dy, int ldy, const float* w_ihwo, int Co_pad, float* dx,
+                                     const float* relu_mask, int accumulate, const ssd_conv_geom* g, void* stream) {
+    return run_direct(dgrad_record(DIRECT_BF16, dy, ldy, w_ihwo, Co_pad, dx, relu_mask, accumulate, g, nullptr, 0), stream);
+}
+extern "C" int ssd_conv2d_dgrad_bf16_ws(const float* dy, int ldy, const float* w_ihwo, int Co_pad, float* dx, const float* relu_mask,
+                                        int accumulate, const ssd_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream) {
+    return run_direct(dgrad_record(DIRECT_BF16, dy, ldy, w_ihwo, Co_pad, dx, relu_mask, accumulate, g, workspace, workspace_bytes), stream);
+}
+extern "C" int ssd_conv2d_dgrad_x3(const float* dy, int ldy, const void* w3_ihwo, int Co_pad, float* dx,
+                                   const float* relu_mask, int accumulate, const ssd_conv_geom* g, void* stream) {
+    return run_direct(dgrad_record(DIRECT_X3, dy, ldy, w3_ihwo, Co_pad, dx, relu_mask, accumulate, g, nullptr, 0), stream);
 }
 extern "C" int ssd_conv3x3_halo_dgrad_bf16(const float* dy, int ldy, const void* w3_ihwo, int Co_pad, float* dx,
                                            const float* relu_mask, int accumulate, const ssd_conv_geom* g, void* stream) {
-    if (int e = check_geom(g)) return e;
-    if (!dy || !w3_ihwo || !dx) return SSD_ERR_NULL;
-    if (Co_pad % 32 != 0 || Co_pad < g->Co || ldy != Co_pad || g->Ci % 4 != 0) return SSD_ERR_BAD_SHAPE;
-    X3Params q{};
-    IgemmParams& p = q.g;
-    p.a = dy; p.bias = nullptr; p.out = dx; p.mask = relu_mask;
-    const size_t ab = (size_t)g->N * g->Ho * g->Wo * Co_pad * 4, pb = (size_t)g->Ci * g->R * g->S * Co_pad * 2;
-    if (ab >= 0xF0000000ull || 3 * pb >= 0xF0000000ull) return SSD_ERR_BAD_SHAPE;
-    p.a_bytes = (unsigned)ab; q.plane_bytes = (unsigned)pb; q.w3 = reinterpret_cast<const __bf16*>(w3_ihwo);
-    p.Ha = g->Ho; p.Wa = g->Wo; p.Ca = Co_pad; p.Ho = g->H; p.Wo = g->W;
-    p.Nout = g->Ci; p.Nrows = g->Ci; p.ldo = g->Ci; p.R = 3; p.S = 3;
-    p.sm = 1; p.sd = g->stride; p.off = g->pad; p.dstep = -g->dil;
-    p.M = g->N * g->H * g->W; p.relu = 0; p.accumulate = accumulate;
-    return try_halo<1>(q, g, (hipStream_t)stream);
+    return run_direct(dgrad_record(DIRECT_HALO1, dy, ldy, w3_ihwo, Co_pad, dx, relu_mask, accumulate, g, nullptr, 0), stream);
 }

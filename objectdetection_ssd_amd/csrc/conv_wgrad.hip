@@ -786,6 +786,7 @@ static int conv2d_wgrad_impl(const float* x, const float* dy, int ldy, float* dw
     const int T = g->R * g->S;
     const int nblk = T * pl.tiles_co * pl.tiles_ci * pl.nsplit;
     if (in_bf16 && !(pl.fused && bf16)) return SSD_ERR_BAD_SHAPE;       // bf16 tensors: the patch kernel only
+    if (T > 49) return SSD_ERR_BAD_SHAPE;                      // the reduction's LDS tile holds up to 7x7 taps
     if (pl.fused && bf16) {
         const dim3 grid(pl.tiles_co * pl.tiles_ci * pl.nsplit);
         const int form = pl.form;
@@ -811,7 +812,6 @@ static int conv2d_wgrad_impl(const float* x, const float* dy, int ldy, float* dw
         else hipLaunchKernelGGL((wgrad_kernel<64, 1>), dim3(nblk), dim3(256), 0, st, p);
     }
     SSD_CHECK_LAUNCH();
-    if (T > 49) return SSD_ERR_BAD_SHAPE;                      // the reduction's LDS tile holds up to 7x7 taps
     const int rblocks = g->Co * ssd_cdiv(g->Ci, 64);
     if (pl.tap_reduce)
         hipLaunchKernelGGL(wgrad_reduce_tap_kernel, dim3(rblocks * T), dim3(256), 0, st, p.slab, dw_oihw, g->Co, g->Ci, T, pl.nsplit,

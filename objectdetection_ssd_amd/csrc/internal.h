@@ -24,6 +24,26 @@ struct WinoConv {
     unsigned long long* bits_out;             // where the input transform writes the bits in > 0 (NULL: nowhere)
 };
 
+// One direct (implicit-GEMM) convolution, forward or data gradient: what it reads and writes.  An entry point of conv_igemm.hip fills in
+// the fields it has and leaves the rest zero; its direction's check fills in w_rows where the entry has none.
+enum DirectForm { DIRECT_F32, DIRECT_BF16, DIRECT_X3, DIRECT_HALO1 };     // f32 / bf16 operands of an f32 filter; three bf16 limb
+                                                                          // planes; the first of them alone (halo kernel only)
+struct DirectConv {
+    const ssd_conv_geom* g;
+    int dgrad;                                // 0: forward, 1: data gradient
+    DirectForm form;
+    const float* src;                         // x (N,H,W,Ci), or dy (N,Ho,Wo,ldy)
+    const void* w;                            // filter OHWI [w_rows][taps][Ci] (data gradient: IHWO [Ci][taps][Co_pad]) or its limb planes
+    int w_rows;                               // rows of a forward filter given as limb planes (else the check's: Co, or Ci)
+    const float* bias;
+    float* dst;                               // y (N,Ho,Wo,ldy), first Co channels, or dx (N,H,W,Ci)
+    int ldy;
+    int Co_pad;                               // data gradient: channels of the IHWO filter rows (= ldy)
+    const float* mask;                        // data gradient: ReLU mask of dx
+    int relu, accumulate;
+    void* ws; size_t ws_bytes;                // split-K slab (may be NULL)
+};
+
 #pragma GCC visibility push(hidden)
 // conv_igemm.hip: the per-launch recorder behind ssd_prof_gemm_begin / _collect.  open returns the slot or -1.
 int ssd_internal_prof_open(double flops, int kind, hipStream_t st);

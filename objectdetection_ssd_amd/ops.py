@@ -145,18 +145,73 @@ def weight_split3(w_layout: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def conv2d_fwd_x3(x: torch.Tensor, w3_ohwi: torch.Tensor, bias: Optional[torch.Tensor], g: ConvGeom, relu: bool,
-                  ld: Optional[int] = None) -> torch.Tensor:
-    _req(x, "x"); _req(w3_ohwi, "w3_ohwi", torch.bfloat16)
+# ---- convolution -----------------------------------------------------------------------
+def _filter(w: torch.Tensor, name: str, limbs: bool):
+    """(rows, taps, channels) of a filter in a kernel layout (OHWI / IHWO), given in f32 or, limbs, as its weight_split3 planes"""
+    _req(w, name, torch.bfloat16 if limbs else torch.float32)
+    if w.dim() != (4 if limbs else 3) or (limbs and w.shape[0] != 3):
+        raise ValueError(f"{name} shape does not match geometry")
+    return tuple(w.shape[-3:])
+
+
+def _fwd_core(x, w, name, limbs, bias, g, ld, out, accumulate):
+    """What every direct forward settles before its library call: the operands against the geometry, and the destination
+    (N,Ho,Wo,ld) -- the caller's, or a fresh one whose columns Co..ld-1 are zero.  -> (out, ld)"""
+    _req(x, "x")
+    rows, taps, ci = _filter(w, name, limbs)
     if tuple(x.shape) != (g.N, g.H, g.W, g.Ci):
-        raise ValueError("x shape does not match geometry")
-    if w3_ohwi.dim() != 4 or w3_ohwi.shape[0] != 3 or w3_ohwi.shape[1] < g.Co or w3_ohwi.shape[2] != g.R * g.S or w3_ohwi.shape[3] != g.Ci:
-        raise ValueError("w3_ohwi shape does not match geometry")
+        raise ValueError(f"x shape {tuple(x.shape)} != geometry {(g.N, g.H, g.W, g.Ci)}")
+    if rows < g.Co or taps != g.R * g.S or ci != g.Ci:
+        raise ValueError(f"{name} shape does not match geometry")
     if bias is not None:
         _req(bias, "bias")
+        if bias.numel() != g.Co:
+            raise ValueError("bias length")
     ld = g.Co if ld is None else ld
-    out = torch.empty((g.N, g.Ho, g.Wo, ld), device=x.device, dtype=torch.float32) if ld == g.Co else \
-        torch.zeros((g.N, g.Ho, g.Wo, ld), device=x.device, dtype=torch.float32)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs an existing out")
+        alloc = torch.empty if ld == g.Co else torch.zeros
+        return alloc((g.N, g.Ho, g.Wo, ld), device=x.device, dtype=torch.float32), ld
+    _req(out, "out")
+    if out.numel() != g.N * g.Ho * g.Wo * ld:
+        raise ValueError("out size")
+    return out, ld
+
+
+def _dgrad_core(dy, w, name, limbs, g, dx, relu_mask, accumulate):
+    """What every direct data gradient settles before its library call: the operands against the geometry, dx (N,H,W,Ci) -- the
+    caller's, or a fresh one -- and the ReLU mask.  -> (dx, co_pad)"""
+    _req(dy, "dy")
+    ci, taps, co_pad = _filter(w, name, limbs)
+    if dy.numel() != g.N * g.Ho * g.Wo * co_pad:
+        raise ValueError(f"dy has {dy.numel()} elements, geometry wants {g.N * g.Ho * g.Wo * co_pad}")
+    if ci != g.Ci or taps != g.R * g.S or co_pad % 32 != 0 or co_pad < g.Co:
+        raise ValueError(f"{name} shape does not match geometry")
+    if dx is None:
+        if accumulate:
+            raise ValueError("accumulate needs an existing dx")
+        dx = torch.empty((g.N, g.H, g.W, g.Ci), device=dy.device, dtype=torch.float32)
+    _req(dx, "dx")
+    if dx.numel() != g.N * g.H * g.W * g.Ci:
+        raise ValueError("dx size")
+    if relu_mask is not None:
+        _req(relu_mask, "relu_mask")
+        if relu_mask.numel() != dx.numel():
+            raise ValueError("relu_mask size")
+    return dx, co_pad
+
+
+def _igemm_ws(g: ConvGeom, direction: int, device):
+    """(pointer, bytes) of the split-K workspace of the _ws entry points: (None, 0) except for small grids with a deep K loop"""
+    nbytes = _lib.load().ssd_conv2d_igemm_workspace(C.byref(g), direction)
+    ws = workspace(nbytes, device, "igemm") if nbytes else None
+    return _ptr(ws), ws.numel() if ws is not None else 0
+
+
+def conv2d_fwd_x3(x: torch.Tensor, w3_ohwi: torch.Tensor, bias: Optional[torch.Tensor], g: ConvGeom, relu: bool,
+                  ld: Optional[int] = None) -> torch.Tensor:
+    out, ld = _fwd_core(x, w3_ohwi, "w3_ohwi", True, bias, g, ld, None, False)
     check(_lib.load().ssd_conv2d_fwd_x3(x.data_ptr(), w3_ohwi.data_ptr(), int(w3_ohwi.shape[1]), _ptr(bias), out.data_ptr(), ld,
                                         C.byref(g), int(relu), _stream()), "conv2d_fwd_x3")
     return out
@@ -164,115 +219,55 @@ def conv2d_fwd_x3(x: torch.Tensor, w3_ohwi: torch.Tensor, bias: Optional[torch.T
 
 def conv2d_dgrad_x3(dy: torch.Tensor, w3_ihwo: torch.Tensor, g: ConvGeom, dx: Optional[torch.Tensor] = None,
                     relu_mask: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
-    _req(dy, "dy"); _req(w3_ihwo, "w3_ihwo", torch.bfloat16)
-    co_pad = w3_ihwo.shape[3]
-    if dy.numel() != g.N * g.Ho * g.Wo * co_pad or w3_ihwo.shape[0] != 3 or w3_ihwo.shape[1] != g.Ci or w3_ihwo.shape[2] != g.R * g.S \
-            or co_pad % 32 != 0:
-        raise ValueError("dgrad_x3 shapes do not match geometry")
-    if dx is None:
-        if accumulate:
-            raise ValueError("accumulate needs an existing dx")
-        dx = torch.empty((g.N, g.H, g.W, g.Ci), device=dy.device, dtype=torch.float32)
-    _req(dx, "dx")
-    if dx.numel() != g.N * g.H * g.W * g.Ci:
-        raise ValueError("dx size")
-    if relu_mask is not None:
-        _req(relu_mask, "relu_mask")
-        if relu_mask.numel() != dx.numel():
-            raise ValueError("relu_mask size")
+    dx, co_pad = _dgrad_core(dy, w3_ihwo, "w3_ihwo", True, g, dx, relu_mask, accumulate)
     check(_lib.load().ssd_conv2d_dgrad_x3(dy.data_ptr(), co_pad, w3_ihwo.data_ptr(), co_pad, dx.data_ptr(), _ptr(relu_mask),
                                           int(accumulate), C.byref(g), _stream()), "conv2d_dgrad_x3")
     return dx
 
 
-# ---- convolution -----------------------------------------------------------------------
 def conv2d_fwd(x: torch.Tensor, w_ohwi: torch.Tensor, bias: Optional[torch.Tensor], g: ConvGeom, relu: bool,
                ld: Optional[int] = None, out: Optional[torch.Tensor] = None, bf16: bool = False,
                w3: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """x (N,H,W,Ci) -> (N,Ho,Wo,ld) (ld defaults to Co; columns Co..ld-1 are left untouched).
-    bf16 with `w3` (weight_split3 of w_ohwi): 3x3/s1/p1 layers on large maps take the halo-tile kernel."""
-    _req(x, "x"); _req(w_ohwi, "w_ohwi")
-    if tuple(x.shape) != (g.N, g.H, g.W, g.Ci):
-        raise ValueError(f"x shape {tuple(x.shape)} != geometry {(g.N, g.H, g.W, g.Ci)}")
-    if w_ohwi.shape[0] < g.Co or w_ohwi.shape[1] != g.R * g.S or w_ohwi.shape[2] != g.Ci:
-        raise ValueError("w_ohwi shape does not match geometry")
-    if bias is not None:
-        _req(bias, "bias")
-        if bias.numel() != g.Co:
-            raise ValueError("bias length")
-    ld = g.Co if ld is None else ld
-    if out is None:
-        out = torch.empty((g.N, g.Ho, g.Wo, ld), device=x.device, dtype=torch.float32) if ld == g.Co else \
-            torch.zeros((g.N, g.Ho, g.Wo, ld), device=x.device, dtype=torch.float32)
-    else:
-        _req(out, "out")
-        if out.numel() != g.N * g.Ho * g.Wo * ld:
-            raise ValueError("out size")
-    if accumulate:                         # out += conv (+ bias), then ReLU: the residual tail of a ResNet BasicBlock
-        if out is None:
-            raise ValueError("accumulate needs an existing out")
-        fn = _lib.load().ssd_conv2d_fwd_accum_bf16 if bf16 else _lib.load().ssd_conv2d_fwd_accum
-        check(fn(x.data_ptr(), w_ohwi.data_ptr(), _ptr(bias), out.data_ptr(), ld, C.byref(g), int(relu), _stream()), "conv2d_fwd_accum")
+    bf16 with `w3` (weight_split3 of w_ohwi): 3x3/s1/p1 layers on large maps take the halo-tile kernel.
+    accumulate: out += conv (+ bias), then ReLU: the residual tail of a ResNet BasicBlock."""
+    out, ld = _fwd_core(x, w_ohwi, "w_ohwi", False, bias, g, ld, out, accumulate)
+    lib = _lib.load()
+    args = (x.data_ptr(), w_ohwi.data_ptr(), _ptr(bias), out.data_ptr(), ld, C.byref(g), int(relu))
+    if accumulate:
+        check((lib.ssd_conv2d_fwd_accum_bf16 if bf16 else lib.ssd_conv2d_fwd_accum)(*args, _stream()), "conv2d_fwd_accum")
         return out
     if bf16 and w3 is not None and g.Ci % 32 == 0:
         _req(w3, "w3", torch.bfloat16)
         if tuple(w3.shape) != (3,) + tuple(w_ohwi.shape):
             raise ValueError("w3 must be weight_split3(w_ohwi)")
-        rc = _lib.load().ssd_conv3x3_halo_fwd_bf16(x.data_ptr(), w3.data_ptr(), int(w3.shape[1]), _ptr(bias), out.data_ptr(), ld,
-                                                   C.byref(g), int(relu), _stream())
+        rc = lib.ssd_conv3x3_halo_fwd_bf16(x.data_ptr(), w3.data_ptr(), int(w3.shape[1]), _ptr(bias), out.data_ptr(), ld,
+                                           C.byref(g), int(relu), _stream())
         if rc <= 0:
             check(rc, "conv3x3_halo_fwd_bf16")
             return out
-    lib = _lib.load()
-    nbytes = lib.ssd_conv2d_igemm_workspace(C.byref(g), 0)             # > 0 only for small grids with a deep K loop
-    ws = workspace(nbytes, x.device, "igemm") if nbytes else None
-    if bf16:
-        check(lib.ssd_conv2d_fwd_bf16_ws(x.data_ptr(), w_ohwi.data_ptr(), _ptr(bias), out.data_ptr(), ld, C.byref(g), int(relu), _ptr(ws),
-                                         ws.numel() if ws is not None else 0, _stream()), "conv2d_fwd_bf16")
-        return out
-    check(lib.ssd_conv2d_fwd_ws(x.data_ptr(), w_ohwi.data_ptr(), _ptr(bias), out.data_ptr(), ld, C.byref(g), int(relu), _ptr(ws),
-                                ws.numel() if ws is not None else 0, _stream()), "conv2d_fwd")
+    fn, what = (lib.ssd_conv2d_fwd_bf16_ws, "conv2d_fwd_bf16") if bf16 else (lib.ssd_conv2d_fwd_ws, "conv2d_fwd")
+    check(fn(*args, *_igemm_ws(g, 0, x.device), _stream()), what)
     return out
 
 
 def conv2d_dgrad(dy: torch.Tensor, w_ihwo: torch.Tensor, g: ConvGeom, dx: Optional[torch.Tensor] = None,
                  relu_mask: Optional[torch.Tensor] = None, accumulate: bool = False, bf16: bool = False,
                  w3: Optional[torch.Tensor] = None) -> torch.Tensor:
-    _req(dy, "dy"); _req(w_ihwo, "w_ihwo")
-    co_pad = w_ihwo.shape[2]
-    if dy.numel() != g.N * g.Ho * g.Wo * co_pad:
-        raise ValueError(f"dy has {dy.numel()} elements, geometry wants {g.N * g.Ho * g.Wo * co_pad}")
-    if w_ihwo.shape[0] != g.Ci or w_ihwo.shape[1] != g.R * g.S or co_pad % 32 != 0 or co_pad < g.Co:
-        raise ValueError("w_ihwo shape does not match geometry")
-    if dx is None:
-        if accumulate:
-            raise ValueError("accumulate needs an existing dx")
-        dx = torch.empty((g.N, g.H, g.W, g.Ci), device=dy.device, dtype=torch.float32)
-    _req(dx, "dx")
-    if dx.numel() != g.N * g.H * g.W * g.Ci:
-        raise ValueError("dx size")
-    if relu_mask is not None:
-        _req(relu_mask, "relu_mask")
-        if relu_mask.numel() != dx.numel():
-            raise ValueError("relu_mask size")
+    dx, co_pad = _dgrad_core(dy, w_ihwo, "w_ihwo", False, g, dx, relu_mask, accumulate)
+    lib = _lib.load()
     if bf16 and w3 is not None and g.Ci % 4 == 0:
         _req(w3, "w3", torch.bfloat16)
         if tuple(w3.shape) != (3,) + tuple(w_ihwo.shape):
             raise ValueError("w3 must be weight_split3(w_ihwo)")
-        rc = _lib.load().ssd_conv3x3_halo_dgrad_bf16(dy.data_ptr(), co_pad, w3.data_ptr(), co_pad, dx.data_ptr(), _ptr(relu_mask),
-                                                     int(accumulate), C.byref(g), _stream())
+        rc = lib.ssd_conv3x3_halo_dgrad_bf16(dy.data_ptr(), co_pad, w3.data_ptr(), co_pad, dx.data_ptr(), _ptr(relu_mask),
+                                             int(accumulate), C.byref(g), _stream())
         if rc <= 0:
             check(rc, "conv3x3_halo_dgrad_bf16")
             return dx
-    lib = _lib.load()
-    nbytes = lib.ssd_conv2d_igemm_workspace(C.byref(g), 1)
-    ws = workspace(nbytes, dy.device, "igemm") if nbytes else None
-    if bf16:
-        check(lib.ssd_conv2d_dgrad_bf16_ws(dy.data_ptr(), co_pad, w_ihwo.data_ptr(), co_pad, dx.data_ptr(), _ptr(relu_mask), int(accumulate),
-                                           C.byref(g), _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "conv2d_dgrad_bf16")
-        return dx
-    check(lib.ssd_conv2d_dgrad_ws(dy.data_ptr(), co_pad, w_ihwo.data_ptr(), co_pad, dx.data_ptr(), _ptr(relu_mask), int(accumulate),
-                                  C.byref(g), _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "conv2d_dgrad")
+    fn, what = (lib.ssd_conv2d_dgrad_bf16_ws, "conv2d_dgrad_bf16") if bf16 else (lib.ssd_conv2d_dgrad_ws, "conv2d_dgrad")
+    check(fn(dy.data_ptr(), co_pad, w_ihwo.data_ptr(), co_pad, dx.data_ptr(), _ptr(relu_mask), int(accumulate), C.byref(g),
+             *_igemm_ws(g, 1, dy.device), _stream()), what)
     return dx
 
 

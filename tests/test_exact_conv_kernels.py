@@ -169,6 +169,8 @@ def _fwd(c, what, relu=True, **kw):
 
 def _fwd_accumulate(c, wf, what, bf16=False):
     from objectdetection_ssd_amd import ops
+    with pytest.raises(ValueError, match="accumulate needs an existing out"):      # not onto fresh, uninitialised memory
+        ops.conv2d_fwd(c.x_nhwc, wf, c.b, c.g, True, bf16=bf16, accumulate=True)
     out, buf = _canvas(tuple(c.y.shape), fill=c.res)
     ops.conv2d_fwd(c.x_nhwc, wf, c.b, c.g, True, out=out, bf16=bf16, accumulate=True)
     _eq(out, (c.res + c.y + c.b).relu(), what)

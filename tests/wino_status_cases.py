@@ -1,23 +1,9 @@
 """The argument tuples of tests/test_wino_status_cpu.py: for every exported Winograd entry point that takes pointers, one valid call on
-a small geometry (made-up pointer values, as in tests/test_host_cpu.py) and that call with every single defect and every pair of
-defects from a fixed list.  Every tuple is one the library must refuse before it enqueues anything; the status it returns --
-which of several applicable ones wins included -- is recorded in tests/golden/wino_status.json (`python tests/wino_status_cases.py
---record`, run against the library the statuses are to be held to, on a machine without a GPU).
-
-An entry's arguments are listed in the order of its C signature, each as (name, kind[, value]):
-  P  required f32 pointer, 16-byte aligned          p  optional one (given in the valid call)      n  optional, not given
-  R  required pointer whose alignment is not checked
-  B / b  required / optional 64-bit mask words (8-byte aligned)          a  optional argmax bytes (4-byte aligned), A required
-  G  the geometry (NULL is a defect too), H the geometry of the layer below (ssd_wino4_adj_output_to_planes)
-  W  the workspace pointer, Zf / Zd / Zw / Zg its size: forward, data-gradient, weight-gradient, weight-gradient-GEMM query
-  i  an int (value given), u a pointer or int no rule looks at (passed as given), S the stream (NULL)
+a small geometry and the defects that entry takes beyond those its argument kinds imply.  tests/status_grid.py explains the argument
+kinds and turns the tables into the grid of single defects and pairs; the recorded statuses are tests/golden/wino_status.json
+(`python tests/wino_status_cases.py --record`, on a machine without a GPU).
 """
-import itertools
-import json
-import os
-
-OK_PTR, ODD_PTR, ODD_BYTES = 0x10000, 0x10004, 0x10002
-FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wino_status.json")
+from status_grid import OK_PTR, Grid
 
 # ops.make_geom arguments of the valid call: 2 x 10 x 10 x 64 -> 64 channels, 3x3 / stride 1 / pad 1
 GEOM = dict(n=2, h=10, w=10, ci=64, co=64, k=3, stride=1, pad=1, dil=1)
@@ -111,100 +97,16 @@ EXTRA = {
     "ssd_wino4_adj_output": _GEOM_ALL + [_DIL4, _CI62],
     "ssd_wino4_adj_output_to_planes": _GEOM_ALL + [_DIL4, _CI62],
 }
-assert set(EXTRA) == set(ENTRIES)
-
-
-def defects(entry):
-    """Every defect of one entry, in a fixed order: those its argument kinds imply, then EXTRA[entry]."""
-    out = []
-    for name, kind, *_ in ENTRIES[entry]:
-        if kind in "PRBAWGH":
-            out.append((f"null:{name}", {name: None}))
-        if kind in "PpnBbW":
-            out.append((f"odd:{name}", {name: ODD_PTR}))
-        if kind in "Aa":
-            out.append((f"odd:{name}", {name: ODD_BYTES}))
-        if kind.startswith("Z"):
-            out.append(("ws-1", {name: -1}))                 # relative to the queried size
-    return out + EXTRA[entry]
-
-
-def cases(entry):
-    """[(label, {argument: value})]: every single defect and every pair that does not set one argument twice"""
-    d = defects(entry)
-    out = [(la, dict(ch)) for la, ch in d]
-    for (la, ca), (lb, cb) in itertools.combinations(d, 2):
-        if not set(ca) & set(cb):
-            out.append((f"{la}+{lb}", {**ca, **cb}))
-    return out
-
-
-def arguments(entry, changes, sizes, make_geom, byref):
-    """The ctypes arguments of `entry` for the valid call (`changes` empty) or a defective one.  sizes: {"Zf": bytes, ...} of the valid
-    geometry; make_geom: ops.make_geom; byref: ctypes.byref.  The geometries are returned too: they must outlive the call."""
-    geom = dict(GEOM, **{k[2:]: v for k, v in changes.items() if k.startswith("g.")})
-    g, below = make_geom(**geom), make_geom(**dict(GEOM, co=GEOM["ci"]))
-    args = []
-    for name, kind, *value in ENTRIES[entry]:
-        if name in changes and not kind.startswith("Z"):
-            v = changes[name]
-            args.append(v if kind not in "GH" else None)
-        elif kind in "PpRBbAW":
-            args.append(OK_PTR)
-        elif kind in "naS":
-            args.append(None)
-        elif kind == "G":
-            args.append(byref(g))
-        elif kind == "H":
-            args.append(byref(below))
-        elif kind.startswith("Z"):
-            args.append(sizes[kind] + changes.get(name, 0))
-        else:
-            args.append(value[0])
-    return args, (g, below)
-
-
 def _sizes(lib, make_geom, byref):
     g = byref(make_geom(**GEOM))
     return {"Zf": lib.ssd_conv3x3_wino_workspace(g, 0, 4), "Zd": lib.ssd_conv3x3_wino_workspace(g, 1, 4),
             "Zw": lib.ssd_conv3x3_wino_wgrad_workspace(g, 64, 4), "Zg": lib.ssd_wino4_wgrad_gemm_workspace(g, 64)}
 
 
-def statuses(lib, make_geom, byref):
-    """{entry: {label: status}} of the loaded library, over every case"""
-    sizes = _sizes(lib, make_geom, byref)
-    assert all(v > 0 for v in sizes.values()), sizes
-    out = {}
-    for entry in ENTRIES:
-        fn = getattr(lib, entry)
-        out[entry] = {}
-        for label, changes in cases(entry):
-            args, keep = arguments(entry, changes, sizes, make_geom, byref)
-            out[entry][label] = fn(*args)
-    return out
-
-
-def _record():
-    """Write the fixture from the importable library.  Refuses where a GPU is present (a tuple the library accepted would be launched
-    on made-up pointers) and where the library accepts any tuple: 0, or SSD_ERR_LAUNCH (-4) from the launch that fails without a GPU."""
-    import ctypes
-    import sys
-    import torch
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from objectdetection_ssd_amd import _lib, ops
-    if torch.cuda.is_available():
-        raise SystemExit("record on a machine without a GPU")
-    got = statuses(_lib.load(), ops.make_geom, ctypes.byref)
-    accepted = [(e, la, s) for e, d in got.items() for la, s in d.items() if s in (0, -4)]
-    if accepted:
-        raise SystemExit("accepted, so no defect of that entry:\n" + "\n".join(f"  {e} {la}: {s}" for e, la, s in accepted))
-    with open(FIXTURE, "w") as f:
-        json.dump(got, f, indent=0, sort_keys=True)
-        f.write("\n")
-    print(f"{sum(len(d) for d in got.values())} cases of {len(got)} entries -> {FIXTURE}")
-
+_GRID = Grid("wino_status.json", ENTRIES, EXTRA, GEOM, _sizes)
+FIXTURE, defects, cases, arguments, statuses = _GRID.fixture, _GRID.defects, _GRID.cases, _GRID.arguments, _GRID.statuses
 
 if __name__ == "__main__":
     import sys
     if "--record" in sys.argv:
-        _record()
+        _GRID.record()
