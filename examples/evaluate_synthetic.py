@@ -46,6 +46,8 @@ def main():
     ap.add_argument("--sweep", action="store_true", help="IoU 0.50:0.05:0.95 instead of 0.5 alone")
     ap.add_argument("--protocol", choices=("voc", "coco"), default="voc", help="coco: the 81-column model and COCO's twelve numbers")
     ap.add_argument("--nms", choices=("hard", "linear", "gaussian"), default="hard", help="suppression rule of the decode")
+    ap.add_argument("--score", choices=("softmax", "sigmoid"), default="softmax",
+                    help="class probabilities of the decode: sigmoid for a model trained with --conf-loss focal")
     ap.add_argument("--keep-score", type=float, default=None, help="Soft-NMS: drop boxes whose decayed score falls below this")
     ap.add_argument("--ema", action="store_true", help="voc protocol: three training steps with a weight EMA, then score with the averaged weights")
     a = ap.parse_args()
@@ -90,7 +92,7 @@ def score_voc(a, cnn, dev):
         gt_boxes, gt_classes, gt_difficult, gt_offsets = ground_truth(a.batch, rng, dev)
         with torch.no_grad():
             loc, conf = cnn(x)
-        boxes, classes, probs, _, count = inference_batch_padded(loc, conf, sizes, min_score=0.02, nms=a.nms, keep_score=a.keep_score)
+        boxes, classes, probs, _, count = inference_batch_padded(loc, conf, sizes, min_score=0.02, nms=a.nms, keep_score=a.keep_score, score=a.score)
         ev.add_batch(boxes, classes, probs, count, gt_boxes, gt_classes, gt_difficult, gt_offsets=gt_offsets)
     res = ev.compute()
     for t, m in zip(res["iou_thresholds"], res["mean_ap"]):
@@ -113,7 +115,7 @@ def main_coco(a, dev):
         gt_area = (gt_boxes[:, 2] - gt_boxes[:, 0]) * (gt_boxes[:, 3] - gt_boxes[:, 1]) * 0.7
         with torch.no_grad():
             loc, conf = cnn(x)
-        boxes, classes, probs, _, count = inference_batch_padded(loc, conf, sizes, min_score=0.02, nms=a.nms, keep_score=a.keep_score)
+        boxes, classes, probs, _, count = inference_batch_padded(loc, conf, sizes, min_score=0.02, nms=a.nms, keep_score=a.keep_score, score=a.score)
         ev.add_batch(boxes, classes, probs, count, gt_boxes, gt_classes, gt_crowd, gt_area, gt_offsets=gt_offsets)
     res = ev.compute()
     for k, v in res["stats"].items():

@@ -103,6 +103,11 @@ def main():
     ap.add_argument("--loc-loss", choices=("l1", "iou", "giou", "diou", "ciou"), default="l1",
                     help="the localisation term (Losses.ssd(loc_loss=...)): the reference's L1 over the encoded offsets, or a box-overlap "
                          "term on the decoded prediction")
+    ap.add_argument("--conf-loss", choices=("ce", "focal"), default="ce",
+                    help="the classification term (Losses.ssd(conf_loss=...)): the reference's cross entropy with hard-negative mining, or "
+                         "the sigmoid focal loss over every prior; focal also starts the heads from SSD_300.init_conf_prior()")
+    ap.add_argument("--focal-alpha", type=float, default=0.25, help="--conf-loss focal: weight of the positives (negative: no weighting)")
+    ap.add_argument("--focal-gamma", type=float, default=2.0, help="--conf-loss focal: exponent of the modulating factor")
     ap.add_argument("--mosaic", type=float, default=0.0, metavar="P",
                     help="compose a sample with probability P of four files, each resized into one quadrant around a random centre "
                          "(mosaic augmentation; feeds from files: implies --decode host unless --decode is given)")
@@ -128,7 +133,12 @@ def main():
         a.fused_sgd = True
         opt_kw.update(max_grad_norm=a.grad_clip, skip_nonfinite=True)
     device = torch.device("cuda")
-    cnn = SSD_300().to(device)
+    cnn = SSD_300()
+    conf_kw = {}
+    if a.conf_loss == "focal":
+        cnn.init_conf_prior()                                 # every prior starts at sigmoid score 0.01 (score with --score sigmoid)
+        conf_kw = dict(conf_loss="focal", focal_alpha=a.focal_alpha, focal_gamma=a.focal_gamma)
+    cnn = cnn.to(device)
     biases = [p for n, p in cnn.named_parameters() if p.requires_grad and n.endswith(".bias")]
     not_biases = [p for n, p in cnn.named_parameters() if p.requires_grad and not n.endswith(".bias")]
     lr = 1e-4
@@ -154,9 +164,9 @@ def main():
         optimizer.zero_grad()
         outputs = cnn(inputs)
         if ignore is None:
-            loss1, loss2 = ssd(outputs, classes, bboxes, loc_loss=a.loc_loss)
+            loss1, loss2 = ssd(outputs, classes, bboxes, loc_loss=a.loc_loss, **conf_kw)
         else:
-            loss1, loss2 = ssd(outputs, classes, bboxes, loc_loss=a.loc_loss, ignore_bboxs=ignore)
+            loss1, loss2 = ssd(outputs, classes, bboxes, loc_loss=a.loc_loss, ignore_bboxs=ignore, **conf_kw)
         loss = loss1 + loss2
         loss.backward()
         optimizer.step()

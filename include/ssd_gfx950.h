@@ -520,6 +520,39 @@ int ssd_multibox_loss_box(const float* loc, const float* conf, const float* gt_b
                           float* losses, int32_t* obj, int32_t* cls, uint8_t* ign, float* dloc, float* dconf, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- MultiBox loss with a choice of classification term (sigmoid focal loss, Lin et al. 2017) ----------
+ * ssd_multibox_loss_box's arguments, meaning and status codes, plus int conf_mode (0 = softmax cross entropy with hard-negative
+ * mining: ssd_multibox_loss_box itself, the same launches, the same bits), float focal_alpha and float focal_gamma.
+ * conf_mode 1: columns 0 .. C-2 of conf are one-against-all logits, column C-1 (the background column) is not read.  Matching, obj,
+ * cls, n_pos and the ignore byte are unchanged; nothing is mined and neg_pos_ratio is not read.  For every prior that is not ignored
+ * and every column c < C-1, with x = conf[i][p][c], t = (cls[i][p] == c), z = t ? x : -x, softplus(u) = max(u, 0) + log1p(exp(-|u|)):
+ *   FL     = a_t exp(-gamma softplus(z)) softplus(-z),       a_t = t ? alpha : 1 - alpha, or 1 where alpha < 0
+ *   dFL/dx = (t ? 1 : -1) a_t exp(-gamma softplus(z)) (-gamma sigmoid(z) softplus(-z) - sigmoid(-z))
+ * (alpha_t (1 - p_t)^gamma times the binary cross entropy with logits; finite for every finite logit; the weight is differentiated,
+ * not detached).  losses[1] = sum of FL / n_pos (norm_mode 0) or the sum (norm_mode 1), reduced in a fixed order: two calls give the
+ * same bits.  dconf is the gradient of that value, +0.0 in column C-1 and in every row of an ignored prior; with dloc == dconf == NULL
+ * only the losses are computed.  losses[0], losses[2], dloc, obj, cls and ign are those of conf_mode 0, bit for bit.
+ * Five launches: the matching (no log-softmax), the per-image pass (no radix select), the finalize pass (dloc, losses[0], losses[2]),
+ * a dense pass over conf (read once, dconf written once) and a one-block sum.  The workspace is ssd_multibox_loss's.
+ * Errors: as ssd_multibox_loss_box; conf_mode outside 0 .. 1, focal_alpha > 1 or NaN, focal_gamma < 0, infinite or NaN are
+ * SSD_ERR_BAD_SHAPE (in either conf_mode). */
+size_t ssd_multibox_loss_focal_workspace(int bs, int P, int n_gt, int n_ign);
+int ssd_multibox_loss_focal(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                            const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh, const float* priors_xyxy,
+                            int P, int n_classes, float iou_threshold, int neg_pos_ratio, int norm_mode, const float* ign_boxes,
+                            const int32_t* ign_start, int n_ign, float ignore_threshold, int overlap_mode, int loc_mode,
+                            int conf_mode, float focal_alpha, float focal_gamma, float* losses, int32_t* obj, int32_t* cls,
+                            uint8_t* ign, float* dloc, float* dconf, void* workspace, size_t workspace_bytes, void* stream);
+/* The dense pass of conf_mode 1 and its sum alone, launched as ssd_multibox_loss_focal launches them, for tests and tools: conf
+ * (bs,P,n_classes), cls (bs,P) int32 class of every prior (n_classes - 1 = background), ign (bs,P) bytes (non-zero: the prior is ignored)
+ * or NULL, n_pos > 0 the divisor of norm_mode 0.  conf_loss[0] receives what losses[1] receives there; dconf (bs,P,n_classes) may be
+ * NULL.  workspace: 4 * bs * ceil(P / 128) bytes rounded up to a multiple of 256, 16-byte aligned.  Status codes in the order null,
+ * shape (the rules of ssd_multibox_loss_focal; n_pos <= 0 or NaN), alignment, workspace. */
+size_t ssd_focal_dense_workspace(int bs, int P);
+int ssd_focal_dense(const float* conf, const int32_t* cls, const uint8_t* ign, int bs, int P, int n_classes, float n_pos, int norm_mode,
+                    float focal_alpha, float focal_gamma, float* conf_loss, float* dconf, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* ---- decode + per-class NMS + top-k (Losses.py:11-98 inference; Util.py:86-96) ----------
  * l_ (P,4), c_ (P,n_classes) of ONE image, n_classes = conf width C, 2..256 (background = C-1 is never a detection).
  * Outputs (capacity top_k): boxes (top_k,4) xyxy scaled by (img_w,img_h,img_w,img_h), classes int64 (0..C-2), probs f32,
@@ -555,6 +588,21 @@ int ssd_decode_nms_batch_soft(const float* l_, const float* c_, const float* pri
                               int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
                               float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes, void* stream,
                               int method, float sigma, float keep_score);
+/* The decode with a choice of score, for a model trained with the sigmoid focal term (ssd_multibox_loss_focal): the arguments of
+ * ssd_decode_nms[_batch]_soft -- method 0 = the greedy rule (sigma and keep_score are then not read), 1 / 2 = Soft-NMS -- followed by
+ * score_mode: 0 = softmax over the C columns (ssd_decode_nms[_batch][_soft] itself, the same launches), 1 = the probability of class
+ * c in 0 .. C-2 is sigmoid(c_[.., c]), computed as 1 / (1 + exp(-|x|)), times exp(-|x|) where x < 0 (no overflow; exactly 1.0 for
+ * large x); the value of the background column C-1 takes no part.  Everything after the score -- the candidate keys, their sort,
+ * both suppression rules, the cross-class top-k -- is unchanged, as are the workspaces.  Another method or score_mode:
+ * SSD_ERR_BAD_SHAPE. */
+int ssd_decode_nms_score(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
+                         float min_score, float iou_threshold, int top_k, float img_w, float img_h,
+                         float* boxes, int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count,
+                         void* workspace, size_t workspace_bytes, void* stream, int method, float sigma, float keep_score, int score_mode);
+int ssd_decode_nms_batch_score(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
+                               int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
+                               float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes, void* stream,
+                               int method, float sigma, float keep_score, int score_mode);
 /* The first two stages of the decode alone, for tests and tools, launched exactly as the decode launches them: every prior's box and
  * class probabilities, the candidates prob >= min_score of every class but the last (NaN is not >=), and their sort.  l_ (B,P,4),
  * c_ (B,P,n_classes), priors_cxcywh (P,4); n_classes = 2..256, C1 = n_classes - 1, P <= 100000.  Outputs, caller-owned, in the layout
@@ -569,6 +617,10 @@ size_t ssd_decode_sorted_workspace(int B, int P, int n_classes);
 int ssd_decode_sorted(const float* l_, const float* c_, const float* priors_cxcywh, int B, int P, int n_classes, float min_score,
                       float* boxes, float* s_boxes, float* s_prob, int32_t* s_idx, int32_t* cand_cnt, void* workspace,
                       size_t workspace_bytes, void* stream, int clear_with_kernel);
+/* ssd_decode_sorted with score_mode as in ssd_decode_nms_score (0 is ssd_decode_sorted itself; another value: SSD_ERR_BAD_SHAPE) */
+int ssd_decode_sorted_score(const float* l_, const float* c_, const float* priors_cxcywh, int B, int P, int n_classes, float min_score,
+                            float* boxes, float* s_boxes, float* s_prob, int32_t* s_idx, int32_t* cand_cnt, void* workspace,
+                            size_t workspace_bytes, void* stream, int clear_with_kernel, int score_mode);
 /* The Soft-NMS kernel alone, for tests and tools: s_boxes (B,C1,P,4) xyxy and s_prob (B,C1,P) hold, per (image, class), the
  * cand_cnt[b * (C1 + 1) + c] candidates in descending order of probability (cand_cnt is (B, C1+1)); C1 = 1..255.  Outputs, per
  * (image, class) in pick order: kept_pos (B,C1,P) sorted positions, kept_prob (B,C1,P) decayed scores, kept_cnt (B, C1+1) number of

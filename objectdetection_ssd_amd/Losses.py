@@ -46,12 +46,15 @@ def _priors_on(dev: torch.device, n_priors: int = 8732):
 
 class _MultiBoxLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, loc, conf, gt, gt_cls, img_start, norm_mode, ignore=None, loc_loss="l1"):
+    def forward(ctx, loc, conf, gt, gt_cls, img_start, norm_mode, ignore=None, loc_loss="l1", conf_loss="ce", focal_alpha=0.25,
+                focal_gamma=2.0):
         pri, pri_xyxy = _priors_on(loc.device, loc.shape[1])
         want = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         kw = {}
         if ignore is not None:                           # (boxes, starts, threshold, overlap): the entry with ignore regions
             kw = dict(ignore_boxes=ignore[0], ignore_start=ignore[1], ignore_threshold=ignore[2], ignore_overlap=ignore[3])
+        if conf_loss != "ce":                            # (the default call stays the call it has always been)
+            kw.update(conf_loss=conf_loss, focal_alpha=focal_alpha, focal_gamma=focal_gamma)
         out = ops.multibox_loss(loc.detach().contiguous(), conf.detach().contiguous(), gt, gt_cls, img_start, pri, pri_xyxy,
                                 IOU_THRESHOLD, NEG_POS_RATIO, norm_mode, want_grads=want, loc_loss=loc_loss, **kw)
         ctx.dloc, ctx.dconf = out["dloc"], out["dconf"]
@@ -65,7 +68,7 @@ class _MultiBoxLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loc, g_conf, _g_npos):
         # loc_loss depends on loc only, conf_loss on conf only
-        return ctx.dloc * g_loc, ctx.dconf * g_conf, None, None, None, None, None, None
+        return ctx.dloc * g_loc, ctx.dconf * g_conf, None, None, None, None, None, None, None, None, None
 
 
 def _image_starts(start, dev: torch.device) -> torch.Tensor:
@@ -106,8 +109,8 @@ def _pack_ignore(ignore_bboxs, dev: torch.device):
     return boxes, _image_starts(start, dev)
 
 
-def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = False, loc_loss: str = "l1", ignore_bboxs=None,
-        ignore_threshold: float = 0.5, ignore_overlap: str = "iou"):
+def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = False, loc_loss: str = "l1", conf_loss: str = "ce",
+        focal_alpha: float = 0.25, focal_gamma: float = 2.0, ignore_bboxs=None, ignore_threshold: float = 0.5, ignore_overlap: str = "iou"):
     """outputs = (loc (bs,8732,4), conf (bs,8732,C)); tr_classes: list of (n_i,) float tensors with values
     0..C-2 (C = conf.shape[-1] = foreground classes + background, 21 for VOC; background = C-1); tr_bboxs: list of
     (n_i,4) xyxy fractional boxes.  Returns (loc_loss, conf_loss) as 0-dim tensors
@@ -123,9 +126,17 @@ def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = Fa
     width / height is clamped to +-log(1000 / 16), a clamped coordinate gets gradient 0).  loc_loss is then the mean over the
     positives (norm_mode 1: the sum); matching, mining, conf_loss and its gradient are the same.  "ciou" needs ground-truth boxes
     of positive height; "iou" has no gradient where prediction and box do not overlap.  A weight on the term is the caller's: scale
-    the returned tensor."""
+    the returned tensor.
+    conf_loss: "ce" (the reference's softmax cross entropy with 3:1 hard-negative mining, the default), or "focal": the sigmoid
+    focal loss of Lin et al. 2017 over the foreground columns 0..C-2 of every prior that is not ignored -- alpha_t (1 - p_t)^gamma
+    times the binary cross entropy, focal_alpha in [0, 1] (negative: no alpha weighting), focal_gamma >= 0 -- summed and divided by
+    the number of positives (norm_mode 1: the sum); nothing is mined, the background column gets no gradient.  Matching, loc_loss
+    and the ignore rule are the same.  Score such a model with `inference*(score="sigmoid")` and start its heads from
+    `SSD_300.init_conf_prior()`."""
     ops.ignore_overlap_mode(ignore_overlap)
     ops.loc_loss_mode(loc_loss)
+    ops.conf_loss_mode(conf_loss)
+    focal_alpha, focal_gamma = ops.focal_params(focal_alpha, focal_gamma)
     if ignore_bboxs is not None and len(ignore_bboxs) != len(tr_bboxs):
         raise ValueError(f"ssd(): ignore_bboxs has {len(ignore_bboxs)} entries for {len(tr_bboxs)} images")
     loc, conf = outputs
@@ -138,7 +149,11 @@ def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = Fa
     ignore = None
     if ignore_bboxs is not None:
         ignore = _pack_ignore(ignore_bboxs, loc.device) + (float(ignore_threshold), ignore_overlap)
-    l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode, ignore, loc_loss)
+    if conf_loss == "ce":
+        l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode, ignore, loc_loss)
+    else:
+        l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode, ignore, loc_loss, conf_loss, focal_alpha,
+                                                   focal_gamma)
     if with_n_pos:
         return l_loc, l_conf, n_pos.detach()
     return l_loc, l_conf
@@ -156,8 +171,8 @@ def _image_size(index, phase):
 draw_hook = None      # optional callable(image_path_or_size, boxes, labels, probs); drawing itself is out of scope
 
 
-def inference(l_, c_, index, top_k=200, phase='train', toDraw=True, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5,
-              keep_score=None):
+def inference(l_, c_, index, top_k=200, phase='train', toDraw=True, min_score=0.2, iou_threshold=0.45, score="softmax", nms="hard",
+              sigma=0.5, keep_score=None):
     """l_ (8732,4) predicted offsets, c_ (8732,C) class scores of ONE image (C = foreground classes + background, 2..256;
     detections carry class ids 0..C-2).  `index` is either the
     reference's dataset index (image size read from `all_images[phase][index]`) or an (img_w, img_h)
@@ -166,14 +181,18 @@ def inference(l_, c_, index, top_k=200, phase='train', toDraw=True, min_score=0.
     out of scope: with toDraw the optional module-level `draw_hook` is called, nothing otherwise.
     nms: "hard" (the reference's greedy rule), or Soft-NMS "linear" / "gaussian" (INTEGRATION.md section 3e): overlapped boxes keep a
     decayed score -- times 1 - IoU beyond iou_threshold, or times exp(-IoU^2 / sigma) -- and are dropped below keep_score (None:
-    min_score); the returned probs are the decayed scores."""
+    min_score); the returned probs are the decayed scores.
+    score: "softmax" (the reference's rule, the default), or "sigmoid" for a model trained with `ssd(conf_loss="focal")`: the
+    probability of class c is the sigmoid of column c alone and the background column is not used."""
     ops.nms_method(nms)
+    ops.score_mode(score)
     if not l_.is_cuda:
         raise RuntimeError("inference() runs on the gfx950 HIP kernels only (no CPU fallback)")
     w, h = _image_size(index, phase)
     pri, _ = _priors_on(l_.device, l_.shape[0])
     boxes, classes, probs, ids, count = ops.decode_nms(l_.detach().float().contiguous(), c_.detach().float().contiguous(), pri,
-                                                      w, h, top_k, min_score, iou_threshold, nms, sigma, keep_score)
+                                                      w, h, top_k, min_score, iou_threshold, score=score, nms=nms, sigma=sigma,
+                                                      keep_score=keep_score)
     k = int(count.item())
     if k == 0:
         return [], [], []
@@ -188,12 +207,14 @@ def inference(l_, c_, index, top_k=200, phase='train', toDraw=True, min_score=0.
 inference.last_prior_ids = None
 
 
-def inference_batch_padded(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5, keep_score=None):
+def inference_batch_padded(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=0.45, score="softmax", nms="hard", sigma=0.5,
+                           keep_score=None):
     """The batched decode as it leaves the device: (boxes (B,top_k,4) pixel xyxy, classes (B,top_k) int64, probs (B,top_k),
     prior_ids (B,top_k) int32, count (B,) int32), rows i >= count[b] zero.  Four kernels + one memset, NO host synchronisation:
     the primary form for a serving loop (slice on the host only when the detections are consumed there).  `sizes`: a (B,2) device
-    tensor of (img_w, img_h) is used as it is; anything else is uploaded.  nms / sigma / keep_score: as in `inference`."""
+    tensor of (img_w, img_h) is used as it is; anything else is uploaded.  nms / sigma / keep_score / score: as in `inference`."""
     ops.nms_method(nms)
+    ops.score_mode(score)
     if not l.is_cuda:
         raise RuntimeError("inference_batch_padded() runs on the gfx950 HIP kernels only (no CPU fallback)")
     if torch.is_tensor(sizes) and sizes.is_cuda and sizes.dtype == torch.float32 and sizes.is_contiguous():
@@ -202,14 +223,15 @@ def inference_batch_padded(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=
         wh = torch.as_tensor(sizes, dtype=torch.float32).reshape(-1, 2).to(l.device).contiguous()
     pri, _ = _priors_on(l.device, l.shape[1])
     return ops.decode_nms_batch(l.detach().float().contiguous(), c.detach().float().contiguous(), pri, wh, top_k, min_score, iou_threshold,
-                                nms, sigma, keep_score)
+                                score=score, nms=nms, sigma=sigma, keep_score=keep_score)
 
 
-def inference_batch(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5, keep_score=None):
+def inference_batch(l, c, sizes, top_k=200, min_score=0.2, iou_threshold=0.45, score="softmax", nms="hard", sigma=0.5, keep_score=None):
     """Batched `inference`: l (B,8732,4), c (B,8732,21), sizes = B (img_w, img_h)
     pairs or a (B,2) tensor.  `inference_batch_padded` + ONE host sync (the counts) for the whole batch.  Returns a list of
-    B tuples (boxes (K_i,4), classes (K_i,), probs (K_i,)); an image without detections gives ([], [], [])."""
-    boxes, classes, probs, ids, count = inference_batch_padded(l, c, sizes, top_k, min_score, iou_threshold, nms, sigma, keep_score)
+    B tuples (boxes (K_i,4), classes (K_i,), probs (K_i,)); an image without detections gives ([], [], []).  score: as in `inference`."""
+    boxes, classes, probs, ids, count = inference_batch_padded(l, c, sizes, top_k, min_score, iou_threshold, score=score, nms=nms, sigma=sigma,
+                                                               keep_score=keep_score)
     out = []
     for i, k in enumerate(count.tolist()):
         out.append(([], [], []) if k == 0 else (boxes[i, :k], classes[i, :k], probs[i, :k]))

@@ -12,6 +12,7 @@ L2-norm kernels) through one `torch.autograd.Function`.
 """
 from __future__ import annotations
 
+import math
 import numbers
 from collections import namedtuple
 from dataclasses import dataclass, replace
@@ -1188,6 +1189,22 @@ class SSD_300(nn.Module):
     def initialize(self, c):
         nn.init.xavier_uniform_(c.weight)
         nn.init.constant_(c.bias, 0.)
+
+    def init_conf_prior(self, prior_prob: float = 0.01) -> None:
+        """Start for a sigmoid (focal) classification head, Lin et al. 2017 section 4.1: the bias of every foreground conf column of
+        every head becomes -log((1 - prior_prob) / prior_prob), so each prior starts with sigmoid score prior_prob instead of 0.5
+        (8732 x n_classes negatives at 0.5 swamp the few positives and the first steps diverge); the background column's bias
+        becomes 0.  Values only: no parameter is added, renamed or re-laid (channel a * (n_classes + 1) + c is anchor a, column c)."""
+        if not 0.0 < float(prior_prob) < 1.0:
+            raise ValueError(f"prior_prob must be in (0, 1), got {prior_prob!r}")
+        b = -math.log((1.0 - float(prior_prob)) / float(prior_prob))
+        n_conf = self.n_classes + 1
+        with torch.no_grad():
+            for name in self._head_names:
+                bias = getattr(self, name + "_cl").bias
+                bias.view(-1, n_conf)[:, :-1] = b
+                bias.view(-1, n_conf)[:, -1] = 0.0
+        self._engine._wcache.clear()
 
     def graphed_forward(self, example_input: torch.Tensor) -> "GraphedForward":
         """Capture the inference forward for this input shape into a HIP graph (see GraphedForward)."""

@@ -217,12 +217,20 @@ SIGNATURES = {
     "ssd_multibox_loss_box_workspace": (_Z, [_I, _I, _I, _I]),
     "ssd_multibox_loss_box": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _F, _I, _I, _P, _P, _P, _P, _P, _P,
                                    _P, _Z, _P]),
+    "ssd_multibox_loss_focal_workspace": (_Z, [_I, _I, _I, _I]),
+    "ssd_multibox_loss_focal": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _F, _I, _I, _I, _F, _F, _P, _P,
+                                     _P, _P, _P, _P, _P, _Z, _P]),
+    "ssd_focal_dense_workspace": (_Z, [_I, _I]),
+    "ssd_focal_dense": (_I, [_P, _P, _P, _I, _I, _I, _F, _I, _F, _F, _P, _P, _P, _Z, _P]),
     "ssd_decode_nms_workspace": (_Z, [_I, _I]),
     "ssd_decode_nms": (_I, [_P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_decode_nms_batch_workspace": (_Z, [_I, _I, _I]),
     "ssd_decode_nms_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_decode_nms_soft": (_I, [_P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _F, _F]),
     "ssd_decode_nms_batch_soft": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _F, _F]),
+    "ssd_decode_nms_score": (_I, [_P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _F, _F, _I]),
+    "ssd_decode_nms_batch_score": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _F, _F, _I]),
+    "ssd_decode_sorted_score": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _I]),
     "ssd_decode_sorted_workspace": (_Z, [_I, _I, _I]),
     "ssd_decode_sorted": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _Z, _P, _I]),
     "ssd_soft_nms_sorted": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _I, _P, _P, _P, _P]),

@@ -49,6 +49,7 @@
 // (sub, max, min, mul, add, sub, IEEE divide): this file is compiled with
 // -ffp-contract=off and the pragma below keeps a*b+c from being fused.
 #include "common.h"
+#include <cfloat>
 #pragma clang fp contract(off)
 
 namespace {
@@ -536,8 +537,9 @@ __global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a, cons
     }
 }
 
-// L1w (64 < C <= 256): L1 without the row staging; grid (ceil(P / 256), bs), 256 threads, a wave per 64 consecutive priors
-template <bool IGN>
+// L1w (64 < C <= 256): L1 without the row staging; grid (ceil(P / 256), bs), 256 threads, a wave per 64 consecutive priors.
+// FOCAL (conf_mode 1, any C): the matching alone -- no conf row is read, cebg is not written; false is the kernel as it was.
+template <bool IGN, bool FOCAL = false>
 __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a, const IgnArgs g) {
     __shared__ f32x4 sg_box[SG];
     __shared__ float sg_area[SG];
@@ -567,7 +569,7 @@ __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a,
     // cross entropy (torch log_softmax order: (x - max) - log(sum exp(x - max))), a row at a time, two rows' loads in flight
     float ce = 0.f;
     const float* src = a.conf + ((size_t)i * P + pb) * C;
-    for (int r = 0; r < rows; r += 2) {                   // (rows <= 0: a wave past the end does nothing here)
+    for (int r = 0; !FOCAL && r < rows; r += 2) {         // (rows <= 0: a wave past the end does nothing here)
         float v0[4], v1[4];
         load_row_wave(src + (size_t)r * C, C, lane, v0);
         const bool two = r + 1 < rows;
@@ -587,7 +589,7 @@ __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a,
     }
     if (live) {
         const size_t ip = (size_t)i * P + p;
-        a.cebg[ip] = ce;
+        if (!FOCAL) a.cebg[ip] = ce;
         a.bestv[ip] = best;
         a.obj[ip] = idx;
         if (IGN) g.ign[ip] = ignore_hit(g, si_box, si_area, i, *reinterpret_cast<const f32x4*>(a.pri_xyxy + (size_t)p * 4)) ? 1 : 0;
@@ -597,7 +599,9 @@ __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a,
 // L2: one workgroup of 1024 threads per image.  IGN: the bytes L1 wrote stay set for non-positives only; those get the mining value 0
 // like the positives and never a selection bit (one bit per prior in LDS behind vals carries that to the last pass).
 // BOX: the localisation term of a positive is box_term's (stats[2] = the sum of the per-positive losses); false is the L1 kernel, unchanged.
-template <bool IGN, bool BOX>
+// FOCAL (conf_mode 1): forced matches, classes, the ignore bytes, n_pos and the loc term as ever, then it returns: no cross entropy,
+// nothing in LDS per prior, no radix select (stats[1] = stats[3] = 0, sel is left unwritten and unread).
+template <bool IGN, bool BOX, bool FOCAL = false>
 __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a, const IgnArgs g) {
     constexpr int NW = 16, NT = 1024;
     extern __shared__ __attribute__((aligned(16))) uint32_t vals[];            // [P] negative CE bits of this image (IGN: + [ceil(P / 32)] ignored bits)
@@ -616,7 +620,7 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a, con
         sg_box[t] = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
     }
     uint32_t* const ibits = vals + P;
-    if (IGN)
+    if (IGN && !FOCAL)
         for (int t = tid; t < (P + 31) / 32; t += NT) ibits[t] = 0u;           // (the barrier below orders this before the atomicOr's)
     // ---- best prior of each box: a wave per box over the NPW per-wave results of L1 ----
     for (int k = s + wave; k < e; k += NW) {
@@ -656,7 +660,7 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a, con
             const size_t ip = (size_t)i * P + (p < P ? p : 0);
             bv[u] = a.bestv[ip];
             ob[u] = a.obj[ip];
-            cev[u] = a.cebg[ip];
+            cev[u] = FOCAL ? 0.f : a.cebg[ip];
             ig[u] = IGN ? g.ign[ip] : (uint8_t)0;
             lc[u] = *reinterpret_cast<const f32x4*>(a.loc + ip * 4);
             prr[u] = *reinterpret_cast<const f32x4*>(a.pri + (size_t)(p < P ? p : 0) * 4);
@@ -678,7 +682,7 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a, con
                 a.obj[ip] = idx;
                 a.cls[ip] = c;
                 float ce = cev[u];
-                if (forced) {                                   // (at most one prior per box: its class may have changed, the lane reads its row)
+                if (!FOCAL && forced) {                         // (at most one prior per box: its class may have changed, the lane reads its row)
                     const float* x = a.conf + ip * C;
                     float m = x[0];
                     for (int q = 1; q < C; ++q) m = fmaxf(m, x[q]);
@@ -708,13 +712,13 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a, con
                 }
                 if (IGN) {
                     const bool ignored = !pos && ig[u] != 0;
-                    if (ignored) {
+                    if (!FOCAL && ignored) {
                         nv = 0.f;
                         atomicOr(&ibits[p >> 5], 1u << (p & 31));
                     }
                     if (pos && ig[u] != 0) g.ign[ip] = 0;       // a positive stays positive inside an ignore box
                 }
-                vals[p] = __float_as_uint(nv > 0.f ? nv : 0.f);      // also maps -0.0 and NaN to +0.0
+                if (!FOCAL) vals[p] = __float_as_uint(nv > 0.f ? nv : 0.f);      // also maps -0.0 and NaN to +0.0
             }
         }
     }
@@ -728,7 +732,9 @@ __global__ __launch_bounds__(1024) void loss_image_kernel(const ImageArgs a, con
         for (int w = 0; w < NW; ++w) { npos += fred[0][w]; ce += fred[1][w]; l1 += fred[2][w]; }
         a.stats[i * 4 + 0] = npos; a.stats[i * 4 + 1] = ce; a.stats[i * 4 + 2] = l1;
         s_bcast[0] = (int)npos;
+        if (FOCAL) a.stats[i * 4 + 3] = 0.f;
     }
+    if (FOCAL) return;                                     // nothing is mined: every prior that is not ignored is in the dense pass
     __syncthreads();
 
     // ---- C: hard negatives ----
@@ -840,10 +846,12 @@ struct FinalArgs {
     float* losses; float* dloc; float* dconf;
     int P, C, bs, norm_mode;
     int loc_mode;                                     // finalize kernels <true>: as ImageArgs::loc_mode
+    float* npos_out = nullptr;                        // finalize_kernel<., true>: n_pos of the batch for the dense pass, one float
 };
 
 // BOX (both finalize kernels): loc_loss is the per-positive mean (or sum) of box_term's loss and dloc its gradient; false is the L1 form
-template <bool BOX>
+// FOCAL (finalize_kernel, any C, no dynamic LDS): losses[0], losses[2] and dloc only; losses[1] and dconf are the dense pass's.
+template <bool BOX, bool FOCAL = false>
 __global__ __launch_bounds__(LB) void finalize_kernel(const FinalArgs a) {
     __shared__ float tot[4];
     if (threadIdx.x == 0) {
@@ -859,7 +867,8 @@ __global__ __launch_bounds__(LB) void finalize_kernel(const FinalArgs a) {
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
         if (BOX) a.losses[0] = a.norm_mode == 0 ? tot[2] / npos : tot[2];
         else a.losses[0] = a.norm_mode == 0 ? tot[2] / (npos * 4.f) : tot[2] / 4.f;     // nn.L1Loss mean over n_pos*4
-        a.losses[1] = a.norm_mode == 0 ? (tot[3] + tot[1]) / npos : (tot[3] + tot[1]);
+        if (!FOCAL) a.losses[1] = a.norm_mode == 0 ? (tot[3] + tot[1]) / npos : (tot[3] + tot[1]);
+        if (FOCAL) *a.npos_out = npos;
         a.losses[2] = npos;
     }
     if (a.dloc == nullptr || a.dconf == nullptr) return;
@@ -872,18 +881,20 @@ __global__ __launch_bounds__(LB) void finalize_kernel(const FinalArgs a) {
     if (p < a.P) {
         const int c = a.cls[ip];
         const bool pos = c != a.C - 1;
-        const bool on = pos || a.sel[ip] != 0;
-        float* dc = fstage + threadIdx.x * a.C;
-        if (on) {                                   // (few rows: the conf row is read by its own lane)
-            const float* x = a.conf + ip * a.C;
-            float m = x[0];
-            for (int q = 1; q < a.C; ++q) m = fmaxf(m, x[q]);
-            float se = 0.f;
-            for (int q = 0; q < a.C; ++q) se += expf(x[q] - m);
-            const float r = 1.f / se;
-            for (int q = 0; q < a.C; ++q) dc[q] = (expf(x[q] - m) * r - (q == c ? 1.f : 0.f)) * inv;
-        } else {
-            for (int q = 0; q < a.C; ++q) dc[q] = 0.f;
+        if constexpr (!FOCAL) {                     // (FOCAL: dconf is the dense pass's, nothing is staged)
+            const bool on = pos || a.sel[ip] != 0;
+            float* dc = fstage + threadIdx.x * a.C;
+            if (on) {                               // (few rows: the conf row is read by its own lane)
+                const float* x = a.conf + ip * a.C;
+                float m = x[0];
+                for (int q = 1; q < a.C; ++q) m = fmaxf(m, x[q]);
+                float se = 0.f;
+                for (int q = 0; q < a.C; ++q) se += expf(x[q] - m);
+                const float r = 1.f / se;
+                for (int q = 0; q < a.C; ++q) dc[q] = (expf(x[q] - m) * r - (q == c ? 1.f : 0.f)) * inv;
+            } else {
+                for (int q = 0; q < a.C; ++q) dc[q] = 0.f;
+            }
         }
         f32x4 dl = {0.f, 0.f, 0.f, 0.f};
         if (pos) {
@@ -906,6 +917,7 @@ __global__ __launch_bounds__(LB) void finalize_kernel(const FinalArgs a) {
         }
         *reinterpret_cast<f32x4*>(a.dloc + ip * 4) = dl;
     }
+    if (FOCAL) return;
     __syncthreads();
     float* const dst = a.dconf + ((size_t)i * a.P + pb) * a.C;
     const int nfl = rows * a.C;
@@ -992,6 +1004,110 @@ __global__ __launch_bounds__(LB) void finalize_wide_kernel(const FinalArgs a) {
     }
 }
 
+// ---- Sigmoid focal classification (ssd_multibox_loss_focal, conf_mode 1) ------------------------------------
+// One element of the term: logit x of a foreground column, target (the prior's class is this column), alpha (< 0: no weighting) and
+// gamma >= 0.  With z = x for a target and -x otherwise,
+//     FL = a_t * exp(-gamma * softplus(z)) * softplus(-z)                      (= a_t * (1 - p_t)^gamma * BCE-with-logits)
+//     dFL/dx = s * a_t * exp(-gamma * softplus(z)) * (-gamma * sigmoid(z) * softplus(-z) - sigmoid(-z)),     s = +1 / -1
+// softplus(u) = max(u, 0) + log1p(exp(-|u|)): both softplus values and both sigmoids come from the one exp(-|x|), nothing overflows
+// for a finite x, the two terms of the bracket have the same sign (no cancellation) and gamma = 0 gives a factor of exactly 1.
+// The loss and its gradient live in ONE function, as box_term() does for the loc side.
+// Arithmetic: the dense pass runs this 7 million times per call, and with libm's expf / log1pf / IEEE division it was 5 x the time of
+// moving its bytes.  The two exponentials, the logarithm and the reciprocal are the hardware's (v_exp_f32, v_log_f32, v_rcp_f32: 1 ulp
+// each; the exponent's scaling by log2(e) adds |u| * 6e-8 relative to exp(u), which is an absolute error below 3e-8 because
+// |u| exp(-|u|) <= 0.37); log1p(e) is e - e^2 / 2 below e = 2^-12, where 1 + e would round e away.
+struct FocalTerm { float loss, grad; };
+__device__ __forceinline__ FocalTerm focal_term(float x, bool target, float alpha, float gamma) {
+    const float z = target ? x : -x;
+    const float e = __expf(-fabsf(z));
+    const float l1p = e < 0x1p-12f ? e * (1.f - 0.5f * e) : __logf(1.f + e);
+    const float sp_z = fmaxf(z, 0.f) + l1p, sp_nz = fmaxf(-z, 0.f) + l1p;       // softplus(z), softplus(-z)
+    const float r = __builtin_amdgcn_rcpf(1.f + e);
+    const float sg_z = z >= 0.f ? r : e * r, sg_nz = z >= 0.f ? e * r : r;     // sigmoid(z), sigmoid(-z)
+    const float a_t = alpha < 0.f ? 1.f : (target ? alpha : 1.f - alpha);
+    const float w = a_t * __expf(-gamma * sp_z);
+    const float d = w * (-gamma * sg_z * sp_nz - sg_nz);
+    return FocalTerm{w * sp_nz, target ? d : -d};
+}
+
+struct FocalArgs {
+    const float* conf; const int32_t* cls; const uint8_t* ign; const float* n_pos_dev;
+    float* dconf; float* part; float* conf_loss;     // conf_loss: where the value goes (losses + 1 of the loss call)
+    int P, C, bs, norm_mode, NBR; float alpha, gamma;
+    float n_pos;                                     // n_pos_dev == nullptr (ssd_focal_dense): the divisor, given by the caller
+};
+
+// n_pos of the batch: the float finalize_kernel<., true> left (the sum its losses[2] is), or the caller's
+__device__ __forceinline__ float focal_n_pos(const FocalArgs& a) { return a.n_pos_dev ? *a.n_pos_dev : a.n_pos; }
+
+// L4 focal_dense_kernel: grid (ceil(P / 128), bs), 256 threads; a block owns 128 consecutive priors of image blockIdx.y, whose 128 x C
+// logits are one contiguous stream: consecutive threads read consecutive floats and write the same floats of dconf (whole lines both
+// ways, four requests per thread in flight), the (row, column) of an element stepped from one division per thread, its class from 128
+// ints in LDS -- nothing per class, any C.  Column C-1 and the rows of ignored priors get +0.0 and add nothing.  The block's sum
+// leaves in a fixed order (thread, wave butterfly, four waves) to part[blockIdx.y * NBR + blockIdx.x]; dconf == nullptr: the sum only.
+constexpr int FR = 128;
+__global__ __launch_bounds__(LB) void focal_dense_kernel(const FocalArgs a) {
+    __shared__ float s_inv;
+    __shared__ float red[4];
+    __shared__ int s_c[FR];                         // class of the row; -1 = ignored prior
+    const int i = blockIdx.y, tid = threadIdx.x;
+    const int pb = blockIdx.x * FR;
+    const int rows = a.P - pb < FR ? a.P - pb : FR;
+    const int C = a.C;
+    if (tid == 0) s_inv = a.norm_mode == 0 ? 1.f / focal_n_pos(a) : 1.f;
+    if (tid < rows) {
+        const size_t ip = (size_t)i * a.P + pb + tid;
+        s_c[tid] = (a.ign != nullptr && a.ign[ip] != 0) ? -1 : a.cls[ip];
+    }
+    __syncthreads();
+    const float inv = s_inv;
+    const size_t base = ((size_t)i * a.P + pb) * C;
+    const float* const src = a.conf + base;
+    float* const dst = a.dconf ? a.dconf + base : nullptr;
+    const int nfl = rows * C;
+    float sum = 0.f;
+    constexpr int UF = 4;
+    const int dr = LB / C, dq = LB - dr * C;               // 256 elements on: dr rows and dq columns
+    int r = tid / C, q = tid - r * C;
+    for (int t0 = tid; t0 < nfl; t0 += UF * LB) {
+        float x[UF];
+#pragma unroll
+        for (int u = 0; u < UF; ++u) {
+            const int t = t0 + u * LB;
+            x[u] = t < nfl ? src[t] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < UF; ++u) {
+            const int t = t0 + u * LB;
+            if (t < nfl) {                                 // (then r < rows)
+                const int c = s_c[r];
+                float d = 0.f;
+                if (c >= 0 && q != C - 1) {
+                    const FocalTerm ft = focal_term(x[u], q == c, a.alpha, a.gamma);
+                    sum += ft.loss;
+                    d = ft.grad * inv;
+                }
+                if (dst) dst[t] = d;
+            }
+            q += dq;
+            r += dr;
+            if (q >= C) { q -= C; ++r; }
+        }
+    }
+    const float tot = block_sum_256(sum, red);
+    if (tid == 0) a.part[(size_t)i * a.NBR + blockIdx.x] = tot;
+}
+
+// L5 focal_sum_kernel: one block; the bs * NBR partials of L4 in a fixed order (thread t takes t, t + 256, ...) -> losses[1]
+__global__ __launch_bounds__(LB) void focal_sum_kernel(const FocalArgs a) {
+    __shared__ float red[4];
+    const int n = a.bs * a.NBR;
+    float sum = 0.f;
+    for (int t = threadIdx.x; t < n; t += LB) sum += a.part[t];
+    const float tot = block_sum_256(sum, red);
+    if (threadIdx.x == 0) *a.conf_loss = a.norm_mode == 0 ? tot / focal_n_pos(a) : tot;
+}
+
 int g_loss_form = 1;      // 1 = three launches (L1 wide, L2 per image, L3), 0 = the four-launch form (ssd_tune_set_loss_form)
 
 struct LossWs {
@@ -1017,7 +1133,14 @@ LossWs carve(void* ws, int bs, int P, int n_gt) {
 
 // L1 (or L1w) and L2 of the three-launch form; IGN = false, BOX = false is what ssd_multibox_loss has always launched
 template <bool IGN, bool BOX>
-int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, hipStream_t st) {
+int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, hipStream_t st, bool focal) {
+    if (focal) {                                    // the matching-only instances: nothing staged per class or per prior, any C
+        hipLaunchKernelGGL((loss_prior_wide_kernel<IGN, true>), dim3(NB, bs), dim3(256), 0, st, ia, ga);
+        SSD_CHECK_LAUNCH();
+        hipLaunchKernelGGL((loss_image_kernel<IGN, BOX, true>), dim3(bs), dim3(1024), 0, st, ia, ga);
+        SSD_CHECK_LAUNCH();
+        return SSD_OK;
+    }
     const bool wide_rows = ia.C > 64;               // L1w / L3w: nothing staged per class
     const size_t l1_lds = wide_rows ? 0 : (size_t)4 * 64 * ia.C * 4;
     const size_t l2_lds = (size_t)ia.P * 4 + (IGN ? (size_t)ssd_cdiv(ia.P, 32) * 4 : 0);
@@ -1043,9 +1166,14 @@ int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, h
 
 // L3 (or L3w): shared by the entries; BOX = false is what they have always launched
 template <bool BOX>
-int launch_finalize(const FinalArgs& fa, hipStream_t st) {
+int launch_finalize(const FinalArgs& fa, hipStream_t st, bool focal = false) {
     const int NB = ssd_cdiv(fa.P, LB);
     const bool grads = fa.dloc != nullptr;
+    if (focal) {
+        hipLaunchKernelGGL((finalize_kernel<BOX, true>), grads ? dim3(NB, fa.bs) : dim3(1, 1), dim3(LB), 0, st, fa);
+        SSD_CHECK_LAUNCH();
+        return SSD_OK;
+    }
     if (fa.C > 64) {
         hipLaunchKernelGGL(finalize_wide_kernel<BOX>, grads ? dim3(ssd_cdiv(fa.P, RW), fa.bs) : dim3(1, 1), dim3(LB), 0, st, fa);
         SSD_CHECK_LAUNCH();
@@ -1077,9 +1205,13 @@ struct LossCall {
     int P, n_classes; float iou_threshold; int neg_pos_ratio, norm_mode;
     bool with_ign; const float* ign_boxes; const int32_t* ign_start; int n_ign; float ignore_threshold; int overlap_mode;
     int loc_mode;
+    int conf_mode = 0; float focal_alpha = 0.25f, focal_gamma = 2.f;      // ssd_multibox_loss_focal: 1 = sigmoid focal classification
     float* losses; int32_t* obj; int32_t* cls; uint8_t* ign; float* dloc; float* dconf;
     void* workspace; size_t workspace_bytes; hipStream_t stream;
 };
+
+// alpha in [0, 1] or negative (no weighting), gamma >= 0 and finite; a NaN fails
+bool focal_params_ok(float alpha, float gamma) { return alpha <= 1.f && gamma >= 0.f && gamma <= FLT_MAX; }
 
 // The status of a call in the header's order: null, shape, alignment, workspace
 int check_loss_call(const LossCall& c) {
@@ -1091,12 +1223,22 @@ int check_loss_call(const LossCall& c) {
     if (c.bs <= 0 || c.n_gt < c.bs || c.P <= 0 || c.P > 36000 || c.n_classes < 2 || c.n_classes > 256 || c.neg_pos_ratio < 0 ||
         (c.norm_mode != 0 && c.norm_mode != 1) || c.loc_mode < 0 || c.loc_mode > 4)
         return SSD_ERR_BAD_SHAPE;
+    if ((c.conf_mode != 0 && c.conf_mode != 1) || !focal_params_ok(c.focal_alpha, c.focal_gamma)) return SSD_ERR_BAD_SHAPE;
     if (c.with_ign && (c.n_ign < 0 || (c.overlap_mode != 0 && c.overlap_mode != 1))) return SSD_ERR_BAD_SHAPE;
     if (!ssd_aligned16(c.loc) || !ssd_aligned16(c.priors_cxcywh) || !ssd_aligned16(c.priors_xyxy) || (c.dloc && !ssd_aligned16(c.dloc)) ||
         !ssd_aligned16(c.workspace))
         return SSD_ERR_ALIGN;
     if (c.with_ign && c.n_ign > 0 && !ssd_aligned16(c.ign_boxes)) return SSD_ERR_ALIGN;
     if (c.workspace_bytes < carve(nullptr, c.bs, c.P, c.n_gt).bytes) return SSD_ERR_WORKSPACE;
+    return SSD_OK;
+}
+
+// L4 and L5, one place for the loss call and for ssd_focal_dense
+int launch_focal_dense(const FocalArgs& za, hipStream_t st) {
+    hipLaunchKernelGGL(focal_dense_kernel, dim3(za.NBR, za.bs), dim3(LB), 0, st, za);
+    SSD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(focal_sum_kernel, dim3(1), dim3(LB), 0, st, za);
+    SSD_CHECK_LAUNCH();
     return SSD_OK;
 }
 
@@ -1111,15 +1253,24 @@ int run_loss(const LossCall& c) {
     const IgnArgs ga = c.with_ign ? IgnArgs{c.ign_boxes, c.ign_start, c.ign, c.ignore_threshold, c.overlap_mode}
                                   : IgnArgs{nullptr, nullptr, nullptr, 0.f, 0};
     const FinalArgs fa{c.loc, c.conf, c.gt_boxes, c.priors_cxcywh, c.obj, c.cls, w.sel, w.stats, c.losses, c.dloc, c.dconf, c.P,
-                       c.n_classes, c.bs, c.norm_mode, c.loc_mode};
-    const bool box = c.loc_mode != 0;
+                       c.n_classes, c.bs, c.norm_mode, c.loc_mode, w.part};
+    const bool box = c.loc_mode != 0, focal = c.conf_mode != 0;
     int rc;
     if (c.with_ign)
-        rc = box ? launch_prior_image<true, true>(ia, ga, c.bs, NB, c.stream) : launch_prior_image<true, false>(ia, ga, c.bs, NB, c.stream);
+        rc = box ? launch_prior_image<true, true>(ia, ga, c.bs, NB, c.stream, focal)
+                 : launch_prior_image<true, false>(ia, ga, c.bs, NB, c.stream, focal);
     else
-        rc = box ? launch_prior_image<false, true>(ia, ga, c.bs, NB, c.stream) : launch_prior_image<false, false>(ia, ga, c.bs, NB, c.stream);
+        rc = box ? launch_prior_image<false, true>(ia, ga, c.bs, NB, c.stream, focal)
+                 : launch_prior_image<false, false>(ia, ga, c.bs, NB, c.stream, focal);
     if (rc != SSD_OK) return rc;
-    return box ? launch_finalize<true>(fa, c.stream) : launch_finalize<false>(fa, c.stream);
+    rc = box ? launch_finalize<true>(fa, c.stream, focal) : launch_finalize<false>(fa, c.stream, focal);
+    if (rc != SSD_OK || !focal) return rc;
+    // conf_mode 1: the dense pass (conf_loss partials, dconf) and the fixed-order sum; the partials lie where the cross entropy of
+    // the mined form lay (bs * ceil(P / 128) of its bs * P floats) and n_pos in the first float of the four-launch form's partials, so
+    // the workspace is the one every entry has
+    return launch_focal_dense(FocalArgs{c.conf, c.cls, c.with_ign ? c.ign : nullptr, w.part, c.dconf, w.neg, c.losses + 1, c.P, c.n_classes, c.bs,
+                                        c.norm_mode, ssd_cdiv(c.P, FR), c.focal_alpha, c.focal_gamma, 0.f},
+                              c.stream);
 }
 
 // The four-launch form of rounds 1-3 (K1 - K3, then L3), the cross-check ssd_tune_set_loss_form(0) selects.  It has neither ignore
@@ -1175,6 +1326,10 @@ extern "C" size_t ssd_multibox_loss_box_workspace(int bs, int P, int n_gt, int n
     return ssd_multibox_loss_ignore_workspace(bs, P, n_gt, n_ign);
 }
 
+extern "C" size_t ssd_multibox_loss_focal_workspace(int bs, int P, int n_gt, int n_ign) {
+    return ssd_multibox_loss_ignore_workspace(bs, P, n_gt, n_ign);
+}
+
 // The plain loss: no ignore regions, L1 localisation term.  The one entry ssd_tune_set_loss_form reaches.
 extern "C" int ssd_multibox_loss(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
                                  const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh,
@@ -1223,4 +1378,45 @@ extern "C" int ssd_multibox_loss_box(const float* loc, const float* conf, const 
                      .dconf = dconf, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream};
     const int bad = check_loss_call(c);
     return bad != SSD_OK ? bad : run_loss(c);
+}
+
+// The loss with a choice of classification term beside ssd_multibox_loss_box's options: conf_mode 0 is that entry, launch for launch;
+// conf_mode 1 the sigmoid focal term (neg_pos_ratio is then not read)
+extern "C" int ssd_multibox_loss_focal(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                                       const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh, const float* priors_xyxy,
+                                       int P, int n_classes, float iou_threshold, int neg_pos_ratio, int norm_mode, const float* ign_boxes,
+                                       const int32_t* ign_start, int n_ign, float ignore_threshold, int overlap_mode, int loc_mode,
+                                       int conf_mode, float focal_alpha, float focal_gamma, float* losses, int32_t* obj, int32_t* cls,
+                                       uint8_t* ign, float* dloc, float* dconf, void* workspace, size_t workspace_bytes, void* stream) {
+    const LossCall c{.loc = loc, .conf = conf, .gt_boxes = gt_boxes, .gt_classes = gt_classes, .img_start = img_start, .bs = bs, .n_gt = n_gt,
+                     .priors_cxcywh = priors_cxcywh, .priors_xyxy = priors_xyxy, .P = P, .n_classes = n_classes,
+                     .iou_threshold = iou_threshold, .neg_pos_ratio = conf_mode == 1 && neg_pos_ratio < 0 ? 0 : neg_pos_ratio,
+                     .norm_mode = norm_mode, .with_ign = ign_start != nullptr, .ign_boxes = ign_boxes, .ign_start = ign_start, .n_ign = n_ign,
+                     .ignore_threshold = ignore_threshold, .overlap_mode = overlap_mode, .loc_mode = loc_mode, .conf_mode = conf_mode,
+                     .focal_alpha = focal_alpha, .focal_gamma = focal_gamma, .losses = losses, .obj = obj, .cls = cls, .ign = ign,
+                     .dloc = dloc, .dconf = dconf, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream};
+    const int bad = check_loss_call(c);
+    return bad != SSD_OK ? bad : run_loss(c);
+}
+
+// The dense pass of conf_mode 1 alone (L4 and L5, launched as the loss launches them), for tests and tools: cls (bs, P) int32 classes
+// (C-1 = background), ign (bs, P) bytes or NULL, n_pos the divisor of norm_mode 0.  conf_loss[0] receives the value of losses[1];
+// dconf may be NULL.  workspace: 4 * bs * ceil(P / 128) bytes rounded up to a multiple of 256, 16-byte aligned.
+extern "C" size_t ssd_focal_dense_workspace(int bs, int P) {
+    if (bs <= 0 || P <= 0) return 0;
+    return ((size_t)bs * ssd_cdiv(P, FR) * 4 + 255) / 256 * 256;
+}
+
+extern "C" int ssd_focal_dense(const float* conf, const int32_t* cls, const uint8_t* ign, int bs, int P, int n_classes, float n_pos,
+                               int norm_mode, float focal_alpha, float focal_gamma, float* conf_loss, float* dconf, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    if (!conf || !cls || !conf_loss || !workspace) return SSD_ERR_NULL;
+    if (bs <= 0 || P <= 0 || P > 36000 || n_classes < 2 || n_classes > 256 || (norm_mode != 0 && norm_mode != 1) || !(n_pos > 0.f) ||
+        !focal_params_ok(focal_alpha, focal_gamma))
+        return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(workspace)) return SSD_ERR_ALIGN;
+    if (workspace_bytes < ssd_focal_dense_workspace(bs, P)) return SSD_ERR_WORKSPACE;
+    return launch_focal_dense(FocalArgs{conf, cls, ign, nullptr, dconf, reinterpret_cast<float*>(workspace), conf_loss, P, n_classes, bs,
+                                        norm_mode, ssd_cdiv(P, FR), focal_alpha, focal_gamma, n_pos},
+                              (hipStream_t)stream);
 }

@@ -7,6 +7,10 @@
 //                      (prob bits << 32 | ~prior index): descending key order = descending prob, lower prior index first on ties
 //                      (the CPU sort order).  Slots come from one atomic per (wave, class) -- ballot + prefix --
 //                      so the order inside keys[] varies from run to run; the ranks D3 computes from the unique keys do not.
+//                      SIGMOID (the *_score entries, score_mode 1; false is the kernel as it was): the probability of class c < C-1
+//                      is sigmoid(conf[c]) -- 1 / (1 + exp(-|x|)), times exp(-|x|) for x < 0: no overflow, exactly 1.0 from about
+//                      x = 17 on -- for a model trained with the sigmoid focal term; no max, no sum, the background column's value
+//                      (staged with its row) is used by nothing.  Everything after the score is the same code.
 //   D3 rank_scatter    rank of every candidate = number of larger keys (keys are unique), so
 //                      the sort is a scatter; all classes and candidates in parallel
 //   D4 nms             block per class, greedy in sorted order, 64 rows at a time: suppression words by
@@ -76,7 +80,7 @@ NmsWs carve(void* ws, int P, int C, int B) {
 
 // grid = (ceil(P/NT), 1, B).  cand_cnt[(C-1)+1 per image] must be zero on entry (hipMemsetAsync in front of the launch).
 constexpr int decode_stride(int C) { return C | 1; }                 // odd row stride in LDS: 21 -> 21, 81 -> 81, 256 -> 257
-template <int NT>
+template <int NT, bool SIGMOID = false>
 __global__ __launch_bounds__(NT) void decode_compact_kernel(const float* __restrict__ l_, const float* __restrict__ c_, const float* __restrict__ pri,
                                                             int P, int C, float min_score, float* __restrict__ boxes, uint64_t* __restrict__ keys,
                                                             int32_t* __restrict__ cand_cnt) {
@@ -110,13 +114,15 @@ __global__ __launch_bounds__(NT) void decode_compact_kernel(const float* __restr
         *reinterpret_cast<f32x4*>(boxes + (size_t)p * 4) = b;
         const float* x = sc + tid * S;                              // odd row stride: conflict-free
         float* xw = sc + tid * S;
-        m = x[0];
-        for (int q = 1; q < C; ++q) m = fmaxf(m, x[q]);
-        se = 0.f;
-        for (int q = 0; q < C; ++q) {                               // exp(x - max) is kept in place of x: the second pass divides, it does
-            const float e = expf(x[q] - m);                         // not exponentiate again (same value, 21 expf per prior instead of 41)
-            xw[q] = e;
-            se += e;
+        if (!SIGMOID) {
+            m = x[0];
+            for (int q = 1; q < C; ++q) m = fmaxf(m, x[q]);
+            se = 0.f;
+            for (int q = 0; q < C; ++q) {                           // exp(x - max) is kept in place of x: the second pass divides, it does
+                const float e = expf(x[q] - m);                     // not exponentiate again (same value, 21 expf per prior instead of 41)
+                xw[q] = e;
+                se += e;
+            }
         }
     }
     // Candidates, 32 classes at a time: every lane collects its hit bits (the probability replaces exp in LDS), lane k then owns class
@@ -126,7 +132,16 @@ __global__ __launch_bounds__(NT) void decode_compact_kernel(const float* __restr
         const int nq = min(32, C1 - q0);
         unsigned hits = 0;
         for (int k = 0; k < nq; ++k) {
-            const float v = live ? sc[tid * S + q0 + k] / se : 0.f;
+            float v = 0.f;
+            if (SIGMOID) {
+                if (live) {
+                    const float xq = sc[tid * S + q0 + k];
+                    const float e = expf(-fabsf(xq)), r = 1.f / (1.f + e);
+                    v = xq >= 0.f ? r : e * r;                      // (NaN stays NaN and fails the comparison below)
+                }
+            } else {
+                v = live ? sc[tid * S + q0 + k] / se : 0.f;
+            }
             if (live) sc[tid * S + q0 + k] = v;
             hits |= (live && v >= min_score ? 1u : 0u) << k;        // Losses.py:32 (NaN fails, as in torch)
         }
@@ -757,20 +772,10 @@ static int launch_topk(const float* s_boxes, const int32_t* s_idx, const uint32_
     return SSD_OK;
 }
 
-// D1 and D3 as the decode launches them, one place for the decode and for ssd_decode_sorted: the counter clear, decode_compact at the
-// block size its class count asks for, rank_scatter.  cand_cnt is (B, C1 + 1), keys (B, C1, P).
-// The candidate counters of decode_compact are cleared by a memset node, or (clear_with_kernel) by zero_counts_kernel: the Soft-NMS
-// decode is replayed from captured graphs, and a memset node of this size was seen to complete only in part against the work in front
-// of it on replay (DESIGN.md section 4e) -- with counters left over, decode_compact and rank_scatter index past their arrays.  The
-// hard rule's launches stay as they were.
-static int launch_decode_sort(const float* l_, const float* c_, const float* priors_cxcywh, int B, int P, int n_classes, float min_score,
-                              float* boxes, uint64_t* keys, int32_t* cand_cnt, float* s_boxes, float* s_prob, int32_t* s_idx,
-                              bool clear_with_kernel, hipStream_t st) {
-    const int C1 = n_classes - 1;
-    if (clear_with_kernel) {
-        hipLaunchKernelGGL(zero_counts_kernel, dim3(ssd_cdiv(n_classes * B, 256)), dim3(256), 0, st, cand_cnt, n_classes * B);
-        SSD_CHECK_LAUNCH();
-    } else if (hipMemsetAsync(cand_cnt, 0, (size_t)n_classes * 4 * B, st) != hipSuccess) return SSD_ERR_LAUNCH;
+// D1 at the block size its class count asks for; SIGMOID = false is what the decode has always launched
+template <bool SIGMOID>
+static int launch_decode_compact(const float* l_, const float* c_, const float* priors_cxcywh, int B, int P, int n_classes, float min_score,
+                                 float* boxes, uint64_t* keys, int32_t* cand_cnt, hipStream_t st) {
     // priors per block: as many as keep the staged rows within 48 KB (256 up to C = 47, C = 21 as always), 64 beyond C = 95
     const int S = decode_stride(n_classes);
     const int nt = 256 * S * 4 <= 48 * 1024 ? 256 : (128 * S * 4 <= 48 * 1024 ? 128 : 64);
@@ -779,22 +784,44 @@ static int launch_decode_sort(const float* l_, const float* c_, const float* pri
         static std::atomic<unsigned long long> raised{0};
         int dev;
         if (ssd_attr_needed(raised, dev)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(decode_compact_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(decode_compact_kernel<64, SIGMOID>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)((size_t)64 * decode_stride(256) * 4)) != hipSuccess)
                 return SSD_ERR_LAUNCH;
             ssd_attr_done(raised, dev);
         }
     }
     if (nt == 256)
-        hipLaunchKernelGGL(decode_compact_kernel<256>, dim3(ssd_cdiv(P, 256), 1, B), dim3(256), dlds, st, l_, c_, priors_cxcywh, P,
+        hipLaunchKernelGGL((decode_compact_kernel<256, SIGMOID>), dim3(ssd_cdiv(P, 256), 1, B), dim3(256), dlds, st, l_, c_, priors_cxcywh, P,
                            n_classes, min_score, boxes, keys, cand_cnt);
     else if (nt == 128)
-        hipLaunchKernelGGL(decode_compact_kernel<128>, dim3(ssd_cdiv(P, 128), 1, B), dim3(128), dlds, st, l_, c_, priors_cxcywh, P,
+        hipLaunchKernelGGL((decode_compact_kernel<128, SIGMOID>), dim3(ssd_cdiv(P, 128), 1, B), dim3(128), dlds, st, l_, c_, priors_cxcywh, P,
                            n_classes, min_score, boxes, keys, cand_cnt);
     else
-        hipLaunchKernelGGL(decode_compact_kernel<64>, dim3(ssd_cdiv(P, 64), 1, B), dim3(64), dlds, st, l_, c_, priors_cxcywh, P,
+        hipLaunchKernelGGL((decode_compact_kernel<64, SIGMOID>), dim3(ssd_cdiv(P, 64), 1, B), dim3(64), dlds, st, l_, c_, priors_cxcywh, P,
                            n_classes, min_score, boxes, keys, cand_cnt);
     SSD_CHECK_LAUNCH();
+    return SSD_OK;
+}
+
+// D1 and D3 as the decode launches them, one place for the decode and for ssd_decode_sorted: the counter clear, decode_compact at the
+// block size its class count asks for, rank_scatter.  cand_cnt is (B, C1 + 1), keys (B, C1, P).
+// The candidate counters of decode_compact are cleared by a memset node, or (clear_with_kernel) by zero_counts_kernel: the Soft-NMS
+// decode is replayed from captured graphs, and a memset node of this size was seen to complete only in part against the work in front
+// of it on replay (DESIGN.md section 4e) -- with counters left over, decode_compact and rank_scatter index past their arrays.  The
+// hard rule's launches stay as they were.
+static int launch_decode_sort(const float* l_, const float* c_, const float* priors_cxcywh, int B, int P, int n_classes, float min_score,
+                              float* boxes, uint64_t* keys, int32_t* cand_cnt, float* s_boxes, float* s_prob, int32_t* s_idx,
+                              bool clear_with_kernel, hipStream_t st, bool sigmoid = false) {
+    const int C1 = n_classes - 1;
+    if (clear_with_kernel) {
+        hipLaunchKernelGGL(zero_counts_kernel, dim3(ssd_cdiv(n_classes * B, 256)), dim3(256), 0, st, cand_cnt, n_classes * B);
+        SSD_CHECK_LAUNCH();
+    } else if (hipMemsetAsync(cand_cnt, 0, (size_t)n_classes * 4 * B, st) != hipSuccess) return SSD_ERR_LAUNCH;
+    {
+        const int rc = sigmoid ? launch_decode_compact<true>(l_, c_, priors_cxcywh, B, P, n_classes, min_score, boxes, keys, cand_cnt, st)
+                               : launch_decode_compact<false>(l_, c_, priors_cxcywh, B, P, n_classes, min_score, boxes, keys, cand_cnt, st);
+        if (rc != SSD_OK) return rc;
+    }
     hipLaunchKernelGGL(rank_scatter_kernel, dim3(ssd_cdiv(P, 256), C1, B), dim3(256), 0, st, keys, cand_cnt, boxes, P, s_boxes, s_prob, s_idx);
     SSD_CHECK_LAUNCH();
     return SSD_OK;
@@ -804,7 +831,7 @@ static int launch_decode_sort(const float* l_, const float* c_, const float* pri
 static int decode_nms_batch_impl(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
                                  int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
                                  float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes, void* stream,
-                                 int method, float sigma, float keep_score) {
+                                 int method, float sigma, float keep_score, int score_mode = 0) {
     if (!l_ || !c_ || !priors_cxcywh || !img_wh || !boxes || !classes || !probs || !prior_ids || !count || !workspace) return SSD_ERR_NULL;
     if (B <= 0 || B > 65535 || P <= 0 || P > 100000 || n_classes < 2 || n_classes > 256 || top_k <= 0 || top_k > 4096) return SSD_ERR_BAD_SHAPE;
     if (method != 0 && !soft_nms_args_ok(P, method, iou_threshold, sigma, keep_score, top_k)) return SSD_ERR_BAD_SHAPE;
@@ -815,7 +842,7 @@ static int decode_nms_batch_impl(const float* l_, const float* c_, const float* 
     const int C1 = n_classes - 1;
     {
         const int rc = launch_decode_sort(l_, c_, priors_cxcywh, B, P, n_classes, min_score, w.boxes, w.keys, w.cand_cnt, w.s_boxes, w.s_prob,
-                                          w.s_idx, method != 0, st);
+                                          w.s_idx, method != 0, st, score_mode != 0);
         if (rc != SSD_OK) return rc;
     }
     if (method != 0) {
@@ -850,7 +877,7 @@ extern "C" int ssd_decode_nms_batch_soft(const float* l_, const float* c_, const
 static int decode_nms_impl(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
                            float min_score, float iou_threshold, int top_k, float img_w, float img_h, float* boxes,
                            int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count, void* workspace,
-                           size_t workspace_bytes, void* stream, int method, float sigma, float keep_score) {
+                           size_t workspace_bytes, void* stream, int method, float sigma, float keep_score, int score_mode = 0) {
     if (!workspace) return SSD_ERR_NULL;
     const size_t need = ssd_decode_nms_batch_workspace(1, P, n_classes);
     if (need == 0) return SSD_ERR_BAD_SHAPE;
@@ -860,7 +887,7 @@ static int decode_nms_impl(const float* l_, const float* c_, const float* priors
     hipLaunchKernelGGL(set_wh_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, wh, img_w, img_h);
     SSD_CHECK_LAUNCH();
     return decode_nms_batch_impl(l_, c_, priors_cxcywh, wh, 1, P, n_classes, min_score, iou_threshold, top_k, boxes, classes, probs,
-                                 prior_ids, count, workspace, workspace_bytes, stream, method, sigma, keep_score);
+                                 prior_ids, count, workspace, workspace_bytes, stream, method, sigma, keep_score, score_mode);
 }
 
 extern "C" int ssd_decode_nms(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
@@ -880,6 +907,29 @@ extern "C" int ssd_decode_nms_soft(const float* l_, const float* c_, const float
                            prior_ids, count, workspace, workspace_bytes, stream, method, sigma, keep_score);
 }
 
+// The decode with a choice of score: the arguments of ssd_decode_nms[_batch]_soft with method 0 (the greedy rule; sigma and keep_score
+// are then not read) allowed beside 1 and 2, followed by score_mode: 0 = softmax over all C columns (the entries above, launch for
+// launch), 1 = sigmoid of each foreground column (decode_compact_kernel<., true>).  Nothing else differs.
+extern "C" int ssd_decode_nms_batch_score(const float* l_, const float* c_, const float* priors_cxcywh, const float* img_wh, int B, int P,
+                                          int n_classes, float min_score, float iou_threshold, int top_k, float* boxes, int64_t* classes,
+                                          float* probs, int32_t* prior_ids, int32_t* count, void* workspace, size_t workspace_bytes,
+                                          void* stream, int method, float sigma, float keep_score, int score_mode) {
+    if (method < 0 || method > 2 || (score_mode != 0 && score_mode != 1)) return SSD_ERR_BAD_SHAPE;
+    return decode_nms_batch_impl(l_, c_, priors_cxcywh, img_wh, B, P, n_classes, min_score, iou_threshold, top_k, boxes, classes, probs,
+                                 prior_ids, count, workspace, workspace_bytes, stream, method, method ? sigma : 0.f, method ? keep_score : 0.f,
+                                 score_mode);
+}
+
+extern "C" int ssd_decode_nms_score(const float* l_, const float* c_, const float* priors_cxcywh, int P, int n_classes,
+                                    float min_score, float iou_threshold, int top_k, float img_w, float img_h, float* boxes,
+                                    int64_t* classes, float* probs, int32_t* prior_ids, int32_t* count, void* workspace,
+                                    size_t workspace_bytes, void* stream, int method, float sigma, float keep_score, int score_mode) {
+    if (method < 0 || method > 2 || (score_mode != 0 && score_mode != 1)) return SSD_ERR_BAD_SHAPE;
+    return decode_nms_impl(l_, c_, priors_cxcywh, P, n_classes, min_score, iou_threshold, top_k, img_w, img_h, boxes, classes, probs,
+                           prior_ids, count, workspace, workspace_bytes, stream, method, method ? sigma : 0.f, method ? keep_score : 0.f,
+                           score_mode);
+}
+
 // D1 + D3 alone, into the caller's arrays: launch_decode_sort as the decode calls it, nothing forced.  The workspace holds the keys.
 extern "C" size_t ssd_decode_sorted_workspace(int B, int P, int n_classes) {
     if (B <= 0 || P <= 0 || n_classes < 2) return 0;
@@ -897,6 +947,20 @@ extern "C" int ssd_decode_sorted(const float* l_, const float* c_, const float* 
     if (workspace_bytes < ssd_decode_sorted_workspace(B, P, n_classes)) return SSD_ERR_WORKSPACE;
     return launch_decode_sort(l_, c_, priors_cxcywh, B, P, n_classes, min_score, boxes, reinterpret_cast<uint64_t*>(workspace), cand_cnt,
                               s_boxes, s_prob, s_idx, clear_with_kernel == 1, (hipStream_t)stream);
+}
+
+// ssd_decode_sorted with a choice of score (score_mode as in ssd_decode_nms_score; 0 is ssd_decode_sorted itself)
+extern "C" int ssd_decode_sorted_score(const float* l_, const float* c_, const float* priors_cxcywh, int B, int P, int n_classes,
+                                       float min_score, float* boxes, float* s_boxes, float* s_prob, int32_t* s_idx, int32_t* cand_cnt,
+                                       void* workspace, size_t workspace_bytes, void* stream, int clear_with_kernel, int score_mode) {
+    if (!l_ || !c_ || !priors_cxcywh || !boxes || !s_boxes || !s_prob || !s_idx || !cand_cnt || !workspace) return SSD_ERR_NULL;
+    if (B <= 0 || B > 65535 || P <= 0 || P > 100000 || n_classes < 2 || n_classes > 256) return SSD_ERR_BAD_SHAPE;
+    if ((clear_with_kernel != 0 && clear_with_kernel != 1) || (score_mode != 0 && score_mode != 1)) return SSD_ERR_BAD_SHAPE;
+    if (!ssd_aligned16(l_) || !ssd_aligned16(priors_cxcywh) || !ssd_aligned16(boxes) || !ssd_aligned16(s_boxes) || !ssd_aligned16(workspace))
+        return SSD_ERR_ALIGN;
+    if (workspace_bytes < ssd_decode_sorted_workspace(B, P, n_classes)) return SSD_ERR_WORKSPACE;
+    return launch_decode_sort(l_, c_, priors_cxcywh, B, P, n_classes, min_score, boxes, reinterpret_cast<uint64_t*>(workspace), cand_cnt,
+                              s_boxes, s_prob, s_idx, clear_with_kernel == 1, (hipStream_t)stream, score_mode == 1);
 }
 
 extern "C" int ssd_soft_nms_sorted(const float* s_boxes, const float* s_prob, const int32_t* cand_cnt, int B, int C1, int P, int method,

@@ -875,9 +875,33 @@ def loc_loss_mode(name):
         raise ValueError(f"loc_loss must be one of {', '.join(map(repr, LOC_LOSSES))}, not {name!r}") from None
 
 
+CONF_LOSSES = {"ce": 0, "focal": 1}
+
+
+def conf_loss_mode(name):
+    """0 / 1 for "ce" / "focal" (the `conf_mode` of the C ABI); ValueError for anything else."""
+    try:
+        return CONF_LOSSES[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"conf_loss must be one of {', '.join(map(repr, CONF_LOSSES))}, not {name!r}") from None
+
+
+def focal_params(focal_alpha, focal_gamma):
+    """(alpha, gamma) as floats: alpha in [0, 1] or negative (no alpha weighting), gamma >= 0 and finite; ValueError otherwise."""
+    try:
+        alpha, gamma = float(focal_alpha), float(focal_gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"focal_alpha / focal_gamma must be numbers, not {focal_alpha!r} / {focal_gamma!r}") from None
+    if not alpha <= 1.0:
+        raise ValueError(f"focal_alpha must be in [0, 1], or negative for no weighting, not {focal_alpha!r}")
+    if not 0.0 <= gamma < float("inf"):
+        raise ValueError(f"focal_gamma must be >= 0 and finite, not {focal_gamma!r}")
+    return alpha, gamma
+
+
 def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, iou_threshold=0.5,
-                  neg_pos_ratio=3, norm_mode=0, want_grads=True, loc_loss="l1", ignore_boxes=None, ignore_start=None,
-                  ignore_threshold=0.5, ignore_overlap="iou"):
+                  neg_pos_ratio=3, norm_mode=0, want_grads=True, loc_loss="l1", conf_loss="ce", focal_alpha=0.25, focal_gamma=2.0,
+                  ignore_boxes=None, ignore_start=None, ignore_threshold=0.5, ignore_overlap="iou"):
     """-> dict(losses (3,), obj (bs,P) i32, cls (bs,P) i32, dloc, dconf).  `ssd_multibox_loss_box` serves every option; the call without any goes
     to `ssd_multibox_loss`, the same host path.
     ignore_boxes (n_ign, 4) fractional xyxy with ignore_start (bs + 1,) int32 prefix offsets (both on the device; n_ign may be 0):
@@ -887,9 +911,16 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
     loc_loss: "l1" (the reference's term), or "iou" / "giou" / "diou" / "ciou": the predicted box of each positive is decoded
     (exponent clamped to +-log(1000 / 16)) and losses[0] is the per-positive mean (norm_mode 1: sum) of 1 - IoU plus the mode's
     penalty, dloc its gradient; everything else is unchanged.  "ciou" needs ground-truth boxes of positive height; "iou" gives no
-    gradient where the two boxes do not overlap."""
+    gradient where the two boxes do not overlap.
+    conf_loss: "ce" (the reference's softmax cross entropy with hard-negative mining), or "focal": columns 0 .. C-2 are
+    one-against-all logits and losses[1] is the sum over every prior that is not ignored and every foreground column of
+    alpha_t (1 - p_t)^focal_gamma BCE (torchvision's `sigmoid_focal_loss`; focal_alpha < 0: no alpha weighting), divided by n_pos
+    (norm_mode 1: the sum); dconf its gradient, zero in the background column; nothing is mined and neg_pos_ratio is not read
+    (`ssd_multibox_loss_focal`).  Matching, losses[0], losses[2], dloc and "ign" are those of "ce"."""
     mode = ignore_overlap_mode(ignore_overlap)
     loc_mode = loc_loss_mode(loc_loss)
+    conf_mode = conf_loss_mode(conf_loss)
+    alpha, gamma = focal_params(focal_alpha, focal_gamma)
     if (ignore_boxes is None) != (ignore_start is None):
         raise ValueError("multibox_loss: ignore_boxes and ignore_start go together")
     _req(loc, "loc"); _req(conf, "conf"); _req(gt_boxes, "gt_boxes"); _req(gt_classes, "gt_classes")
@@ -919,7 +950,11 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
             priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, ncls, float(iou_threshold), int(neg_pos_ratio), int(norm_mode))
     outs = (out["losses"].data_ptr(), out["obj"].data_ptr(), out["cls"].data_ptr())
     tail = (_ptr(out["dloc"]), _ptr(out["dconf"]), ws.data_ptr(), ws.numel(), _stream())
-    if loc_mode == 0 and ignore_boxes is None:                # (the entry the cross-check switch `ssd_tune_set_loss_form` reaches)
+    if conf_mode != 0:
+        check(lib.ssd_multibox_loss_focal(*head, ignore_boxes.data_ptr() if n_ign else None, _ptr(ignore_start), n_ign,
+                                          float(ignore_threshold), mode, loc_mode, conf_mode, alpha, gamma, *outs, _ptr(out.get("ign")),
+                                          *tail), "multibox_loss_focal")
+    elif loc_mode == 0 and ignore_boxes is None:              # (the entry the cross-check switch `ssd_tune_set_loss_form` reaches)
         check(lib.ssd_multibox_loss(*head, *outs, *tail), "multibox_loss")
     else:
         check(lib.ssd_multibox_loss_box(*head, ignore_boxes.data_ptr() if n_ign else None, _ptr(ignore_start), n_ign,
@@ -939,11 +974,25 @@ def nms_method(nms):
         raise ValueError(f"nms must be 'hard', 'linear' or 'gaussian', not {nms!r}") from None
 
 
-def decode_nms(l_, c_, priors_cxcywh, img_w, img_h, top_k=200, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5,
-               keep_score=None):
+SCORES = {"softmax": 0, "sigmoid": 1}
+
+
+def score_mode(score):
+    """0 / 1 for "softmax" / "sigmoid" (the `score_mode` of the C ABI); ValueError for anything else."""
+    try:
+        return SCORES[score]
+    except (KeyError, TypeError):
+        raise ValueError(f"score must be 'softmax' or 'sigmoid', not {score!r}") from None
+
+
+def decode_nms(l_, c_, priors_cxcywh, img_w, img_h, top_k=200, min_score=0.2, iou_threshold=0.45, score="softmax", nms="hard",
+               sigma=0.5, keep_score=None):
     """-> (boxes (top_k,4), classes (top_k,) i64, probs (top_k,), prior_ids (top_k,) i32, count (1,) i32), all device.
-    nms = "linear" / "gaussian": Soft-NMS (probs are the decayed scores; keep_score None = min_score)."""
+    nms = "linear" / "gaussian": Soft-NMS (probs are the decayed scores; keep_score None = min_score).
+    score = "sigmoid": the probability of a class is the sigmoid of its own column (a model trained with conf_loss="focal"); the
+    default "softmax" makes the call it has always made."""
     method = nms_method(nms)
+    smode = score_mode(score)
     _req(l_, "l_"); _req(c_, "c_"); _req(priors_cxcywh, "priors")
     p, ncls = c_.shape
     if tuple(l_.shape) != (p, 4) or tuple(priors_cxcywh.shape) != (p, 4):
@@ -956,6 +1005,13 @@ def decode_nms(l_, c_, priors_cxcywh, img_w, img_h, top_k=200, min_score=0.2, io
     probs = torch.zeros((top_k,), device=dev, dtype=torch.float32)
     ids = torch.zeros((top_k,), device=dev, dtype=torch.int32)
     count = torch.zeros((1,), device=dev, dtype=torch.int32)
+    if smode != 0:
+        check(lib.ssd_decode_nms_score(l_.data_ptr(), c_.data_ptr(), priors_cxcywh.data_ptr(), p, ncls, float(min_score),
+                                       float(iou_threshold), int(top_k), float(img_w), float(img_h), boxes.data_ptr(),
+                                       classes.data_ptr(), probs.data_ptr(), ids.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream(), method, float(sigma), float(min_score if keep_score is None else keep_score), smode),
+              "decode_nms_score")
+        return boxes, classes, probs, ids, count
     if method != 0:
         check(lib.ssd_decode_nms_soft(l_.data_ptr(), c_.data_ptr(), priors_cxcywh.data_ptr(), p, ncls, float(min_score),
                                       float(iou_threshold), int(top_k), float(img_w), float(img_h), boxes.data_ptr(),
@@ -969,12 +1025,13 @@ def decode_nms(l_, c_, priors_cxcywh, img_w, img_h, top_k=200, min_score=0.2, io
     return boxes, classes, probs, ids, count
 
 
-def decode_nms_batch(l, c, priors_cxcywh, img_wh, top_k=200, min_score=0.2, iou_threshold=0.45, nms="hard", sigma=0.5,
-                     keep_score=None):
+def decode_nms_batch(l, c, priors_cxcywh, img_wh, top_k=200, min_score=0.2, iou_threshold=0.45, score="softmax", nms="hard",
+                     sigma=0.5, keep_score=None):
     """l (B,P,4), c (B,P,C), img_wh (B,2) device floats -> (boxes (B,top_k,4), classes (B,top_k) i64, probs (B,top_k),
     prior_ids (B,top_k) i32, count (B,) i32), all on the device, one launch set, no host sync.
-    nms = "linear" / "gaussian": Soft-NMS (probs are the decayed scores; keep_score None = min_score)."""
+    nms = "linear" / "gaussian": Soft-NMS (probs are the decayed scores; keep_score None = min_score).  score: as in `decode_nms`."""
     method = nms_method(nms)
+    smode = score_mode(score)
     _req(l, "l"); _req(c, "c"); _req(priors_cxcywh, "priors"); _req(img_wh, "img_wh")
     b, p, ncls = c.shape
     if tuple(l.shape) != (b, p, 4) or tuple(priors_cxcywh.shape) != (p, 4) or tuple(img_wh.shape) != (b, 2):
@@ -987,6 +1044,13 @@ def decode_nms_batch(l, c, priors_cxcywh, img_wh, top_k=200, min_score=0.2, iou_
     probs = torch.zeros((b, top_k), device=dev, dtype=torch.float32)
     ids = torch.zeros((b, top_k), device=dev, dtype=torch.int32)
     count = torch.zeros((b,), device=dev, dtype=torch.int32)
+    if smode != 0:
+        check(lib.ssd_decode_nms_batch_score(l.data_ptr(), c.data_ptr(), priors_cxcywh.data_ptr(), img_wh.data_ptr(), b, p, ncls,
+                                             float(min_score), float(iou_threshold), int(top_k), boxes.data_ptr(), classes.data_ptr(),
+                                             probs.data_ptr(), ids.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+                                             method, float(sigma), float(min_score if keep_score is None else keep_score), smode),
+              "decode_nms_batch_score")
+        return boxes, classes, probs, ids, count
     if method != 0:
         check(lib.ssd_decode_nms_batch_soft(l.data_ptr(), c.data_ptr(), priors_cxcywh.data_ptr(), img_wh.data_ptr(), b, p, ncls,
                                             float(min_score), float(iou_threshold), int(top_k), boxes.data_ptr(), classes.data_ptr(),
