@@ -108,6 +108,10 @@ def main():
                          "the sigmoid focal loss over every prior; focal also starts the heads from SSD_300.init_conf_prior()")
     ap.add_argument("--focal-alpha", type=float, default=0.25, help="--conf-loss focal: weight of the positives (negative: no weighting)")
     ap.add_argument("--focal-gamma", type=float, default=2.0, help="--conf-loss focal: exponent of the modulating factor")
+    ap.add_argument("--match", choices=("iou", "atss"), default="iou",
+                    help="which priors are positives (Losses.ssd(match=...)): the reference's IoU >= 0.5 rule with one forced prior per "
+                         "box, or ATSS (the candidates of the --atss-topk nearest cells per level above mean + std of their IoUs)")
+    ap.add_argument("--atss-topk", type=int, default=9, help="--match atss: cells per pyramid level and box (1 .. 32)")
     ap.add_argument("--mosaic", type=float, default=0.0, metavar="P",
                     help="compose a sample with probability P of four files, each resized into one quadrant around a random centre "
                          "(mosaic augmentation; feeds from files: implies --decode host unless --decode is given)")
@@ -138,6 +142,8 @@ def main():
     if a.conf_loss == "focal":
         cnn.init_conf_prior()                                 # every prior starts at sigmoid score 0.01 (score with --score sigmoid)
         conf_kw = dict(conf_loss="focal", focal_alpha=a.focal_alpha, focal_gamma=a.focal_gamma)
+    if a.match != "iou":
+        conf_kw.update(match=a.match, atss_topk=a.atss_topk)
     cnn = cnn.to(device)
     biases = [p for n, p in cnn.named_parameters() if p.requires_grad and n.endswith(".bias")]
     not_biases = [p for n, p in cnn.named_parameters() if p.requires_grad and not n.endswith(".bias")]

@@ -553,6 +553,46 @@ int ssd_focal_dense(const float* conf, const int32_t* cls, const uint8_t* ign, i
                     float focal_alpha, float focal_gamma, float* conf_loss, float* dconf, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* ---- MultiBox loss with a choice of matching rule (ATSS, Zhang et al. 2020) ----------
+ * ssd_multibox_loss_focal's arguments, meaning and status codes, plus int match_mode (0 = the IoU rule: ssd_multibox_loss_focal
+ * itself, the same launches, the same bits; topk and the level description are then not looked at), int topk (1 .. 32), int n_levels
+ * (1 .. 8) and two HOST arrays of n_levels ints: level_cells (grid cells of each pyramid level) and level_anchors (priors per cell).
+ * The priors are stored level after level, cell after cell (row-major), the priors of a cell contiguous; sum cells * anchors = P.
+ * match_mode 1, for every box g of an image:
+ *   candidates  in every level the min(topk, cells) cells whose centre -- (cx, cy) of the cell's first prior -- is nearest to
+ *               ((x1 + x2) / 2, (y1 + y2) / 2): squared f32 distance, nearest first, equal distances -> lower cell, NaN last; all
+ *               priors of a chosen cell are candidates, in the order (level, rank of the cell, prior of the cell)
+ *   statistics  IoU of each candidate with g (the matching's f32 op sequence); f64 mean and unbiased variance (0 for n < 2): lane j
+ *               of 64 adds candidates j, j + 64, ... in order, then a butterfly (xor 32, 16, .. 1) adds the 64 partial sums
+ *   accepted    d = (double)iou - mean: d >= 0 && d * d >= var (no square root), and the prior's centre strictly inside g
+ *   conflicts   a prior accepted by several boxes of its image goes to the largest IoU bits, equal -> lower box index
+ * A prior with a box is positive (class and regression target of that box); every other prior is background.  iou_threshold is not
+ * read and there are no forced matches: a box can end with no prior and an image with no positive (its sel bytes are all zero).  A
+ * batch without any positive divides by n_pos = 0 in norm_mode 0 exactly as the other entries do.  Everything behind the assignment
+ * (mining, ignore bytes, loc and conf terms, norm modes) is unchanged.  obj of a non-positive prior is unspecified.
+ * One memset node, the assignment pass (a workgroup per box) and the launches of ssd_multibox_loss_focal with the matching-free
+ * instances of the first kernel.  No float atomics: two calls give the same bits.  The workspace is larger than the other entries'.
+ * Errors: as ssd_multibox_loss_focal; match_mode outside 0 .. 1 is SSD_ERR_BAD_SHAPE; with match_mode 1 null level arrays are
+ * SSD_ERR_NULL, and topk or n_levels out of range, a level with cells or anchors < 1 or levels that do not sum to P are
+ * SSD_ERR_BAD_SHAPE. */
+size_t ssd_multibox_loss_atss_workspace(int bs, int P, int n_gt, int n_ign);
+int ssd_multibox_loss_atss(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                           const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh, const float* priors_xyxy,
+                           int P, int n_classes, float iou_threshold, int neg_pos_ratio, int norm_mode, const float* ign_boxes,
+                           const int32_t* ign_start, int n_ign, float ignore_threshold, int overlap_mode, int loc_mode,
+                           int conf_mode, float focal_alpha, float focal_gamma, int match_mode, int topk, int n_levels,
+                           const int* level_cells, const int* level_anchors, float* losses, int32_t* obj, int32_t* cls,
+                           uint8_t* ign, float* dloc, float* dconf, void* workspace, size_t workspace_bytes, void* stream);
+/* The assignment pass of match_mode 1 alone, launched as ssd_multibox_loss_atss launches it, for tests and tools.  Outputs: assign
+ * (bs,P) int32 global box index or -1; per box (each may be NULL) n_cand int32 candidates, mean / var float64, n_acc int32 accepted
+ * candidates (before conflicts).  workspace: 8 * bs * P bytes rounded up to a multiple of 256, 16-byte aligned.  Status codes in the
+ * order null, shape (bs <= 0, n_gt <= 0, P <= 0 or > 36000, the level rules above), alignment, workspace. */
+size_t ssd_atss_assign_workspace(int bs, int P);
+int ssd_atss_assign(const float* gt_boxes, const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh,
+                    const float* priors_xyxy, int P, int topk, int n_levels, const int* level_cells, const int* level_anchors,
+                    int32_t* assign, int32_t* n_cand, double* mean, double* var, int32_t* n_acc, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ---- decode + per-class NMS + top-k (Losses.py:11-98 inference; Util.py:86-96) ----------
  * l_ (P,4), c_ (P,n_classes) of ONE image, n_classes = conf width C, 2..256 (background = C-1 is never a detection).
  * Outputs (capacity top_k): boxes (top_k,4) xyxy scaled by (img_w,img_h,img_w,img_h), classes int64 (0..C-2), probs f32,

@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import ops
-from .Util import all_images, class_to_label, create_priors_ssd300, create_priors_ssd512, device, xywh_to_xyxy  # noqa: F401
+from .Util import all_images, class_to_label, create_priors_ssd300, create_priors_ssd512, device, prior_levels, xywh_to_xyxy  # noqa: F401
 
 # module-level priors, as reference Losses.py:6-7 (immutable after import)
 ancs_xywh = create_priors_ssd300()
@@ -47,7 +47,7 @@ def _priors_on(dev: torch.device, n_priors: int = 8732):
 class _MultiBoxLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, loc, conf, gt, gt_cls, img_start, norm_mode, ignore=None, loc_loss="l1", conf_loss="ce", focal_alpha=0.25,
-                focal_gamma=2.0):
+                focal_gamma=2.0, match="iou", atss_topk=9):
         pri, pri_xyxy = _priors_on(loc.device, loc.shape[1])
         want = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         kw = {}
@@ -55,6 +55,8 @@ class _MultiBoxLoss(torch.autograd.Function):
             kw = dict(ignore_boxes=ignore[0], ignore_start=ignore[1], ignore_threshold=ignore[2], ignore_overlap=ignore[3])
         if conf_loss != "ce":                            # (the default call stays the call it has always been)
             kw.update(conf_loss=conf_loss, focal_alpha=focal_alpha, focal_gamma=focal_gamma)
+        if match != "iou":                               # the levels of the prior set in use
+            kw.update(match=match, atss_topk=atss_topk, prior_levels=prior_levels(loc.shape[1]))
         out = ops.multibox_loss(loc.detach().contiguous(), conf.detach().contiguous(), gt, gt_cls, img_start, pri, pri_xyxy,
                                 IOU_THRESHOLD, NEG_POS_RATIO, norm_mode, want_grads=want, loc_loss=loc_loss, **kw)
         ctx.dloc, ctx.dconf = out["dloc"], out["dconf"]
@@ -68,7 +70,7 @@ class _MultiBoxLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loc, g_conf, _g_npos):
         # loc_loss depends on loc only, conf_loss on conf only
-        return ctx.dloc * g_loc, ctx.dconf * g_conf, None, None, None, None, None, None, None, None, None
+        return ctx.dloc * g_loc, ctx.dconf * g_conf, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _image_starts(start, dev: torch.device) -> torch.Tensor:
@@ -110,7 +112,8 @@ def _pack_ignore(ignore_bboxs, dev: torch.device):
 
 
 def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = False, loc_loss: str = "l1", conf_loss: str = "ce",
-        focal_alpha: float = 0.25, focal_gamma: float = 2.0, ignore_bboxs=None, ignore_threshold: float = 0.5, ignore_overlap: str = "iou"):
+        focal_alpha: float = 0.25, focal_gamma: float = 2.0, match: str = "iou", atss_topk: int = 9, ignore_bboxs=None,
+        ignore_threshold: float = 0.5, ignore_overlap: str = "iou"):
     """outputs = (loc (bs,8732,4), conf (bs,8732,C)); tr_classes: list of (n_i,) float tensors with values
     0..C-2 (C = conf.shape[-1] = foreground classes + background, 21 for VOC; background = C-1); tr_bboxs: list of
     (n_i,4) xyxy fractional boxes.  Returns (loc_loss, conf_loss) as 0-dim tensors
@@ -132,8 +135,16 @@ def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = Fa
     times the binary cross entropy, focal_alpha in [0, 1] (negative: no alpha weighting), focal_gamma >= 0 -- summed and divided by
     the number of positives (norm_mode 1: the sum); nothing is mined, the background column gets no gradient.  Matching, loc_loss
     and the ignore rule are the same.  Score such a model with `inference*(score="sigmoid")` and start its heads from
-    `SSD_300.init_conf_prior()`."""
+    `SSD_300.init_conf_prior()`.
+    match: "iou" (the reference's rule, the default: IoU >= 0.5 against the prior's best box plus one forced prior per box), or "atss"
+    (Zhang et al. 2020): per box, the priors of the atss_topk (1 .. 32, default 9) nearest cells of every pyramid level are candidates;
+    those whose IoU reaches the mean + standard deviation of the candidates' IoUs and whose centre lies inside the box are the box's
+    positives, and a prior wanted by several boxes goes to the largest IoU.  Nothing is forced: a box may get no prior, an image no
+    positive; a batch without any positive divides by n_pos = 0 in norm_mode 0 (as the default rule would, which cannot get there).
+    Mining, the ignore rule and every loss term are the same."""
     ops.ignore_overlap_mode(ignore_overlap)
+    ops.match_mode(match)
+    atss_topk = ops.atss_topk_value(atss_topk)
     ops.loc_loss_mode(loc_loss)
     ops.conf_loss_mode(conf_loss)
     focal_alpha, focal_gamma = ops.focal_params(focal_alpha, focal_gamma)
@@ -149,7 +160,10 @@ def ssd(outputs, tr_classes, tr_bboxs, norm_mode: int = 0, with_n_pos: bool = Fa
     ignore = None
     if ignore_bboxs is not None:
         ignore = _pack_ignore(ignore_bboxs, loc.device) + (float(ignore_threshold), ignore_overlap)
-    if conf_loss == "ce":
+    if match != "iou":
+        l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode, ignore, loc_loss, conf_loss, focal_alpha,
+                                                   focal_gamma, match, atss_topk)
+    elif conf_loss == "ce":
         l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode, ignore, loc_loss)
     else:
         l_loc, l_conf, n_pos = _MultiBoxLoss.apply(loc, conf, gt, cls, img_start, norm_mode, ignore, loc_loss, conf_loss, focal_alpha,

@@ -81,6 +81,16 @@ def create_priors_ssd512() -> torch.Tensor:
     return torch.tensor(out, dtype=torch.float64).to(torch.float32).clamp_(0, 1)
 
 
+def prior_levels(n_priors: int):
+    """(cells, anchors) of the prior set with `n_priors` priors, per pyramid level: grid cells and priors per cell, in storage order
+    (level after level, cell after cell, the priors of a cell contiguous) -- what `ops.multibox_loss(match="atss")` needs.
+    8732: create_priors_ssd300, 24564: create_priors_ssd512; ValueError for any other count."""
+    for grid, anchors in ((_GRID, ANCHORS_PER_CELL), (_GRID512, ANCHORS_PER_CELL_512)):
+        if sum(g * g * a for g, a in zip(grid, anchors)) == n_priors:
+            return tuple(g * g for g in grid), tuple(anchors)
+    raise ValueError(f"prior_levels: no built-in prior set has {n_priors!r} priors (8732: SSD300, 24564: SSD512)")
+
+
 def xywh_to_xyxy(box: torch.Tensor) -> torch.Tensor:
     """reference Util.py:93-96"""
     return torch.cat((box[:, :2] - box[:, 2:] / 2., box[:, :2] + box[:, 2:] / 2.), dim=1)

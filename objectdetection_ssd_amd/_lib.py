@@ -222,6 +222,11 @@ SIGNATURES = {
                                      _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_focal_dense_workspace": (_Z, [_I, _I]),
     "ssd_focal_dense": (_I, [_P, _P, _P, _I, _I, _I, _F, _I, _F, _F, _P, _P, _P, _Z, _P]),
+    "ssd_multibox_loss_atss_workspace": (_Z, [_I, _I, _I, _I]),
+    "ssd_multibox_loss_atss": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _I, _F, _I, _I, _I, _F, _F, _I, _I, _I,
+                                    _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ssd_atss_assign_workspace": (_Z, [_I, _I]),
+    "ssd_atss_assign": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_decode_nms_workspace": (_Z, [_I, _I]),
     "ssd_decode_nms": (_I, [_P, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ssd_decode_nms_batch_workspace": (_Z, [_I, _I, _I]),

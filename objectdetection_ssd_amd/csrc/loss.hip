@@ -42,6 +42,11 @@
 // summed the four absolute differences, and L3 / L3w write box_term()'s gradient where they wrote +-1/4: one device function for the
 // decode, the four losses and their gradients, so the two finalize kernels cannot drift apart.
 //
+// ATSS matching (ssd_multibox_loss_atss, match_mode 1).  The assignment pass of atss.hip runs in front and leaves
+// one 64-bit key per prior; L1 and L1w are templates on ATSS, whose instances read the key where the others run match_wave (no IoU
+// loop), answer L2's threshold test with +-inf and fill every box's slots of partv / parti with "nothing", so that L2 -- the same
+// kernel -- finds no forced match whatever the workspace held.  The ATSS = false instances are the kernels above, unchanged.
+//
 // Class labels index conf rows: every kernel reads them through class_index(), which keeps any value (negative, >= C - 1, NaN)
 // inside the row.  Labels outside 0 .. C-2 are the caller's error and give unspecified losses, but no access outside the tensors.
 //
@@ -49,6 +54,7 @@
 // (sub, max, min, mul, add, sub, IEEE divide): this file is compiled with
 // -ffp-contract=off and the pragma below keeps a*b+c from being fused.
 #include "common.h"
+#include "atss.h"
 #include <cfloat>
 #pragma clang fp contract(off)
 
@@ -378,6 +384,7 @@ struct ImageArgs {
     int32_t* best_prior; int32_t* obj; int32_t* cls; uint8_t* sel; float* stats;
     int P, C, ratio, NPW; float thr;
     int loc_mode;                                     // loss_image_kernel<., true>: 1 .. 4 = IoU, GIoU, DIoU, CIoU (box_term)
+    const unsigned long long* akey = nullptr;         // ATSS instances of L1 / L1w: [bs][P] keys of the assignment pass (atss.hip)
 };
 
 constexpr int SG = 128;        // GT boxes of an image kept in LDS (more are read from memory: correct, slower)
@@ -460,6 +467,21 @@ __device__ __forceinline__ void match_wave(const ImageArgs& a, const f32x4* sg_b
     }
 }
 
+// L1 / L1w with ATSS (ssd_multibox_loss_atss, match_mode 1): the prior's box is the one the assignment pass gave it (atss.hip: the low
+// word of its key is 0xFFFFFFFF - box), no IoU is computed.  (best, idx) are what L2 reads: +inf with the box, or -inf, against the
+// threshold 0.5 the host puts in place of the caller's.  There are no forced matches, and L2 finds them in partv / parti of a workspace
+// that may hold anything: this wave writes "nothing" (0x7fffffff) for every box of the image into its slot.
+__device__ __forceinline__ void match_assigned(const ImageArgs& a, int i, int s, int e, int p, bool live, int lane, int slot, float& best,
+                                               int& idx) {
+    for (int k = s + lane; k < e; k += 64) {
+        a.partv[(size_t)k * a.NPW + slot] = 0.f;
+        a.parti[(size_t)k * a.NPW + slot] = 0x7fffffff;
+    }
+    const unsigned long long key = live ? a.akey[(size_t)i * a.P + p] : 0ull;
+    idx = key != 0ull ? (int)(0xFFFFFFFFu - (uint32_t)key) : s;
+    best = key != 0ull ? INFINITY : -INFINITY;
+}
+
 // A conf row of C <= 256 floats across one wave: lane l holds columns l, l + 64, l + 128, l + 192 (-inf past the end).  Returns the
 // row's max and sum of exp(x - max) (butterflies: the same value in every lane, the same bits on every run).
 struct RowStats { float m, se; };
@@ -487,11 +509,12 @@ __device__ __forceinline__ float col_wave(const float v[4], int c) {         // 
 }
 
 // L1: grid (ceil(P / 256), bs), 256 threads; a wave owns 64 consecutive priors of image blockIdx.y
-template <bool IGN>
+// ATSS: match_assigned in match_wave's place (no box is staged); false is the kernel as it was.
+template <bool IGN, bool ATSS = false>
 __global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a, const IgnArgs g) {
     extern __shared__ __attribute__((aligned(16))) float stage_all[];       // [4][64 * C] conf rows
-    __shared__ f32x4 sg_box[SG];
-    __shared__ float sg_area[SG];
+    __shared__ f32x4 sg_box[ATSS ? 1 : SG];
+    __shared__ float sg_area[ATSS ? 1 : SG];
     __shared__ int sg_cls[SG];
     __shared__ f32x4 si_box[IGN ? SG : 1];
     __shared__ float si_area[IGN ? SG : 1];
@@ -500,9 +523,11 @@ __global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a, cons
     const int P = a.P, C = a.C;
     const int ns = e - s < SG ? e - s : SG;
     for (int t = tid; t < ns; t += 256) {
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
-        sg_box[t] = g4;
-        sg_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
+        if constexpr (!ATSS) {
+            const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
+            sg_box[t] = g4;
+            sg_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
+        }
         sg_cls[t] = class_index(a.gt_cls[s + t], C);
     }
     if (IGN) stage_ignore(g, i, tid, si_box, si_area);
@@ -519,7 +544,8 @@ __global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a, cons
     const bool live = lane < rows;
     float best;
     int idx;
-    match_wave(a, sg_box, sg_area, s, e, p, live, lane, blockIdx.x * 4 + wave, best, idx);
+    if constexpr (ATSS) match_assigned(a, i, s, e, p, live, lane, blockIdx.x * 4 + wave, best, idx);
+    else match_wave(a, sg_box, sg_area, s, e, p, live, lane, blockIdx.x * 4 + wave, best, idx);
     if (live) {
         const size_t ip = (size_t)i * P + p;
         // cross entropy against the class the prior has unless a box claims it in L2 (Losses.py:164-167: those few are redone there);
@@ -539,10 +565,11 @@ __global__ __launch_bounds__(256) void loss_prior_kernel(const ImageArgs a, cons
 
 // L1w (64 < C <= 256): L1 without the row staging; grid (ceil(P / 256), bs), 256 threads, a wave per 64 consecutive priors.
 // FOCAL (conf_mode 1, any C): the matching alone -- no conf row is read, cebg is not written; false is the kernel as it was.
-template <bool IGN, bool FOCAL = false>
+// ATSS: as in L1.
+template <bool IGN, bool FOCAL = false, bool ATSS = false>
 __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a, const IgnArgs g) {
-    __shared__ f32x4 sg_box[SG];
-    __shared__ float sg_area[SG];
+    __shared__ f32x4 sg_box[ATSS ? 1 : SG];
+    __shared__ float sg_area[ATSS ? 1 : SG];
     __shared__ int sg_cls[SG];
     __shared__ f32x4 si_box[IGN ? SG : 1];
     __shared__ float si_area[IGN ? SG : 1];
@@ -551,9 +578,11 @@ __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a,
     const int P = a.P, C = a.C;
     const int ns = e - s < SG ? e - s : SG;
     for (int t = tid; t < ns; t += 256) {
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
-        sg_box[t] = g4;
-        sg_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
+        if constexpr (!ATSS) {
+            const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.gt + (size_t)(s + t) * 4);
+            sg_box[t] = g4;
+            sg_area[t] = (g4[2] - g4[0]) * (g4[3] - g4[1]);
+        }
         sg_cls[t] = class_index(a.gt_cls[s + t], C);
     }
     if (IGN) stage_ignore(g, i, tid, si_box, si_area);
@@ -564,7 +593,8 @@ __global__ __launch_bounds__(256) void loss_prior_wide_kernel(const ImageArgs a,
     const bool live = lane < rows;
     float best;
     int idx;
-    match_wave(a, sg_box, sg_area, s, e, p, live, lane, blockIdx.x * 4 + wave, best, idx);
+    if constexpr (ATSS) match_assigned(a, i, s, e, p, live, lane, blockIdx.x * 4 + wave, best, idx);
+    else match_wave(a, sg_box, sg_area, s, e, p, live, lane, blockIdx.x * 4 + wave, best, idx);
     const int c = !live || best < a.thr ? C - 1 : (idx - s < SG ? sg_cls[idx - s] : class_index(a.gt_cls[idx], C));
     // cross entropy (torch log_softmax order: (x - max) - log(sum exp(x - max))), a row at a time, two rows' loads in flight
     float ce = 0.f;
@@ -1132,10 +1162,11 @@ LossWs carve(void* ws, int bs, int P, int n_gt) {
 }
 
 // L1 (or L1w) and L2 of the three-launch form; IGN = false, BOX = false is what ssd_multibox_loss has always launched
-template <bool IGN, bool BOX>
+// ATSS picks the instances of L1 / L1w that read the assignment (L2 is the same kernel); false launches what it always did
+template <bool IGN, bool BOX, bool ATSS = false>
 int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, hipStream_t st, bool focal) {
     if (focal) {                                    // the matching-only instances: nothing staged per class or per prior, any C
-        hipLaunchKernelGGL((loss_prior_wide_kernel<IGN, true>), dim3(NB, bs), dim3(256), 0, st, ia, ga);
+        hipLaunchKernelGGL((loss_prior_wide_kernel<IGN, true, ATSS>), dim3(NB, bs), dim3(256), 0, st, ia, ga);
         SSD_CHECK_LAUNCH();
         hipLaunchKernelGGL((loss_image_kernel<IGN, BOX, true>), dim3(bs), dim3(1024), 0, st, ia, ga);
         SSD_CHECK_LAUNCH();
@@ -1147,7 +1178,7 @@ int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, h
     static std::atomic<unsigned long long> raised_l12{0};     // one bit per device (common.h); one word per instance of this template
     int dev;
     if ((l1_lds > 48 * 1024 || l2_lds > 48 * 1024) && ssd_attr_needed(raised_l12, dev)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(loss_prior_kernel<IGN>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(loss_prior_kernel<IGN, ATSS>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) !=
                 hipSuccess ||
             hipFuncSetAttribute(reinterpret_cast<const void*>(loss_image_kernel<IGN, BOX>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
                 hipSuccess)
@@ -1155,9 +1186,9 @@ int launch_prior_image(const ImageArgs& ia, const IgnArgs& ga, int bs, int NB, h
         ssd_attr_done(raised_l12, dev);
     }
     if (wide_rows)
-        hipLaunchKernelGGL(loss_prior_wide_kernel<IGN>, dim3(NB, bs), dim3(256), 0, st, ia, ga);
+        hipLaunchKernelGGL((loss_prior_wide_kernel<IGN, false, ATSS>), dim3(NB, bs), dim3(256), 0, st, ia, ga);
     else
-        hipLaunchKernelGGL(loss_prior_kernel<IGN>, dim3(NB, bs), dim3(256), l1_lds, st, ia, ga);
+        hipLaunchKernelGGL((loss_prior_kernel<IGN, ATSS>), dim3(NB, bs), dim3(256), l1_lds, st, ia, ga);
     SSD_CHECK_LAUNCH();
     hipLaunchKernelGGL((loss_image_kernel<IGN, BOX>), dim3(bs), dim3(1024), l2_lds, st, ia, ga);
     SSD_CHECK_LAUNCH();
@@ -1206,6 +1237,7 @@ struct LossCall {
     bool with_ign; const float* ign_boxes; const int32_t* ign_start; int n_ign; float ignore_threshold; int overlap_mode;
     int loc_mode;
     int conf_mode = 0; float focal_alpha = 0.25f, focal_gamma = 2.f;      // ssd_multibox_loss_focal: 1 = sigmoid focal classification
+    int match_mode = 0; int level_status = SSD_OK; AtssLevels levels{};   // ssd_multibox_loss_atss: 1 = ATSS; ssd_internal_atss_levels' verdict
     float* losses; int32_t* obj; int32_t* cls; uint8_t* ign; float* dloc; float* dconf;
     void* workspace; size_t workspace_bytes; hipStream_t stream;
 };
@@ -1220,16 +1252,19 @@ int check_loss_call(const LossCall& c) {
         return SSD_ERR_NULL;
     if ((c.dloc == nullptr) != (c.dconf == nullptr)) return SSD_ERR_NULL;
     if (c.with_ign && (!c.ign_start || !c.ign || (c.n_ign > 0 && !c.ign_boxes))) return SSD_ERR_NULL;
+    if (c.match_mode != 0 && c.level_status == SSD_ERR_NULL) return SSD_ERR_NULL;
     if (c.bs <= 0 || c.n_gt < c.bs || c.P <= 0 || c.P > 36000 || c.n_classes < 2 || c.n_classes > 256 || c.neg_pos_ratio < 0 ||
         (c.norm_mode != 0 && c.norm_mode != 1) || c.loc_mode < 0 || c.loc_mode > 4)
         return SSD_ERR_BAD_SHAPE;
     if ((c.conf_mode != 0 && c.conf_mode != 1) || !focal_params_ok(c.focal_alpha, c.focal_gamma)) return SSD_ERR_BAD_SHAPE;
     if (c.with_ign && (c.n_ign < 0 || (c.overlap_mode != 0 && c.overlap_mode != 1))) return SSD_ERR_BAD_SHAPE;
+    if ((c.match_mode != 0 && c.match_mode != 1) || (c.match_mode == 1 && c.level_status != SSD_OK)) return SSD_ERR_BAD_SHAPE;
     if (!ssd_aligned16(c.loc) || !ssd_aligned16(c.priors_cxcywh) || !ssd_aligned16(c.priors_xyxy) || (c.dloc && !ssd_aligned16(c.dloc)) ||
         !ssd_aligned16(c.workspace))
         return SSD_ERR_ALIGN;
     if (c.with_ign && c.n_ign > 0 && !ssd_aligned16(c.ign_boxes)) return SSD_ERR_ALIGN;
-    if (c.workspace_bytes < carve(nullptr, c.bs, c.P, c.n_gt).bytes) return SSD_ERR_WORKSPACE;
+    if (c.workspace_bytes < carve(nullptr, c.bs, c.P, c.n_gt).bytes + (c.match_mode == 1 ? ssd_internal_atss_key_bytes(c.bs, c.P) : 0))
+        return SSD_ERR_WORKSPACE;
     return SSD_OK;
 }
 
@@ -1247,16 +1282,32 @@ int launch_focal_dense(const FocalArgs& za, hipStream_t st) {
 int run_loss(const LossCall& c) {
     const LossWs w = carve(c.workspace, c.bs, c.P, c.n_gt);
     const int NB = ssd_cdiv(c.P, LB);
+    // match_mode 1: the keys lie behind what every entry has; L1 / L1w answer L2's threshold test with +-inf, against 0.5 whatever
+    // the caller left in iou_threshold
+    const bool atss = c.match_mode == 1;
+    unsigned long long* const keys = atss ? reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c.workspace) + w.bytes) : nullptr;
+    if (atss) {
+        const int rk = ssd_internal_atss_keys(c.gt_boxes, c.img_start, c.bs, c.n_gt, c.priors_cxcywh, c.priors_xyxy, c.P, c.levels, keys,
+                                              nullptr, nullptr, nullptr, nullptr, c.stream);
+        if (rk != SSD_OK) return rk;
+    }
     const ImageArgs ia{c.loc, c.conf, c.gt_boxes, c.gt_classes, c.img_start, c.priors_cxcywh, c.priors_xyxy, w.partv, w.parti, w.bestv,
-                       w.neg, w.best_prior, c.obj, c.cls, w.sel, w.stats, c.P, c.n_classes, c.neg_pos_ratio, NB * 4, c.iou_threshold,
-                       c.loc_mode};
+                       w.neg, w.best_prior, c.obj, c.cls, w.sel, w.stats, c.P, c.n_classes, c.neg_pos_ratio, NB * 4,
+                       atss ? 0.5f : c.iou_threshold, c.loc_mode, keys};
     const IgnArgs ga = c.with_ign ? IgnArgs{c.ign_boxes, c.ign_start, c.ign, c.ignore_threshold, c.overlap_mode}
                                   : IgnArgs{nullptr, nullptr, nullptr, 0.f, 0};
     const FinalArgs fa{c.loc, c.conf, c.gt_boxes, c.priors_cxcywh, c.obj, c.cls, w.sel, w.stats, c.losses, c.dloc, c.dconf, c.P,
                        c.n_classes, c.bs, c.norm_mode, c.loc_mode, w.part};
     const bool box = c.loc_mode != 0, focal = c.conf_mode != 0;
     int rc;
-    if (c.with_ign)
+    if (atss) {
+        if (c.with_ign)
+            rc = box ? launch_prior_image<true, true, true>(ia, ga, c.bs, NB, c.stream, focal)
+                     : launch_prior_image<true, false, true>(ia, ga, c.bs, NB, c.stream, focal);
+        else
+            rc = box ? launch_prior_image<false, true, true>(ia, ga, c.bs, NB, c.stream, focal)
+                     : launch_prior_image<false, false, true>(ia, ga, c.bs, NB, c.stream, focal);
+    } else if (c.with_ign)
         rc = box ? launch_prior_image<true, true>(ia, ga, c.bs, NB, c.stream, focal)
                  : launch_prior_image<true, false>(ia, ga, c.bs, NB, c.stream, focal);
     else
@@ -1395,6 +1446,33 @@ extern "C" int ssd_multibox_loss_focal(const float* loc, const float* conf, cons
                      .ignore_threshold = ignore_threshold, .overlap_mode = overlap_mode, .loc_mode = loc_mode, .conf_mode = conf_mode,
                      .focal_alpha = focal_alpha, .focal_gamma = focal_gamma, .losses = losses, .obj = obj, .cls = cls, .ign = ign,
                      .dloc = dloc, .dconf = dconf, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = (hipStream_t)stream};
+    const int bad = check_loss_call(c);
+    return bad != SSD_OK ? bad : run_loss(c);
+}
+
+// The loss with a choice of matching rule beside ssd_multibox_loss_focal's options: match_mode 0 is that entry, launch for launch;
+// match_mode 1 runs the ATSS assignment pass (atss.hip) in front and the instances of L1 / L1w that read it
+extern "C" size_t ssd_multibox_loss_atss_workspace(int bs, int P, int n_gt, int n_ign) {
+    const size_t base = ssd_multibox_loss_ignore_workspace(bs, P, n_gt, n_ign);
+    return base ? base + ssd_internal_atss_key_bytes(bs, P) : 0;
+}
+
+extern "C" int ssd_multibox_loss_atss(const float* loc, const float* conf, const float* gt_boxes, const float* gt_classes,
+                                      const int32_t* img_start, int bs, int n_gt, const float* priors_cxcywh, const float* priors_xyxy,
+                                      int P, int n_classes, float iou_threshold, int neg_pos_ratio, int norm_mode, const float* ign_boxes,
+                                      const int32_t* ign_start, int n_ign, float ignore_threshold, int overlap_mode, int loc_mode,
+                                      int conf_mode, float focal_alpha, float focal_gamma, int match_mode, int topk, int n_levels,
+                                      const int* level_cells, const int* level_anchors, float* losses, int32_t* obj, int32_t* cls,
+                                      uint8_t* ign, float* dloc, float* dconf, void* workspace, size_t workspace_bytes, void* stream) {
+    LossCall c{.loc = loc, .conf = conf, .gt_boxes = gt_boxes, .gt_classes = gt_classes, .img_start = img_start, .bs = bs, .n_gt = n_gt,
+               .priors_cxcywh = priors_cxcywh, .priors_xyxy = priors_xyxy, .P = P, .n_classes = n_classes,
+               .iou_threshold = iou_threshold, .neg_pos_ratio = conf_mode == 1 && neg_pos_ratio < 0 ? 0 : neg_pos_ratio,
+               .norm_mode = norm_mode, .with_ign = ign_start != nullptr, .ign_boxes = ign_boxes, .ign_start = ign_start, .n_ign = n_ign,
+               .ignore_threshold = ignore_threshold, .overlap_mode = overlap_mode, .loc_mode = loc_mode, .conf_mode = conf_mode,
+               .focal_alpha = focal_alpha, .focal_gamma = focal_gamma, .match_mode = match_mode, .losses = losses, .obj = obj, .cls = cls,
+               .ign = ign, .dloc = dloc, .dconf = dconf, .workspace = workspace, .workspace_bytes = workspace_bytes,
+               .stream = (hipStream_t)stream};
+    if (match_mode != 0) c.level_status = ssd_internal_atss_levels(P, topk, n_levels, level_cells, level_anchors, c.levels);
     const int bad = check_loss_call(c);
     return bad != SSD_OK ? bad : run_loss(c);
 }

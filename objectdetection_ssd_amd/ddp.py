@@ -606,12 +606,16 @@ class GraphedTrainStep:
     conf_loss / focal_alpha / focal_gamma (default "ce": the captured graph is the one it always was): the classification term of
     `Losses.ssd(conf_loss=...)`; "focal" is the sigmoid focal loss, its five launches captured like the three of "ce".  Attributes too.
 
+    match / atss_topk (default "iou": the captured graph is the one it always was): the matching rule of `Losses.ssd(match=...)`; "atss"
+    captures the key memset and the assignment pass in front of the loss kernels, the level description of the net's prior set baked
+    in.  Attributes too; changing one re-captures.
+
     `__call__(x, classes, boxes, ignore=None)` -> (loc_sum, conf_sum, n_pos): 0-dim views of a static device tensor holding this rank's
     un-normalised loss sums and positive count (`Losses.ssd(..., norm_mode=1, with_n_pos=True)`), overwritten by the next call."""
 
     def __init__(self, net, trainer: FlatSGDDataParallel, max_boxes_per_image: int = 8, warmup: int = 2, two_streams: bool = True,
                  loc_loss: str = "l1", conf_loss: str = "ce", focal_alpha: float = 0.25, focal_gamma: float = 2.0,
-                 max_ignore_per_image: int = 0):
+                 match: str = "iou", atss_topk: int = 9, max_ignore_per_image: int = 0):
         if trainer.grad_dtype == torch.bfloat16 and trainer.world > 1:       # (before anything below touches the trainer or the net)
             raise ValueError("GraphedTrainStep exchanges the f32 gradient buffer in one all-reduce behind the replay: a trainer built with "
                              "grad_dtype=torch.bfloat16 would silently send f32 -- build it with the f32 default, or step it eagerly")
@@ -626,6 +630,8 @@ class GraphedTrainStep:
         ops.conf_loss_mode(conf_loss)
         self.conf_loss = conf_loss
         self.focal_alpha, self.focal_gamma = ops.focal_params(focal_alpha, focal_gamma)
+        ops.match_mode(match)
+        self.match, self.atss_topk = match, ops.atss_topk_value(atss_topk)
         self.two_streams = bool(two_streams)
         self.graph = None
         self._sig = None
@@ -716,6 +722,12 @@ class GraphedTrainStep:
             return {}
         return dict(conf_loss=self.conf_loss, focal_alpha=self.focal_alpha, focal_gamma=self.focal_gamma)
 
+    def _match_kw(self):
+        """the matching arguments of `Losses.ssd`; none for "iou", whose call stays the one it has always been"""
+        if self.match == "iou":
+            return {}
+        return dict(match=self.match, atss_topk=self.atss_topk)
+
     def _body(self, with_sgd: bool):
         from . import Losses
         S, net, tr = self._static, self.net, self.trainer
@@ -727,6 +739,8 @@ class GraphedTrainStep:
         if self.max_ignore_per_image > 0:
             kw = dict(ignore_boxes=S["ign"], ignore_start=S["ign_start"], ignore_threshold=self.ignore_threshold,
                       ignore_overlap=self.ignore_overlap)
+        if self.match != "iou":
+            kw.update(self._match_kw(), prior_levels=Losses.prior_levels(loc.shape[1]))
         out = ops.multibox_loss(loc, conf, S["gt"], S["cls"], S["start"], pri, pri_xyxy, Losses.IOU_THRESHOLD, Losses.NEG_POS_RATIO, 1,
                                 want_grads=True, loc_loss=self.loc_loss, **kw, **self._conf_kw())
         need = {n: bool(P[n].requires_grad) for n in eng.names}
@@ -744,7 +758,7 @@ class GraphedTrainStep:
         return tuple((g["lr"], g.get("momentum"), g["weight_decay"], g.get("betas"), g.get("eps")) for g in tr.param_groups) + (
             tr.optimizer_kind, tr.world, eng.overlap_tail, eng.defer_tail_wgrad) + tr._clip_settings() + tr._sched_settings() + eng.schedule_key() + (
             (self.ignore_threshold, self.ignore_overlap) if self.max_ignore_per_image > 0 else ()) + (self.loc_loss,) + tuple(
-            self._conf_kw().values())
+            self._conf_kw().values()) + tuple(self._match_kw().values())
 
     def _eager(self, x, classes, boxes, ignore=None):
         from . import Losses
@@ -755,7 +769,8 @@ class GraphedTrainStep:
         if self.max_ignore_per_image > 0:
             kw = dict(ignore_bboxs=self._ignore_lists(ignore, x.shape[0]), ignore_threshold=self.ignore_threshold,
                       ignore_overlap=self.ignore_overlap)
-        l1, l2, n_pos = Losses.ssd((loc, conf), classes, boxes, norm_mode=1, with_n_pos=True, loc_loss=self.loc_loss, **kw, **self._conf_kw())
+        l1, l2, n_pos = Losses.ssd((loc, conf), classes, boxes, norm_mode=1, with_n_pos=True, loc_loss=self.loc_loss, **kw, **self._conf_kw(),
+                                   **self._match_kw())
         (l1 + l2).backward()
         tr.reduce_and_step(n_pos)
         return l1.detach(), l2.detach(), n_pos

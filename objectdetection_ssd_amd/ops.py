@@ -899,9 +899,44 @@ def focal_params(focal_alpha, focal_gamma):
     return alpha, gamma
 
 
+MATCHES = {"iou": 0, "atss": 1}
+
+
+def match_mode(name):
+    """0 / 1 for "iou" / "atss" (the `match_mode` of the C ABI); ValueError for anything else."""
+    try:
+        return MATCHES[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"match must be one of {', '.join(map(repr, MATCHES))}, not {name!r}") from None
+
+
+def atss_topk_value(atss_topk):
+    """atss_topk as an int in 1 .. 32; ValueError otherwise."""
+    if isinstance(atss_topk, bool) or not isinstance(atss_topk, int) or not 1 <= atss_topk <= 32:
+        raise ValueError(f"atss_topk must be an integer in 1 .. 32, not {atss_topk!r}")
+    return atss_topk
+
+
+def atss_levels(prior_levels, n_priors):
+    """prior_levels = (cells, anchors), two equally long sequences of 1 .. 8 positive ints with sum(cells * anchors) == n_priors
+    (`Util.prior_levels`) -> two ctypes int arrays for the C ABI; ValueError otherwise."""
+    try:
+        cells, anchors = prior_levels
+        cells, anchors = [int(v) for v in cells], [int(v) for v in anchors]
+    except (TypeError, ValueError):
+        raise ValueError(f"prior_levels must be (cells, anchors), two sequences of ints, not {prior_levels!r}") from None
+    if len(cells) != len(anchors) or not 1 <= len(cells) <= 8:
+        raise ValueError(f"prior_levels must describe 1 .. 8 levels, cells and anchors equally long, not {prior_levels!r}")
+    if min(cells) < 1 or min(anchors) < 1 or sum(c * a for c, a in zip(cells, anchors)) != n_priors:
+        raise ValueError(f"prior_levels {prior_levels!r} does not sum to the {n_priors} priors")
+    arr = C.c_int * len(cells)
+    return arr(*cells), arr(*anchors)
+
+
 def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, priors_xyxy, iou_threshold=0.5,
                   neg_pos_ratio=3, norm_mode=0, want_grads=True, loc_loss="l1", conf_loss="ce", focal_alpha=0.25, focal_gamma=2.0,
-                  ignore_boxes=None, ignore_start=None, ignore_threshold=0.5, ignore_overlap="iou"):
+                  match="iou", atss_topk=9, prior_levels=None, ignore_boxes=None, ignore_start=None, ignore_threshold=0.5,
+                  ignore_overlap="iou"):
     """-> dict(losses (3,), obj (bs,P) i32, cls (bs,P) i32, dloc, dconf).  `ssd_multibox_loss_box` serves every option; the call without any goes
     to `ssd_multibox_loss`, the same host path.
     ignore_boxes (n_ign, 4) fractional xyxy with ignore_start (bs + 1,) int32 prefix offsets (both on the device; n_ign may be 0):
@@ -916,8 +951,18 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
     one-against-all logits and losses[1] is the sum over every prior that is not ignored and every foreground column of
     alpha_t (1 - p_t)^focal_gamma BCE (torchvision's `sigmoid_focal_loss`; focal_alpha < 0: no alpha weighting), divided by n_pos
     (norm_mode 1: the sum); dconf its gradient, zero in the background column; nothing is mined and neg_pos_ratio is not read
-    (`ssd_multibox_loss_focal`).  Matching, losses[0], losses[2], dloc and "ign" are those of "ce"."""
+    (`ssd_multibox_loss_focal`).  Matching, losses[0], losses[2], dloc and "ign" are those of "ce".
+    match: "iou" (the reference's rule: IoU >= iou_threshold against the prior's best box, plus one forced prior per box), or "atss"
+    (`ssd_multibox_loss_atss`): per box the priors of the atss_topk (1 .. 32) nearest cells of every level are
+    candidates, those with IoU >= mean + std of the candidates' IoUs and their centre inside the box are its positives, a prior wanted
+    by several boxes goes to the largest IoU.  It needs prior_levels = (cells, anchors) per pyramid level (`Util.prior_levels`);
+    iou_threshold is not read, nothing is forced: a box may get no prior and an image no positive (a batch without any positive
+    divides by n_pos = 0 in norm_mode 0, as every entry does).  Everything behind the assignment is unchanged."""
     mode = ignore_overlap_mode(ignore_overlap)
+    mmode = match_mode(match)
+    topk = atss_topk_value(atss_topk)
+    if mmode and prior_levels is None:
+        raise ValueError('multibox_loss: match="atss" needs prior_levels (Util.prior_levels)')
     loc_mode = loc_loss_mode(loc_loss)
     conf_mode = conf_loss_mode(conf_loss)
     alpha, gamma = focal_params(focal_alpha, focal_gamma)
@@ -936,9 +981,10 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
         n_ign = ignore_boxes.shape[0]
         if tuple(ignore_boxes.shape) != (n_ign, 4) or ignore_start.numel() != bs + 1:
             raise ValueError("multibox_loss ignore shapes")
+    levels = atss_levels(prior_levels, p) if mmode else None
     lib = _lib.load()
     dev = loc.device
-    ws = workspace(lib.ssd_multibox_loss_box_workspace(bs, p, n_gt, n_ign), dev, "loss")
+    ws = workspace((lib.ssd_multibox_loss_atss_workspace if mmode else lib.ssd_multibox_loss_box_workspace)(bs, p, n_gt, n_ign), dev, "loss")
     out = dict(losses=torch.empty((3,), device=dev, dtype=torch.float32),
                obj=torch.empty((bs, p), device=dev, dtype=torch.int32),
                cls=torch.empty((bs, p), device=dev, dtype=torch.int32),
@@ -950,7 +996,11 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
             priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, ncls, float(iou_threshold), int(neg_pos_ratio), int(norm_mode))
     outs = (out["losses"].data_ptr(), out["obj"].data_ptr(), out["cls"].data_ptr())
     tail = (_ptr(out["dloc"]), _ptr(out["dconf"]), ws.data_ptr(), ws.numel(), _stream())
-    if conf_mode != 0:
+    if mmode != 0:
+        check(lib.ssd_multibox_loss_atss(*head, ignore_boxes.data_ptr() if n_ign else None, _ptr(ignore_start), n_ign,
+                                         float(ignore_threshold), mode, loc_mode, conf_mode, alpha, gamma, mmode, topk, len(levels[0]),
+                                         levels[0], levels[1], *outs, _ptr(out.get("ign")), *tail), "multibox_loss_atss")
+    elif conf_mode != 0:
         check(lib.ssd_multibox_loss_focal(*head, ignore_boxes.data_ptr() if n_ign else None, _ptr(ignore_start), n_ign,
                                           float(ignore_threshold), mode, loc_mode, conf_mode, alpha, gamma, *outs, _ptr(out.get("ign")),
                                           *tail), "multibox_loss_focal")
@@ -960,6 +1010,28 @@ def multibox_loss(loc, conf, gt_boxes, gt_classes, img_start, priors_cxcywh, pri
         check(lib.ssd_multibox_loss_box(*head, ignore_boxes.data_ptr() if n_ign else None, _ptr(ignore_start), n_ign,
                                         float(ignore_threshold), mode, loc_mode, *outs, _ptr(out.get("ign")), *tail),
               "multibox_loss_box" if loc_mode else "multibox_loss_ignore")
+    return out
+
+
+def atss_assign(gt_boxes, img_start, priors_cxcywh, priors_xyxy, prior_levels, atss_topk=9):
+    """The assignment pass of `multibox_loss(match="atss")` alone (`ssd_atss_assign`) -> dict(assign (bs,P) i32 global box index or -1,
+    n_cand (n_gt,) i32 candidates per box, mean / var (n_gt,) f64 of their IoUs, n_acc (n_gt,) i32 candidates that passed the
+    threshold and the centre test, before conflicts)."""
+    topk = atss_topk_value(atss_topk)
+    _req(gt_boxes, "gt_boxes"); _req(img_start, "img_start", torch.int32); _req(priors_cxcywh, "priors"); _req(priors_xyxy, "priors_xyxy")
+    bs, n_gt, p = img_start.numel() - 1, gt_boxes.shape[0], priors_cxcywh.shape[0]
+    if bs < 1 or n_gt < 1 or tuple(gt_boxes.shape) != (n_gt, 4) or tuple(priors_cxcywh.shape) != (p, 4) or tuple(priors_xyxy.shape) != (p, 4):
+        raise ValueError("atss_assign shapes")
+    cells, anchors = atss_levels(prior_levels, p)
+    lib = _lib.load()
+    dev = gt_boxes.device
+    ws = workspace(lib.ssd_atss_assign_workspace(bs, p), dev, "atss")
+    out = dict(assign=torch.empty((bs, p), device=dev, dtype=torch.int32), n_cand=torch.empty((n_gt,), device=dev, dtype=torch.int32),
+               mean=torch.empty((n_gt,), device=dev, dtype=torch.float64), var=torch.empty((n_gt,), device=dev, dtype=torch.float64),
+               n_acc=torch.empty((n_gt,), device=dev, dtype=torch.int32))
+    check(lib.ssd_atss_assign(gt_boxes.data_ptr(), img_start.data_ptr(), bs, n_gt, priors_cxcywh.data_ptr(), priors_xyxy.data_ptr(), p, topk,
+                              len(cells), cells, anchors, out["assign"].data_ptr(), out["n_cand"].data_ptr(), out["mean"].data_ptr(),
+                              out["var"].data_ptr(), out["n_acc"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "atss_assign")
     return out
 
 
